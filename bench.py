@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the sequential leg-IK hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--detail] [--legs all]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--detail]] [--legs all]
 
 Metric (BASELINE.json): leg-IK solves/s, one solve = one (frame, leg) = 4 stage sub-solves -> 7 joint angles + the stage-4
 forward kinematics.  Workload: BASELINE config 3, "synthetic 1M frames x 6 legs, random in-workspace target key points,
@@ -9,11 +9,15 @@ forward kinematics.  Workload: BASELINE config 3, "synthetic 1M frames x 6 legs,
 of a sequence is warm-started from frame t-1: the reference's semantics, examples/example_leg_inv_kinematics_parallel.py:143-198
 applied to many recordings), 6 legs each = 93,750 chains; rank r solves sequences [r S/N, (r+1) S/N) (`--scaling strong`, the
 default; `weak` = 1M frames per GPU).  A step = one pass of the hot path over the rank's batch, inputs resident in HBM;
-consecutive steps overlap on HIP streams (`--streams 0`: the depth is calibrated over the very region that is measured).
+consecutive steps overlap on HIP streams (`--streams 0`: the depth is calibrated over the region that is measured, <= 100 steps).
 
-OUTPUT.  The LAST line of stdout is ONE compact JSON object (< 4 KB: `compact_line`) -- the contract's keys, `roofline`,
-`cpu_baseline`, `parity_max_abs_dtheta`, `value_single_job`, `value_smooth` and, at N > 1, `multi_gpu`.  The full record (every
-calibration candidate, the VALU issue floor, per-rank times, `--detail` legs) goes to `bench_detail.json` and to stderr.
+A plain run: set-up, depth calibration, warm-up, the K timed steps, their bit check against a lone launch, the line.  `--full`
+(N = 1; `--detail` implies it) adds the single-job rate, the other variant, parity vs the reference fixtures, the CPU baseline.
+`--dump-outputs DIR`: angles + FK of the last timed step (a fixed, seeded sample of sequences) as float64 .npy, < 64 MB in all.
+
+OUTPUT.  The LAST line of stdout is ONE compact JSON object (< 4 KB: `compact_line`) -- the contract's keys, `roofline`, with
+`--full` `cpu_baseline`, `parity_max_abs_dtheta`, `value_single_job`, `value_smooth` and, at N > 1, `multi_gpu`.  The full record
+(every calibration candidate, the VALU issue floor, per-rank times, `--detail` legs) goes to `bench_detail.json` and to stderr.
 
 N > 1: started by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (one rank per GPU) or plainly as
 `python bench.py --gpus N`, in which case this process only LAUNCHES that command as a child, relays rank 0's line and exits
@@ -100,11 +104,10 @@ if __name__ == "__main__":
     launch_ranks_if_needed(sys.argv[1:])
     set_runtime_env()
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import bench_support as bs  # noqa: E402
-from bench_support import BYTES_PATH, BYTES_STAGE, FP64_VECTOR_PEAK_TF, HBM_PEAK_GBS, Batch  # noqa: E402
+from bench_support import BYTES_PATH, FP64_VECTOR_PEAK_TF, HBM_PEAK_GBS, Batch  # noqa: E402
 from seqikpy_amd import _lib, runtime_env, sharding, synthetic  # noqa: E402
 
 LINE_LIMIT = 4096        # bytes of the compact line (the driver's parser lost a 26 KB line in round 5)
@@ -131,7 +134,9 @@ def parse(argv=None):
                          "-1 (default) = 0 with an explicit --streams, calibrated together with the depth otherwise")
     ap.add_argument("--staged", action="store_true", help="one launch per stage (SeqikOptions.reserved[1] = 1) instead of the single launch")
     ap.add_argument("--streams", type=int, default=0, help="HIP streams the steps are issued on round-robin; 0 (default) = calibrated in the run")
-    ap.add_argument("--detail", action="store_true", help="N = 1: also run the legs of bench_extras.py (other configs, parity report, shares)")
+    ap.add_argument("--full", action="store_true", help="N = 1: also the single-job rate, the other variant, parity and the CPU baseline")
+    ap.add_argument("--detail", action="store_true", help="N = 1, implies --full: also the legs of bench_extras.py (other configs, parity report, shares)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the angles / FK of the last timed step (seeded sample, float64 .npy) to DIR")
     ap.add_argument("--legs", default="default", choices=["default", "all"], help="N > 1: `all` adds the legs of bench_extras.py")
     ap.add_argument("--one-recording", action="store_true", help="config 3 as ONE recording, frame-sharded over the ranks (bench_extras.py)")
     ap.add_argument("--detail-path", default=os.path.join(ROOT, "bench_detail.json"))
@@ -140,7 +145,11 @@ def parse(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="headline and roofline only (profiling runs)")
     ap.add_argument("--cpu-sample-seqs", type=int, default=8192,
                     help="sequences of the batch the CPU baseline solves (8192 x 6 x 64 = 3.1 M leg-frames: 10-20 s on 16 cores)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.detail
+    if args.dump_outputs and (args.gpus > 1 or args.one_recording):
+        ap.error("--dump-outputs: the one-GPU headline path only")
+    return args
 
 
 def compact_line(rec):
@@ -182,40 +191,6 @@ def compact_line(rec):
     if len(s) >= LINE_LIMIT:
         raise RuntimeError(f"bench.py: compact line of {len(s)} bytes")
     return s
-
-
-def build_roofline(args, batch, ev, ms_per_step, device_index):
-    """`roofline` of the dominant kernel: its average launch duration from the HIP events the library recorded around it on its
-    launch stream inside the timed region; algorithmic bytes x units per launch / that against HBM; and -- what actually binds --
-    the FP64 VALU figures from the committed PMC summary of THIS build (bench_support.pmc_roofline)."""
-    main_steps = [i for i in range(args.steps) if not bs.in_lat_range(batch, i)]
-    stage_ms = np.array([[ev[i][k].elapsed_time(ev[i][k + 1]) for k in range(4)] for i in main_steps]).mean(0)
-    if args.staged:
-        dom = int(np.argmax(stage_ms)) + 1
-        kname, key, bytes_unit, dom_ms = f"seqik_stage_kernel<{dom}, ...>", f"stage{dom}", BYTES_STAGE[dom], float(stage_ms[dom - 1])
-    else:  # one kernel per step: event [0] is recorded in front of it, [1] behind it
-        queued = batch.pool > 0
-        kname, key, bytes_unit, dom_ms = ("seqik_fused_queue_kernel<true>" if queued else "seqik_fused_kernel<true>"), "fused", BYTES_PATH, float(stage_ms[0])
-    ach_gbs = bytes_unit * batch.units / (dom_ms * 1e-3) / 1e9
-    traffic, valu, fp64, matches, pmc_file = bs.pmc_roofline(args.variant, args.staged, key, batch.units, ms_per_step, device_index, batch.pool)
-    hbm = {"achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_gbs / HBM_PEAK_GBS, "bytes_per_unit": bytes_unit,
-           "note": f"algorithmic bytes x units per launch / the kernel's average launch duration (launches of {len(batch.streams)} steps "
-                   f"overlap, so a launch lasts ~{len(batch.streams)}x a step); HBM is not what binds: ~1e4 f64 instructions per 392 B"}
-    if fp64:
-        tfl = float(f"{fp64['flops_per_step'] / (ms_per_step * 1e-3) / 1e12:.3g}")
-        roof = {"bound": "valu-fp64", "kernel": kname, "achieved": tfl, "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
-                "frac": float(f"{tfl / FP64_VECTOR_PEAK_TF:.3g}"), "traffic": traffic, "avg_launch_ms": dom_ms, "fp64": fp64,
-                "valu_issue": valu, "hbm": hbm,
-                "note": "bound by FP64 VALU issue, not HBM or MFMA: `achieved` = FP64 operations performed by active lanes per second "
-                        "(PMC instruction mix x lane share, live timing) against the vector FP64 peak; `valu_issue` = how close the step "
-                        "is to the floor its wave-instruction count allows; `hbm` = the algorithmic-bytes figure"}
-    else:  # no PMC summary of THIS build for this workload: only the HBM figure can be stated
-        roof = {"bound": "hbm", "kernel": kname, **hbm, "traffic": traffic, "avg_launch_ms": dom_ms}
-    roof.update({"pmc_matches_build": matches, "pmc_file": pmc_file,
-                 "traffic_over_algorithmic": traffic / (bytes_unit * batch.units) if traffic else None})
-    if args.staged:
-        roof["stage_ms"] = [float(v) for v in stage_ms]
-    return roof
 
 
 def main():
@@ -330,10 +305,14 @@ def main():
         # How many steps to keep in flight, and on which kernel family: measured over exactly the region that will be measured
         # (warm-up + steps between two synchronisations), with the gather running; every rank takes the candidate that is
         # fastest on the SLOWEST rank.  The whole problem fills the GPU at depth 3 (the only candidate then); a 1/8 share needs 20.
-        depth_calibration = {"candidates": [], "rule": "fastest ms per step on the slowest rank over the same region as the headline"}
+        # A long run calibrates over its first CALIBRATION_STEPS steps: its set-up must not grow with --steps.
+        cal_k, cal_w = min(args.steps, bs.CALIBRATION_STEPS), min(args.warmup, bs.CALIBRATION_STEPS)
+        depth_calibration = {"candidates": [], "steps": cal_k,
+                             "rule": "fastest ms per step on the slowest rank over the same region as the headline (at most "
+                                     f"{bs.CALIBRATION_STEPS} steps)"}
         best = None
         plain = args.lanes_per_wave == 0 and not args.staged and not args.interleave_legs
-        for n_st, pipe, lat, pool in [c + (0,) for c in bs.depth_candidates(args.steps, S * L)] + \
+        for n_st, pipe, lat, pool in [c + (0,) for c in bs.depth_candidates(cal_k, S * L)] + \
                 [(d, 1 if p else 0, None, p) for d, p in (bs.queue_candidates(S * L) if plain else [])]:
             bt, ms = None, float("inf")
             try:
@@ -346,10 +325,10 @@ def main():
                 local_ok, bufs = False, None
             if ranks.all_ok(local_ok):       # consensus BEFORE any collective of the candidate: nobody waits for a rank that failed
                 g, _ = make_gather(bufs[0], len(bufs))
-                tm, _ = ranks.timed_region(bt, bufs, g, args.steps, args.warmup)
+                tm, _ = ranks.timed_region(bt, bufs, g, cal_k, cal_w)
                 if hasattr(g, "close"):
                     g.close()
-                ms = tm / args.steps * 1e3
+                ms = tm / cal_k * 1e3
                 if best is None or ms < best[0]:
                     best = (ms, n_st, pipe, bt, lat, pool)
             depth_calibration["candidates"].append({"streams": n_st, "stage_pipeline": pipe, "latency_kernel_steps": lat, "chain_queue": pool,
@@ -357,8 +336,9 @@ def main():
             del bufs
         if best is None:
             raise SystemExit("bench: no pipeline depth could be run")
-        depth_calibration["chosen"] = {"streams": best[1], "stage_pipeline": best[2], "latency_kernel_steps": best[4], "chain_queue": best[5]}
         batch = best[3]
+        batch.lat_range = bs.tail_range(best[1], args.steps) if best[4] else None     # (the same partial round, of the K steps)
+        depth_calibration["chosen"] = {"streams": best[1], "stage_pipeline": best[2], "latency_kernel_steps": batch.lat_range, "chain_queue": best[5]}
         del batch.d_fks[len(batch.streams):]
         torch.cuda.empty_cache()
     d_ang = buffers_for(batch)
@@ -385,9 +365,11 @@ def main():
     if not ranks.all_ok(same):
         raise SystemExit("bench: overlapped launches did not reproduce a launch made alone -- result invalid")
     del chk_ang, chk_fk
+    if args.dump_outputs:     # what the LAST timed step wrote for its caller (buffers of step i: bench_support.Batch.launch)
+        bs.dump_outputs(args.dump_outputs, d_ang[(args.steps - 1) % len(d_ang)], batch.d_fks[(args.steps - 1) % len(batch.streams)], S)
 
     ms_per_step = elapsed / args.steps * 1e3
-    rec = record(ms_per_step, elapsed, batch, build_roofline(args, batch, ev, ms_per_step, device_index),
+    rec = record(ms_per_step, elapsed, batch, bs.build_roofline(args, batch, ev, ms_per_step, device_index),
                  {**({"depth_calibration": depth_calibration} if depth_calibration else {}), **({"gather": gather_how} if gather_how else {})})
     rec["verified"] = "every angle / FK buffer of the timed region == one launch made alone, bit for bit"
     ctx = dict(args=args, ranks=ranks, batch=batch, d_ang=d_ang, params=params, pose=pose, legs=legs, body=body, rec=rec, S_total=S_total,
@@ -443,7 +425,7 @@ def main():
                 bench_extras.multi_gpu_legs(ctx, multi)
         lifeline.disarm()
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and args.full and not args.no_extras:
         try:
             lone = Batch(None, params, args, 1, pipeline=0, like=batch)       # ONE call at a time: the library's own kernel choice
             k1 = max(4, min(16, args.steps // 6))
@@ -473,7 +455,7 @@ def main():
             import traceback
             rec["extras_error"] = f"{type(exc).__name__}: {exc}"
             sys.stderr.write("bench.py: a leg behind the headline failed, the line is printed without it:\n" + traceback.format_exc())
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             rec["cpu_baseline"] = bs.cpu_baseline(pose, legs, body, args.cpu_sample_seqs, not args.no_python_baseline)
             rec["gpu_over_cpu"] = rec["value"] / rec["cpu_baseline"]["value"]

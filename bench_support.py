@@ -20,6 +20,7 @@ import torch  # noqa: E402  (loads the HIP runtime that libseqik_hip.so binds to
 from seqikpy_amd import _lib, data, sharding, synthetic, utils  # noqa: E402
 
 MAX_DEPTH = int(os.environ.get("SEQIK_BENCH_MAX_DEPTH") or 20)   # steps in flight at most (24 streams of a 1/8 share lose again)
+CALIBRATION_STEPS = 100    # steps the depth calibration times per candidate at most (bench.py: K = 100 is calibrated over all K)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md)
 FP64_VECTOR_PEAK_TF = 78.6  # 256 CUs x 4 SIMDs x 16 f64 lanes x 2 flop x 2.4 GHz
 # Algorithmic HBM bytes per leg-frame (DESIGN.md "Kernels"):
@@ -204,10 +205,16 @@ def _depth_candidates(steps):
     if balanced > 3 and balanced not in (8, 12, 16, 20):
         cands.append((balanced, 1, None))
     for depth in (16, 20):
-        rest = steps % depth
-        if depth <= MAX_DEPTH and steps > depth and 0 < rest <= 8:
-            cands.append((depth, 1, (steps - rest, steps)))
+        if depth <= MAX_DEPTH and tail_range(depth, steps):
+            cands.append((depth, 1, tail_range(depth, steps)))
     return cands
+
+
+def tail_range(depth, steps):
+    """[lo, hi): the partial last round of `steps` steps at `depth` in flight, if it is short enough (at most 8 steps) to be
+    launched with the library's own kernel choice (depth_candidates); None otherwise."""
+    rest = steps % depth
+    return (steps - rest, steps) if steps > depth and 0 < rest <= 8 else None
 
 
 def in_lat_range(batch, i):
@@ -339,6 +346,39 @@ def pmc_roofline(variant, staged, key, units_per_step, ms_per_step, device_index
     return None, None, None, None, None
 
 
+def build_roofline(args, batch, ev, ms_per_step, device_index):
+    """`roofline` of the dominant kernel: its average launch duration from the HIP events the library recorded around it on its
+    launch stream inside the timed region; algorithmic bytes x units per launch / that against HBM; and -- what actually binds --
+    the FP64 VALU figures from the committed PMC summary of THIS build (bench_support.pmc_roofline)."""
+    main_steps = [i for i in range(args.steps) if not in_lat_range(batch, i)]
+    stage_ms = np.array([[ev[i][k].elapsed_time(ev[i][k + 1]) for k in range(4)] for i in main_steps]).mean(0)
+    if args.staged:
+        dom = int(np.argmax(stage_ms)) + 1
+        kname, key, bytes_unit, dom_ms = f"seqik_stage_kernel<{dom}, ...>", f"stage{dom}", BYTES_STAGE[dom], float(stage_ms[dom - 1])
+    else:  # one kernel per step: event [0] is recorded in front of it, [1] behind it
+        queued = batch.pool > 0
+        kname, key, bytes_unit, dom_ms = ("seqik_fused_queue_kernel<true>" if queued else "seqik_fused_kernel<true>"), "fused", BYTES_PATH, float(stage_ms[0])
+    ach_gbs = bytes_unit * batch.units / (dom_ms * 1e-3) / 1e9
+    traffic, valu, fp64, matches, pmc_file = pmc_roofline(args.variant, args.staged, key, batch.units, ms_per_step, device_index, batch.pool)
+    hbm = {"achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_gbs / HBM_PEAK_GBS, "bytes_per_unit": bytes_unit,
+           "note": f"algorithmic bytes x units per launch / the kernel's average launch duration (launches of {len(batch.streams)} steps "
+                   f"overlap, so a launch lasts ~{len(batch.streams)}x a step); HBM is not what binds: ~1e4 f64 instructions per 392 B"}
+    if fp64:
+        tfl = float(f"{fp64['flops_per_step'] / (ms_per_step * 1e-3) / 1e12:.3g}")
+        roof = {"bound": "valu-fp64", "kernel": kname, "achieved": tfl, "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
+                "frac": float(f"{tfl / FP64_VECTOR_PEAK_TF:.3g}"), "traffic": traffic, "avg_launch_ms": dom_ms, "fp64": fp64,
+                "valu_issue": valu, "hbm": hbm,
+                "note": "bound by FP64 VALU issue, not HBM or MFMA: `achieved` = FP64 operations performed by active lanes per second "
+                        "(PMC instruction mix x lane share, live timing) against the vector FP64 peak; `valu_issue` = how close the step "
+                        "is to the floor its wave-instruction count allows; `hbm` = the algorithmic-bytes figure"}
+    else:  # no PMC summary of THIS build for this workload: only the HBM figure can be stated
+        roof = {"bound": "hbm", "kernel": kname, **hbm, "traffic": traffic, "avg_launch_ms": dom_ms}
+    roof.update({"pmc_matches_build": matches, "pmc_file": pmc_file,
+                 "traffic_over_algorithmic": traffic / (bytes_unit * batch.units) if traffic else None})
+    if args.staged:
+        roof["stage_ms"] = [float(v) for v in stage_ms]
+    return roof
+
 
 def quick_parity():
     """max |d theta| of the HIP serial walk against the committed reference fixtures (the shipped anipose outputs outside the LF
@@ -354,6 +394,24 @@ def quick_parity():
             err[legs.index("LF"), LF_WINDOW[0]:LF_WINDOW[1]] = 0.0
         worst = max(worst, float(err.max()))
     return worst
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: < 64 MB in all
+DUMP_SEED = 20240611      # the sequences sampled when the whole output is larger: a function of the batch size alone
+
+
+def dump_outputs(path, d_ang, d_fk, n_seq):
+    """`bench.py --dump-outputs`: what a caller of the hot path receives from one step, in the caller's layout -- joint angles
+    (S, L, T, 7) and the stage-4 FK (S, L, T, 9, 3), float64 -- as <path>/angles.npy and fk.npy.  When all S sequences would take
+    more than DUMP_BYTES, a fixed, seeded sample of them (sorted; their indices in sequences.npy, as float64)."""
+    L, T = d_fk.shape[1], d_fk.shape[2]
+    k = min(n_seq, DUMP_BYTES // (L * T * (7 + 27) * 8))
+    idx = np.arange(n_seq) if k == n_seq else np.sort(np.random.default_rng(DUMP_SEED).choice(n_seq, k, replace=False))
+    sel = torch.from_numpy(idx).to(d_fk.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "angles.npy"), d_ang[:n_seq].index_select(0, sel).permute(0, 1, 3, 2).contiguous().cpu().numpy())
+    np.save(os.path.join(path, "fk.npy"), d_fk[:n_seq].index_select(0, sel).cpu().numpy())
+    np.save(os.path.join(path, "sequences.npy"), idx.astype(np.float64))
 
 
 def round_numbers(v):

@@ -107,12 +107,13 @@ def test_bench_files_stay_small_and_split():
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_default_line_on_the_gpu(tmp_path):
-    """The driver's command on the real program, at a size that takes seconds: ONE stdout line below 4 KB with every key of the
-    contract, roofline and cpu_baseline filled, the full record in the detail file."""
+    """The driver's command with --full on the real program, at a size that takes seconds: ONE stdout line below 4 KB with every
+    key of the contract, roofline and cpu_baseline filled, the full record in the detail file.  The hardware-queue count is left
+    to bench.py (recommended_env), whatever the caller's environment holds."""
     detail = tmp_path / "detail.json"
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GPU_MAX_HW_QUEUES")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--frames", "64000",
-                        "--cpu-sample-seqs", "64", "--detail-path", str(detail)], env=env, capture_output=True, text=True, timeout=800)
+                        "--cpu-sample-seqs", "64", "--detail-path", str(detail), "--full"], env=env, capture_output=True, text=True, timeout=800)
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
     b = check_line(lines[0], 1)
@@ -123,3 +124,61 @@ def test_bench_default_line_on_the_gpu(tmp_path):
     assert b["config"]["env"]["GPU_MAX_HW_QUEUES"] == "22" and "extras_error" not in b
     full = json.loads(detail.read_text())
     assert full["value"] == pytest.approx(b["value"], rel=1e-5) and "depth_calibration" in full["config"] and "single_job" in full
+
+
+def test_plain_run_options_and_the_output_dump(tmp_path, monkeypatch):
+    """A plain run leaves the legs behind the headline to --full (which --detail implies); --dump-outputs writes the caller's
+    arrays of one step -- angles (S, L, T, 7) from the planar device buffer, FK (S, L, T, 9, 3) -- in float64, all sequences while
+    they fit, else the same seeded sample every time."""
+    import numpy as np
+    import torch
+    bench = bench_module()
+    import bench_support as bs
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse(["--full"]).full and bench.parse(["--detail"]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--gpus", "2", "--dump-outputs", str(tmp_path)])
+    S, L, T = 50, 6, 4
+    ang = torch.arange(S * L * 7 * T, dtype=torch.float64).reshape(S, L, 7, T)
+    padded = torch.cat([ang, torch.full((2, L, 7, T), float("nan"), dtype=torch.float64)])   # angle buffers padded to s_pad rows
+    fk = torch.randn((S, L, T, 9, 3), dtype=torch.float64, generator=torch.Generator().manual_seed(3))
+    bs.dump_outputs(str(tmp_path / "all"), padded, fk, S)
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("angles", "fk", "sequences")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["sequences"], np.arange(S)) and np.array_equal(got["fk"], fk.numpy())
+    assert np.array_equal(got["angles"], ang.permute(0, 1, 3, 2).numpy())
+    monkeypatch.setattr(bs, "DUMP_BYTES", 10 * L * T * (7 + 27) * 8)
+    for d in ("s1", "s2"):
+        bs.dump_outputs(str(tmp_path / d), padded, fk, S)
+    idx = np.load(tmp_path / "s1" / "sequences.npy")
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(tmp_path / "s2" / "sequences.npy"))
+    sel = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "s1" / "angles.npy"), ang.permute(0, 1, 3, 2).numpy()[sel])
+    assert np.array_equal(np.load(tmp_path / "s1" / "fk.npy"), fk.numpy()[sel])
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_and_its_output_dump_on_the_gpu(tmp_path):
+    """The plain command: the headline line (contract keys, roofline from the timed region's events, `verified`) and nothing of
+    --full; --dump-outputs holds what the last timed step computed, bit for bit what one call of the library returns for the
+    same (seeded) inputs."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", "6400",
+                        "--dump-outputs", str(out), "--detail-path", str(tmp_path / "detail.json")],
+                       env=env, capture_output=True, text=True, timeout=500)
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
+    b = check_line(lines[0], 1)
+    assert b["steps"] == 3 and b["warmup"] == 1 and abs(b["value"] - 6400 * 6 / (b["ms_per_step"] * 1e-3)) < 1e-5 * b["value"]
+    assert b["roofline"]["avg_launch_ms"] > 0 and "verified" in b
+    assert not {"cpu_baseline", "parity_max_abs_dtheta", "value_single_job", "value_smooth", "extras_error"} & set(b)
+    import bench_support as bs
+    from seqikpy_amd import _lib, synthetic
+    _, _, pose, params = bs.make_workload(100, 64, "iid", synthetic.SEED_BASE)
+    ref = _lib.solve_seq(pose, params)
+    assert np.array_equal(np.load(out / "sequences.npy"), np.arange(100))
+    assert np.array_equal(np.load(out / "angles.npy"), ref["angles"]) and np.array_equal(np.load(out / "fk.npy"), ref["fk"])

@@ -565,7 +565,8 @@ def test_bench_launches_its_own_ranks(tmp_path):
     import json
     import subprocess
     import time
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SEQIK_BENCH_BACKEND", "SEQIK_GATHER")}
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SEQIK_BENCH_BACKEND", "SEQIK_GATHER",
+                                                         "GPU_MAX_HW_QUEUES")}    # (bench.py's own environment, recorded in the line)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     detail = tmp_path / "detail.json"
     t0 = time.time()
@@ -929,12 +930,13 @@ def test_bench_headline_survives_a_leg_that_does_not_finish(tmp_path):
     the run leaves with exit code 75 (round-5 advice: a stuck run must not look healthy)."""
     import json
     import subprocess
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SEQIK_BENCH_BACKEND", "SEQIK_GATHER")}
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SEQIK_BENCH_BACKEND", "SEQIK_GATHER",
+                                                         "GPU_MAX_HW_QUEUES")}    # (bench.py's own environment)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     env["SEQIK_BENCH_CONFIG5_FRAMES"] = "256000"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--frames", "8256",
            "--detail-path", str(tmp_path / "d.json")]
-    r = subprocess.run(cmd + ["--legs", "all"], env=dict(env, SEQIK_BENCH_LEGS_TIMEOUT="1.5"), capture_output=True, text=True, timeout=500)
+    r = subprocess.run(cmd + ["--legs", "all"], env=dict(env, SEQIK_BENCH_LEGS_TIMEOUT="0.5"), capture_output=True, text=True, timeout=500)
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
     b = json.loads(lines[0])
