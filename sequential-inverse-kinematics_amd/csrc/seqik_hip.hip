@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "seqik_core.hpp"
@@ -67,6 +68,16 @@ int fail(int code, const char *fmt, const char *detail = "")
 {
     snprintf(g_err, sizeof(g_err), fmt, detail);
     return code;
+}
+
+// the message of a seqik::validate_leg* result (SEQIK_OK: none)
+int leg_error(int rc)
+{
+    if (rc == SEQIK_ERR_BAD_BOUNDS) return fail(rc, "Each lower bound must be strictly less than each upper bound.%s");
+    if (rc == SEQIK_ERR_X0_OUT_OF_BOUNDS) return fail(rc, "Initial guess is outside of provided bounds%s");
+    if (rc == SEQIK_ERR_BAD_ARG)
+        return fail(rc, "a joint limit is non-zero but smaller than 2^-600 in magnitude: not supported (DESIGN.md, floating-point contract)%s");
+    return rc;
 }
 
 #define HIP_TRY(expr)                                                              \
@@ -261,6 +272,32 @@ __device__ __forceinline__ bool chain_of_lane(int64_t n_seq, int32_t n_legs, int
     return chain_of_wave_lane(g >> 6, (int)(g & 63), n_seq, n_legs, W, order, c, leg);
 }
 
+// Kernel prologue: the workgroup copies the per-leg constant table (n_legs entries) into LDS; the kernel's
+// __syncthreads() follows
+template <typename T>
+__device__ __forceinline__ void stage_legs(T *s_legs, const T *legs, int32_t n_legs)
+{
+    const int words = n_legs * (int)(sizeof(T) / sizeof(uint32_t));
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(legs);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
+    for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
+}
+
+// the ChainIO fields every kernel fills the same way for (the first) chain c, in the order the kernels had them; the caller
+// sets init, frames, n_frames and whatever its kernel needs beyond that (diagnostics, chunk / queue fields)
+__device__ __forceinline__ void chain_io(const KernelArgs &a, int64_t c, seqik::ChainIO &io)
+{
+    io.pose = a.pose + c * a.pose_chain;
+    io.pose_row = a.pose_row;
+    io.pose_frame = a.pose_frame;
+    io.angles = a.angles + c * a.ang_chain;
+    io.ang_dof = a.ang_dof;
+    io.ang_frame = a.ang_frame;
+    io.fk = a.fk ? a.fk + c * a.n_frames * 27 : nullptr;
+    io.status = nullptr;
+    io.nfev = nullptr;
+}
+
 // Dispatch order of the legs: descending total width of the joint limits (stable).
 LegOrder make_leg_order(const SeqikLegParams *legs, int32_t n_legs)
 {
@@ -349,25 +386,14 @@ __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(
 seqik_stage_kernel(KernelArgs a)
 {
     __shared__ seqik::LegConst s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     int64_t c;
     int leg;
     if (!chain_of_lane(a.n_seq, a.n_legs, a.lanes_per_wave, a.leg_order, c, leg)) return;
 
     seqik::ChainIO io;
-    io.pose = a.pose + c * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c * a.n_frames * 27 : nullptr;
+    chain_io(a, c, io);
     io.status = a.status ? a.status + c * a.n_frames * 4 : nullptr;
     io.nfev = a.nfev ? a.nfev + c * a.n_frames * 4 : nullptr;
     io.init = a.init ? a.init + c * 7 : nullptr;
@@ -389,26 +415,13 @@ __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(
 seqik_fused_kernel(KernelArgs a)
 {
     __shared__ seqik::LegConst s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     int64_t c;
     int leg;
     if (!chain_of_lane(a.n_seq, a.n_legs, a.lanes_per_wave, a.leg_order, c, leg)) return;
     seqik::ChainIO io;
-    io.pose = a.pose + c * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c * a.n_frames * 27 : nullptr;
-    io.status = nullptr;
-    io.nfev = nullptr;
+    chain_io(a, c, io);
     io.init = a.init ? a.init + c * 7 : nullptr;
     io.frames = a.frames + c * a.n_frames * 12;
     io.n_frames = a.n_frames;
@@ -437,12 +450,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SEQIK_W
 seqik_fused_queue_kernel(KernelArgs a)
 {
     __shared__ seqik::LegConst s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     // one wavefront per workgroup: wave = blockIdx.x; the waves of a leg are adjacent, legs in dispatch order (chain_of_lane)
     const int64_t n_grp = (a.n_seq + a.pool - 1) / a.pool;   // pools (= wavefronts) per leg
@@ -454,15 +462,7 @@ seqik_fused_queue_kernel(KernelArgs a)
     if (pool_first + (int64_t)threadIdx.x >= pool_end) return;   // (only in the last pool of a leg: a lane with no chain to start on)
     const int64_t c0 = pool_first * a.n_legs + leg;   // first chain of the pool: wave-uniform, so are the pointers below
     seqik::ChainIO io;
-    io.pose = a.pose + c0 * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c0 * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c0 * a.n_frames * 27 : nullptr;
-    io.status = nullptr;
-    io.nfev = nullptr;
+    chain_io(a, c0, io);
     io.init = a.init ? a.init + c0 * 7 : nullptr;
     io.frames = a.frames + c0 * a.n_frames * 12;
     io.n_frames = a.n_frames;
@@ -504,6 +504,12 @@ struct PipeShared {
     int consumed[3][64];
 };
 
+// the pipeline kernels' prologue beside stage_legs(): the ring counters start at zero
+__device__ __forceinline__ void reset_ring(PipeShared &sh)
+{
+    for (int i = threadIdx.x; i < 3 * 64; i += blockDim.x) { (&sh.produced[0][0])[i] = 0; (&sh.consumed[0][0])[i] = 0; }
+}
+
 // pairs (wave-uniform): the wave carries every chain on an even number of adjacent lanes, lanes 2k / 2k + 1 split the
 // passes of the stages with two active joints between them
 // LAT: run_stage's option of the same name (the latency build; the 256-register instantiations set it)
@@ -543,28 +549,15 @@ seqik_pipe_kernel(KernelArgs a)
 {
     __shared__ seqik::LegConst s_legs[kMaxLegs];
     __shared__ PipeShared sh;
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-        for (int i = threadIdx.x; i < 3 * 64; i += blockDim.x) { (&sh.produced[0][0])[i] = 0; (&sh.consumed[0][0])[i] = 0; }
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
+    reset_ring(sh);
     __syncthreads();  // the only barrier: from here on the four waves are coupled by the ring counters alone
     const int stage_wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int64_t c;
     int leg;
     if (!chain_of_wave_lane(blockIdx.x, lane, a.n_seq, a.n_legs, a.lanes_per_wave, a.leg_order, c, leg)) return;
     seqik::ChainIO io;
-    io.pose = a.pose + c * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c * a.n_frames * 27 : nullptr;
-    io.status = nullptr;
-    io.nfev = nullptr;
+    chain_io(a, c, io);
     io.init = a.init ? a.init + c * 7 : nullptr;
     io.frames = nullptr;
     io.n_frames = a.n_frames;
@@ -739,15 +732,7 @@ __device__ __forceinline__ void chunk_io(const KernelArgs &a, const ChunkArgs &c
     const int64_t vseq = vc / a.n_legs;
     const int64_t seq = vseq / K, k = vseq - seq * K;
     const int64_t c = seq * a.n_legs + leg;
-    io.pose = a.pose + c * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c * N * 27 : nullptr;
-    io.status = nullptr;
-    io.nfev = nullptr;
+    chain_io(a, c, io);
     const int64_t ws_frames = C + (ca.halo > lead ? ca.halo : lead);
     io.frames = a.frames + vc * ws_frames * 12;
     io.t_store = lead + k * C;
@@ -773,15 +758,7 @@ __device__ __forceinline__ void chunk_io(const KernelArgs &a, const ChunkArgs &c
 // ChainIO of real chain c walked serially from frame 0 (the guard's fallback): the whole call, everything stored
 __device__ __forceinline__ void serial_io(const KernelArgs &a, int64_t c, seqik::ChainIO &io)
 {
-    io.pose = a.pose + c * a.pose_chain;
-    io.pose_row = a.pose_row;
-    io.pose_frame = a.pose_frame;
-    io.angles = a.angles + c * a.ang_chain;
-    io.ang_dof = a.ang_dof;
-    io.ang_frame = a.ang_frame;
-    io.fk = a.fk ? a.fk + c * a.n_frames * 27 : nullptr;
-    io.status = nullptr;
-    io.nfev = nullptr;
+    chain_io(a, c, io);
     io.frames = nullptr;
     io.t_begin = 0;
     io.t_store = 0;
@@ -801,12 +778,7 @@ __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(
 seqik_chunk_kernel(KernelArgs a, ChunkArgs ca)
 {
     __shared__ seqik::LegConst s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = (int)(g & 63);
@@ -887,13 +859,8 @@ seqik_chunk_pipe_kernel(KernelArgs a, ChunkArgs ca)
     static_assert(mode == CHUNK_SPEC || mode == CHUNK_REPAIR || mode == CHUNK_SERIAL, "the sweep stays on the lane-per-chunk kernel");
     __shared__ seqik::LegConst s_legs[kMaxLegs];
     __shared__ PipeShared sh;
-    {
-        const int words = a.n_legs * (int)(sizeof(seqik::LegConst) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-        for (int i = threadIdx.x; i < 3 * 64; i += blockDim.x) { (&sh.produced[0][0])[i] = 0; (&sh.consumed[0][0])[i] = 0; }
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
+    reset_ring(sh);
     __syncthreads();
     const int stage_wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (mode == CHUNK_SPEC) {
@@ -941,34 +908,61 @@ __global__ void seqik_chunk_reset_kernel(ChunkArgs ca, int32_t n_chunks_total)
     if (ca.stats && i < 16) ca.stats[i] = (i == 0) ? n_chunks_total : (i == 1) ? ca.chunk : (i == 2) ? ca.halo : 0;
 }
 
-// from_angles: first stage of a run that starts after stage 1; handoff: a later stage follows
-template <int STAGE, bool FROM_ANGLES, bool HANDOFF>
-void launch_stage2(const KernelArgs &a, bool fk, bool diag, dim3 grid, dim3 block, hipStream_t stream)
+// ---------------------------------------------------------------------------------------------------------------
+// Kernel selection.  Each helper maps the runtime flags of a call onto the template arguments of ONE kernel template
+// (and only onto instantiations that exist); launch_kernel() launches and checks.
+// ---------------------------------------------------------------------------------------------------------------
+using Kernel = void (*)(KernelArgs);
+using ChunkKernel = void (*)(KernelArgs, ChunkArgs);
+
+// f(std::true_type{}) if b, else f(std::false_type{}); with ALLOWED = false only the false branch is instantiated
+template <bool ALLOWED = true, typename F>
+auto with_flag(bool b, F &&f)
 {
-    if constexpr (STAGE >= 2) {
-        if (fk && diag) { hipLaunchKernelGGL((seqik_stage_kernel<STAGE, true, true, FROM_ANGLES, HANDOFF>), grid, block, 0, stream, a); return; }
-        if (fk) { hipLaunchKernelGGL((seqik_stage_kernel<STAGE, true, false, FROM_ANGLES, HANDOFF>), grid, block, 0, stream, a); return; }
-    }
-    if (diag) hipLaunchKernelGGL((seqik_stage_kernel<STAGE, false, true, FROM_ANGLES, HANDOFF>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((seqik_stage_kernel<STAGE, false, false, FROM_ANGLES, HANDOFF>), grid, block, 0, stream, a);
+    if constexpr (ALLOWED)
+        if (b) return f(std::true_type{});
+    return f(std::false_type{});
 }
 
+// from_angles: first stage of a run that starts after stage 1; handoff: a later stage follows.  Stage 1 has no FK and no
+// earlier stage, stage 4 no later one.
 template <int STAGE>
-void launch_stage(const KernelArgs &a, bool fk, bool diag, bool from_angles, bool handoff, dim3 grid, dim3 block,
-                  hipStream_t stream)
+Kernel stage_kernel(bool fk, bool diag, bool from_angles, bool handoff)
 {
-    if constexpr (STAGE == 1) {
-        if (handoff) launch_stage2<1, false, true>(a, fk, diag, grid, block, stream);
-        else launch_stage2<1, false, false>(a, fk, diag, grid, block, stream);
-    } else if constexpr (STAGE == 4) {
-        if (from_angles) launch_stage2<4, true, false>(a, fk, diag, grid, block, stream);
-        else launch_stage2<4, false, false>(a, fk, diag, grid, block, stream);
-    } else {
-        if (from_angles && handoff) launch_stage2<STAGE, true, true>(a, fk, diag, grid, block, stream);
-        else if (from_angles) launch_stage2<STAGE, true, false>(a, fk, diag, grid, block, stream);
-        else if (handoff) launch_stage2<STAGE, false, true>(a, fk, diag, grid, block, stream);
-        else launch_stage2<STAGE, false, false>(a, fk, diag, grid, block, stream);
-    }
+    return with_flag<STAGE >= 2>(fk, [&](auto FK) { return with_flag(diag, [&](auto DIAG) {
+        return with_flag<STAGE >= 2>(from_angles, [&](auto FROM) { return with_flag<STAGE <= 3>(handoff, [&](auto HANDOFF) -> Kernel {
+            return seqik_stage_kernel<STAGE, decltype(FK)::value, decltype(DIAG)::value, decltype(FROM)::value, decltype(HANDOFF)::value>;
+        }); }); }); });
+}
+
+constexpr Kernel (*kStageKernel[4])(bool, bool, bool, bool) = {stage_kernel<1>, stage_kernel<2>, stage_kernel<3>, stage_kernel<4>};
+
+Kernel fused_kernel(bool fk) { return with_flag(fk, [](auto FK) -> Kernel { return seqik_fused_kernel<decltype(FK)::value>; }); }
+Kernel fused_queue_kernel(bool fk) { return with_flag(fk, [](auto FK) -> Kernel { return seqik_fused_queue_kernel<decltype(FK)::value>; }); }
+
+// roomy: at most two workgroups per CU -- the 256-register (latency) build of the pipeline kernels
+Kernel pipe_kernel(bool fk, bool roomy)
+{
+    return with_flag(fk, [&](auto FK) { return with_flag(roomy, [&](auto ROOMY) -> Kernel {
+        return seqik_pipe_kernel<decltype(FK)::value, decltype(ROOMY)::value ? 2 : SEQIK_WAVES_PER_EU>; }); });
+}
+
+template <int MODE>
+ChunkKernel chunk_kernel(bool fk) { return with_flag(fk, [](auto FK) -> ChunkKernel { return seqik_chunk_kernel<decltype(FK)::value, MODE>; }); }
+
+template <int MODE>
+ChunkKernel chunk_pipe_kernel(bool fk, bool roomy)
+{
+    return with_flag(fk, [&](auto FK) { return with_flag(roomy, [&](auto ROOMY) -> ChunkKernel {
+        return seqik_chunk_pipe_kernel<decltype(FK)::value, MODE, decltype(ROOMY)::value ? 2 : SEQIK_WAVES_PER_EU>; }); });
+}
+
+template <typename... P, typename... A>
+int launch_kernel(void (*k)(P...), dim3 grid, dim3 block, hipStream_t stream, const A &...args)
+{
+    hipLaunchKernelGGL(k, grid, block, 0, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return SEQIK_OK;
 }
 
 using GenericLegTable = seqik::GenericLeg;   // { GenericConst gc; LegAffine aff; } (seqik_generic.hpp)
@@ -1001,12 +995,7 @@ __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(
 seqik_generic_kernel(GenericKernelArgs a)
 {
     __shared__ GenericLegTable s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(GenericLegTable) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     int64_t c;
     int leg;
@@ -1033,12 +1022,7 @@ __global__ void __launch_bounds__(kMaxBlock) __attribute__((amdgpu_waves_per_eu(
 seqik_generic_queue_kernel(GenericKernelArgs a, int32_t *counters)
 {
     __shared__ GenericLegTable s_legs[kMaxLegs];
-    {
-        const int words = a.n_legs * (int)(sizeof(GenericLegTable) / sizeof(uint32_t));
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.legs);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(s_legs);
-        for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
-    }
+    stage_legs(s_legs, a.legs, a.n_legs);
     __syncthreads();
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     seqik::GenericIO io;
@@ -1053,6 +1037,19 @@ seqik_generic_queue_kernel(GenericKernelArgs a, int32_t *counters)
     q.pose = a.pose; q.pose_chain = a.pose_chain; q.angles = a.angles; q.ang_chain = a.ang_chain;
     q.fk = a.fk; q.status = a.status; q.nfev = a.nfev; q.init = a.init;
     seqik::run_generic<WANT_DIAG, false, true>(s_legs[0].gc, s_legs[0].aff, io, &q);
+}
+
+using GenericKernel = void (*)(GenericKernelArgs);
+GenericKernel generic_kernel(bool diag, bool grouped)
+{
+    return with_flag(diag, [&](auto DIAG) { return with_flag(grouped, [&](auto GROUPED) -> GenericKernel {
+        return seqik_generic_kernel<decltype(DIAG)::value, decltype(GROUPED)::value>; }); });
+}
+
+using GenericQueueKernel = void (*)(GenericKernelArgs, int32_t *);
+GenericQueueKernel generic_queue_kernel(bool diag)
+{
+    return with_flag(diag, [](auto DIAG) -> GenericQueueKernel { return seqik_generic_queue_kernel<decltype(DIAG)::value>; });
 }
 
 // Device copies of the per-leg constant tables.  Callers almost always pass the same legs on every call, so the
@@ -1277,52 +1274,135 @@ struct ArenaCursor {
     template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + off); off += padded(sizeof(T) * count); return p; }
 };
 
-int check_args(int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
-               int32_t first_stage, int32_t last_stage, const void *pose, const void *angles)
+// null pointers and sizes: the first check of every entry point of the leg and the generic solver
+int check_sizes(int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs, const void *pose,
+                const void *angles)
 {
     if (!legs || !pose || !angles) return fail(SEQIK_ERR_BAD_ARG, "null pointer argument%s");
     if (n_seq < 0 || n_frames < 0 || n_legs <= 0 || n_legs > kMaxLegs)
         return fail(SEQIK_ERR_BAD_ARG, "bad sizes (n_legs must be 1..8)%s");
+    return SEQIK_OK;
+}
+
+int check_args(int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
+               int32_t first_stage, int32_t last_stage, const void *pose, const void *angles)
+{
+    if (int rc = check_sizes(n_seq, n_legs, n_frames, legs, pose, angles)) return rc;
     if (first_stage < 1 || last_stage > 4 || first_stage > last_stage)
         return fail(SEQIK_ERR_BAD_STAGE, "Maximum stage number is 4 and the list should be strictly incremental.%s");
     return seqik_validate_legs(legs, n_legs, first_stage, last_stage);
 }
 
-int launch(const double *d_pose, int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
-           const seqik::LegConst *d_legs, int32_t first_stage, int32_t last_stage, double *d_angles,
-           double *d_fk, int32_t *d_status, int32_t *d_nfev, const double *d_init, const SeqikLayout *layout,
-           const SeqikOptions *opt, hipStream_t stream)
+int check_generic_args(int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs, const void *pose,
+                       const void *angles)
 {
-    KernelArgs a;
-    a.init = d_init;
-    a.fault = fault_word(stream);
+    const int rc = check_sizes(n_seq, n_legs, n_frames, legs, pose, angles);
+    return rc ? rc : seqik_validate_legs_generic(legs, n_legs);
+}
+
+// element strides of the caller's SeqikLayout; without one the dense layout: pose [chain][frame][5][3], angles [chain][frame][7]
+template <typename Args>
+void set_strides(Args &a, const SeqikLayout *layout, int64_t n_frames)
+{
     if (layout) {
-        if (layout->pose_chain < 0 || layout->pose_row <= 0 || layout->pose_frame <= 0 || layout->ang_chain < 0 ||
-            layout->ang_dof <= 0 || layout->ang_frame <= 0)
-            return fail(SEQIK_ERR_BAD_ARG, "layout strides must be positive%s");
         a.pose_chain = layout->pose_chain; a.pose_row = layout->pose_row; a.pose_frame = layout->pose_frame;
         a.ang_chain = layout->ang_chain; a.ang_dof = layout->ang_dof; a.ang_frame = layout->ang_frame;
     } else {
         a.pose_chain = n_frames * 15; a.pose_row = 3; a.pose_frame = 15;
         a.ang_chain = n_frames * 7; a.ang_dof = 1; a.ang_frame = 7;
     }
-    a.pose = d_pose; a.angles = d_angles; a.fk = d_fk; a.status = d_status; a.nfev = d_nfev;
-    a.legs = d_legs;
+}
+
+int block_size(const SeqikOptions *opt, int *block)
+{
+    *block = (opt && opt->block_size > 0) ? opt->block_size : 64;
+    if (*block % 64 != 0 || *block > kMaxBlock) return fail(SEQIK_ERR_BAD_ARG, "block_size must be a multiple of 64, <= 256%s");
+    return SEQIK_OK;
+}
+
+// Wavefronts of a launch over n_vseq (virtual) sequences of n_legs chains, W chains per wave: leg-pure waves, or with
+// SeqikOptions.reserved[2] = 1 leg-interleaved ones (|W| consecutive chains per wave; W is then made negative).
+int64_t wave_count(int64_t n_vseq, int32_t n_legs, const SeqikOptions *opt, int32_t &W)
+{
+    if (opt && opt->reserved[2] == 1) {
+        const int64_t n = (n_vseq * n_legs + W - 1) / W;
+        W = -W;
+        return n;
+    }
+    return ((n_vseq + W - 1) / W) * n_legs;
+}
+
+// Workspace of a chunked call, the one owner of its size and layout: hand-off frames | start states (unused when the
+// caller keeps them) | control block | work list | chain_serial | fail_count | serial list.  (The stage pipeline hands
+// frames over through LDS, but the sweep at the end of a piped call runs on the lane-per-chunk kernel and uses the
+// hand-off frames.)  Points ca's buffers into the workspace at `base` (0 in plan_launch: sizing only) and returns its bytes.
+size_t carve_chunk_workspace(uintptr_t base, int64_t n_chains, ChunkArgs &ca)
+{
+    static_assert(sizeof(ChunkCtrl) * (kCtrlSerial + 1) <= 128, "control block");
+    const size_t n_ch = (size_t)n_chains, n_vchains = n_ch * (size_t)ca.n_chunks;
+    size_t off = sizeof(double) * 12 * n_vchains * (size_t)(ca.chunk + (ca.halo > ca.lead ? ca.halo : ca.lead));
+    auto take = [&](size_t bytes) { const uintptr_t at = base + off; off += bytes; return at; };
+    ca.start_state = reinterpret_cast<double *>(take(sizeof(double) * 7 * n_vchains));
+    ca.ctrl = reinterpret_cast<ChunkCtrl *>(take(128));
+    ca.worklist = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * n_vchains));
+    ca.chain_serial = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * 2 * n_ch));  // launch_chunked zeroes both halves:
+    ca.fail_count = ca.chain_serial + n_ch;                                             // chain_serial | fail_count
+    ca.serial_list = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * n_ch));
+    return off;
+}
+
+// The launch sequence of a chunked call (SeqikOptions.chunk_resume decoded, see plan_launch)
+struct ChunkSchedule {
+    bool speculate;          // the speculative pass (not when resuming: angles / chunk_states are a previous call's)
+    bool first_check;        // the first verification: verify + decide kernels
+    int32_t repair_rounds;   // {scan, repair} rounds
+    bool sweep;              // the final scan + serial sweep
+    bool guard;              // the serial walk of the chains the first verification gave up on
+};
+
+enum class Family { None, Staged, Fused, Queue, Pipe, Chunked };
+
+// Everything launch() decides before it touches the GPU
+struct LaunchPlan {
+    KernelArgs a;
+    Family family = Family::None;   // None: nothing to solve
+    bool fk = false, diag = false;
+    bool piped = false;             // on the stage pipeline (Pipe; Chunked: the speculative pass and the repairs)
+    bool roomy = false;             // the 256-register (latency) build of the pipeline kernels
+    int64_t n_waves = 0;
+    dim3 grid, block;               // lane-per-chain kernels
+    dim3 pipe_grid;                 // pipeline kernels: one workgroup (4 stage waves) per group of W chains
+    size_t ws_bytes = 0;            // workspace (stage hand-off frames; chunked: carve_chunk_workspace)
+    ChunkArgs ca;                   // Chunked: the geometry (the pointers are carved from the workspace)
+    ChunkSchedule sched;
+};
+
+// Every check and every decision of a launch, no HIP call.  `a` holds the caller's device pointers, the leg table and
+// the fault word; SEQIK_OK with p.family == None when there is nothing to solve.
+int plan_launch(const KernelArgs &a_in, int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
+                int32_t first_stage, int32_t last_stage, const SeqikLayout *layout, const SeqikOptions *opt, LaunchPlan &p)
+{
+    KernelArgs &a = p.a;
+    a = a_in;
+    if (layout && (layout->pose_chain < 0 || layout->pose_row <= 0 || layout->pose_frame <= 0 || layout->ang_chain < 0 ||
+                   layout->ang_dof <= 0 || layout->ang_frame <= 0))
+        return fail(SEQIK_ERR_BAD_ARG, "layout strides must be positive%s");
+    set_strides(a, layout, n_frames);
     a.n_chains = n_seq * (int64_t)n_legs;
     a.n_frames = n_frames;
     a.n_legs = n_legs;
     if (a.n_chains == 0 || n_frames == 0) return SEQIK_OK;
-    int block = (opt && opt->block_size > 0) ? opt->block_size : 64;
-    if (block % 64 != 0 || block > kMaxBlock) return fail(SEQIK_ERR_BAD_ARG, "block_size must be a multiple of 64, <= 256%s");
+    int block;
+    if (int rc = block_size(opt, &block)) return rc;
     a.n_seq = n_seq;
     a.leg_order = make_leg_order(legs, n_legs);
-    const bool diag = d_status || d_nfev;
-    const bool fk = d_fk && last_stage == 4;  // FK is the stage-4 chain's (leg_inverse_kinematics.py:279-282)
-    if (!fk) a.fk = nullptr;
+    p.diag = a.status || a.nfev;
+    p.fk = a.fk && last_stage == 4;  // FK is the stage-4 chain's (leg_inverse_kinematics.py:279-282)
+    if (!p.fk) a.fk = nullptr;
     // frame chunks (SeqikOptions.frame_chunk): runs of all four stages without diagnostics only
     int32_t chunk = 0, halo = 0, lead = 0;
     int64_t n_chunks = 1;
-    const bool chunked = first_stage == 1 && last_stage == 4 && !diag &&
+    const bool chunked = first_stage == 1 && last_stage == 4 && !p.diag &&
                          pick_frame_chunks(opt, n_frames, chunk, halo, lead, n_chunks);
     if (!chunked && opt && (opt->frame_lead > 0 || opt->chunk_resume))
         return fail(SEQIK_ERR_BAD_ARG, "frame_lead / chunk_resume need frame chunks (frame_chunk != 0, all four stages, no diagnostics)%s");
@@ -1335,22 +1415,18 @@ int launch(const double *d_pose, int64_t n_seq, int32_t n_legs, int64_t n_frames
     // register-carried Jacobian / gradient / scaling reuse against the plain instantiation, bit for bit
     const int pipe_opt = opt ? opt->reserved[3] : 0;
     const bool staged = opt && opt->reserved[1] == 1;  // "always one launch per stage" rules out the AUTOMATIC pipeline
-    const bool piped = first_stage == 1 && last_stage == 4 && !diag &&
-                       (pipe_opt >= 2 || (pipe_opt == 0 && !(staged && !chunked) &&
-                                          n_vchains <= (chunked ? kPipeMaxChunks : kPipeMaxChains)));
+    p.piped = first_stage == 1 && last_stage == 4 && !p.diag &&
+              (pipe_opt >= 2 || (pipe_opt == 0 && !(staged && !chunked) &&
+                                 n_vchains <= (chunked ? kPipeMaxChunks : kPipeMaxChains)));
     a.lane_pairs = (pipe_opt == 3 || pipe_opt == 5) ? 0 : 1;  // 3 / 5 = thin waves without lane pairs (measurements)
-    a.lanes_per_wave = pick_lanes_per_wave(n_vchains, opt, chunked || piped);
-    int64_t n_waves = ((n_seq * n_chunks + a.lanes_per_wave - 1) / a.lanes_per_wave) * n_legs;  // leg-pure waves
-    if (opt && opt->reserved[2] == 1) {  // leg-interleaved: |W| consecutive chains per wave
-        n_waves = (n_vchains + a.lanes_per_wave - 1) / a.lanes_per_wave;
-        a.lanes_per_wave = -a.lanes_per_wave;
-    }
+    a.lanes_per_wave = pick_lanes_per_wave(n_vchains, opt, chunked || p.piped);
+    int64_t n_waves = wave_count(n_seq * n_chunks, n_legs, opt, a.lanes_per_wave);
     // chain queue of the fused kernel: SeqikOptions.reserved[0] in 65..4096 = chains a wavefront OWNS (a multiple of 64; its 64
     // lanes take them one after the other).  Only where seqik_fused_kernel would run: all four stages, no diagnostics, not
     // chunked, not piped, leg-pure wavefronts, at least 1024 chains; anywhere else the option is refused rather than ignored.
     a.pool = 0;
     if (opt && opt->reserved[0] > 64) {
-        const bool plain_fused = first_stage == 1 && last_stage == 4 && !diag && !chunked && !piped && !staged && opt->reserved[2] != 1;
+        const bool plain_fused = first_stage == 1 && last_stage == 4 && !p.diag && !chunked && !p.piped && !staged && opt->reserved[2] != 1;
         const int64_t widest = n_legs * (a.pose_chain > a.ang_chain ? a.pose_chain : a.ang_chain) > (int64_t)n_legs * n_frames * 27
                                    ? n_legs * (a.pose_chain > a.ang_chain ? a.pose_chain : a.ang_chain) : (int64_t)n_legs * n_frames * 27;
         if (opt->reserved[0] > 4096 || opt->reserved[0] % 64 != 0 || !plain_fused || n_seq > 0x7fffffffLL || widest > 0xffffffffLL)
@@ -1361,159 +1437,141 @@ int launch(const double *d_pose, int64_t n_seq, int32_t n_legs, int64_t n_frames
         n_waves = ((n_seq + a.pool - 1) / a.pool) * n_legs;
         block = 64;
     }
-    static const bool queue64 = getenv("SEQIK_QUEUE64") != nullptr;   // measurement: the queue kernel with pools of 64 (no pulls)
-    if (queue64 && a.pool == 0 && a.lanes_per_wave == 64 && first_stage == 1 && last_stage == 4 && !diag && !chunked && !piped && !staged &&
-        !(opt && opt->reserved[2] == 1)) {
-        a.pool = 64;
-        block = 64;
-    }
-    int64_t grid64 = (n_waves * 64 + block - 1) / block;
+    const int64_t grid64 = (n_waves * 64 + block - 1) / block;
     if (grid64 > 0x7fffffffLL || n_waves > 0x7fffffffLL) return fail(SEQIK_ERR_BAD_ARG, "too many chains for one launch%s");
-    const dim3 grid((unsigned)grid64), blk(block);
-    const dim3 pipe_grid((unsigned)n_waves), pipe_blk(256);  // one workgroup (4 stage waves) per group of W chains
+    p.n_waves = n_waves;
+    p.grid = dim3((unsigned)grid64);
+    p.block = dim3(block);
+    p.pipe_grid = dim3((unsigned)n_waves);
     // at most two workgroups per CU: the 256-register (latency) build of the pipeline kernels, unless switched off (4 / 5)
-    const bool roomy = n_waves <= 2 * 256 && pipe_opt != 4 && pipe_opt != 5;
-    // stage hand-off workspace: the frame after the active links of stage k is the prefix of stage k + 1
-    a.frames = nullptr;
-    static const bool pool_workspace = getenv("SEQIK_WORKSPACE_POOL") != nullptr;  // diagnosis only (see Workspace)
-    const size_t ws_frames = chunked ? (size_t)chunk + (size_t)(halo > lead ? halo : lead) : 0;  // hand-off frames per chunk
-    if (chunked) {
-        const size_t ws_bytes = sizeof(double) * (12 * ws_frames + 7) * n_vchains + 128 +
-                                sizeof(int32_t) * ((size_t)n_vchains + 3 * (size_t)a.n_chains);
-        if (int rc = workspace_for(stream, ws_bytes, &a.frames)) return rc;
-    } else if (last_stage > first_stage && !piped) {
-        const size_t ws_bytes = sizeof(double) * 12 * a.n_chains * n_frames;
-        if (pool_workspace) HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&a.frames), ws_bytes, stream));
-        else if (int rc = workspace_for(stream, ws_bytes, &a.frames)) return rc;
-    }
-    const bool fused = (piped || !staged) && first_stage == 1 && last_stage == 4 && !diag;
-    if (chunked) {
-        ChunkArgs ca;
-        ca.n_chunks = n_chunks; ca.n_vseq = n_seq * n_chunks; ca.chunk = chunk; ca.halo = halo; ca.lead = lead;
-        ca.tol = (opt->chunk_tol > 0) ? opt->chunk_tol : (opt->chunk_tol < 0 ? 0.0 : 1e-6);
-        ca.n_rounds = (opt->chunk_rounds > 0) ? (opt->chunk_rounds < kMaxChunkRounds ? opt->chunk_rounds : kMaxChunkRounds) : 3;
-        ca.stats = opt->chunk_stats;
-        ca.flags = opt->chunk_flags;
-        ca.round = 0;
-        // chunk_resume: 0 = a whole call; 1 / 2 = resume (2: chunk 0 must continue d_init exactly); LOCKSTEP pieces of ONE call spread
-        // over the GPUs of a frame-sharded recording, so that the ranks together run exactly the rounds one GPU would run:
-        // 3 = the speculative pass and the first verification only; 4 = ONE {scan, repair} round (chunk 0 against d_init, held back
-        // where CHUNK_FLAG_LEFT_BLOCKED says the chunk in front of it is about to change); 5 = the final scan + serial sweep only
-        const int mode = opt->chunk_resume;
-        if (mode < 0 || mode > 5) return fail(SEQIK_ERR_BAD_ARG, "chunk_resume must be 0 .. 5%s");
-        const bool resume = mode == 1 || mode == 2 || mode == 4 || mode == 5;
-        ca.resume = resume ? (mode == 2 ? 2 : 1) : 0;
-        if ((mode >= 3) && opt->frame_chunk <= 0)
-            return fail(SEQIK_ERR_BAD_ARG, "chunk_resume 3 / 4 / 5 (lockstep pieces) need an explicit frame_chunk > 0%s");
-        if (mode == 3 && !opt->chunk_states)
-            return fail(SEQIK_ERR_BAD_ARG, "chunk_resume = 3 needs chunk_states (the rounds that follow are other calls)%s");
-        if (mode == 4) ca.n_rounds = 1;          // one round, no sweep (the loop below stops in front of it)
-        if (mode == 5) ca.n_rounds = 0;          // straight to the final scan + sweep
-        ca.left_blocked = (mode == 4 && opt->chunk_flags) ? 1 : 0;
-        if (resume && !opt->chunk_states)
-            return fail(SEQIK_ERR_BAD_ARG, "chunk_resume needs the chunk_states of the call it resumes%s");
-        // chunk 0 is verified (and repaired) like the others when it started from a run-in and the caller says what the
-        // true state in front of it is
-        ca.k_first = ((lead > 0 || resume) && d_init) ? 0 : 1;
-        // the guard against failed speculation belongs to the automatic mode of a whole recording
-        ca.guard = (opt->frame_chunk == -1 && lead == 0 && !resume) ? 1 : 0;
-        // carve the workspace: [hand-off frames] | start states (unless the caller keeps them) | control block |
-        // work list | serial flags | serial list.  (The stage pipeline hands frames over through LDS, but the sweep at the
-        // end of a piped call runs on the lane-per-chunk kernel and uses the hand-off frames.)
-        char *base = reinterpret_cast<char *>(a.frames);
-        size_t off = sizeof(double) * 12 * (size_t)n_vchains * ws_frames;
-        ca.start_state = reinterpret_cast<double *>(base + off); off += sizeof(double) * 7 * (size_t)n_vchains;
-        if (opt->chunk_states) ca.start_state = opt->chunk_states;
-        ca.ctrl = reinterpret_cast<ChunkCtrl *>(base + off); off += 128;
-        ca.worklist = reinterpret_cast<int32_t *>(base + off); off += sizeof(int32_t) * (size_t)n_vchains;
-        ca.chain_serial = reinterpret_cast<int32_t *>(base + off); off += sizeof(int32_t) * (size_t)a.n_chains;
-        ca.fail_count = reinterpret_cast<int32_t *>(base + off); off += sizeof(int32_t) * (size_t)a.n_chains;  // (zeroed with chain_serial)
-        ca.serial_list = reinterpret_cast<int32_t *>(base + off);
-        if (opt->stage_events) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[0]), stream));
-        hipLaunchKernelGGL(seqik_chunk_reset_kernel, dim3(1), dim3(64), 0, stream, ca, (int32_t)(n_chunks * a.n_chains));
-        HIP_TRY(hipMemsetAsync(ca.chain_serial, 0, sizeof(int32_t) * 2 * (size_t)a.n_chains, stream));
-        if (resume) {
-            // nothing is solved speculatively: angles / chunk_states are a previous call's, d_init the true state
-        } else if (piped) {
-            if (roomy) {
-                if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_SPEC, 2>), pipe_grid, pipe_blk, 0, stream, a, ca);
-                else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_SPEC, 2>), pipe_grid, pipe_blk, 0, stream, a, ca);
-            } else if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_SPEC, SEQIK_WAVES_PER_EU>), pipe_grid, pipe_blk, 0, stream, a, ca);
-            else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_SPEC, SEQIK_WAVES_PER_EU>), pipe_grid, pipe_blk, 0, stream, a, ca);
-        } else if (fk) hipLaunchKernelGGL((seqik_chunk_kernel<true, CHUNK_SPEC>), grid, blk, 0, stream, a, ca);
-        else hipLaunchKernelGGL((seqik_chunk_kernel<false, CHUNK_SPEC>), grid, blk, 0, stream, a, ca);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(seqik_chunk_verify_kernel, dim3((unsigned)((n_vchains + 255) / 256)), dim3(256), 0, stream, a, ca);
-        hipLaunchKernelGGL(seqik_chunk_decide_kernel, dim3((unsigned)((a.n_chains + 255) / 256)), dim3(256), 0, stream, a, ca);
-        const dim3 scan_grid((unsigned)((n_vchains + 255) / 256)), scan_blk(256);
-        const int64_t rep_waves = n_waves < 4096 ? n_waves : 4096;  // the work list is walked grid-stride
-        const dim3 rep_grid((unsigned)((rep_waves * 64 + block - 1) / block));
-        for (int r = 0; r <= ca.n_rounds && mode != 3; ++r) {
-            if (mode == 4 && r == ca.n_rounds) break;   // lockstep round: the sweep is another call (chunk_resume = 5)
-            ca.round = r;
-            hipLaunchKernelGGL(seqik_chunk_scan_kernel, scan_grid, scan_blk, 0, stream, a, ca);
-            if (r < ca.n_rounds && piped) {
-                const dim3 rep_pipe_grid((unsigned)(n_waves < 1024 ? n_waves : 1024));
-                if (roomy) {
-                    if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_REPAIR, 2>), rep_pipe_grid, pipe_blk, 0, stream, a, ca);
-                    else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_REPAIR, 2>), rep_pipe_grid, pipe_blk, 0, stream, a, ca);
-                } else if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_REPAIR, SEQIK_WAVES_PER_EU>), rep_pipe_grid, pipe_blk, 0, stream, a, ca);
-                else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_REPAIR, SEQIK_WAVES_PER_EU>), rep_pipe_grid, pipe_blk, 0, stream, a, ca);
-            } else if (r < ca.n_rounds) {
-                if (fk) hipLaunchKernelGGL((seqik_chunk_kernel<true, CHUNK_REPAIR>), rep_grid, blk, 0, stream, a, ca);
-                else hipLaunchKernelGGL((seqik_chunk_kernel<false, CHUNK_REPAIR>), rep_grid, blk, 0, stream, a, ca);
-            } else {  // serial sweep: one wave per real chain
-                const dim3 sweep_grid((unsigned)a.n_chains), sweep_blk(64);
-                if (fk) hipLaunchKernelGGL((seqik_chunk_kernel<true, CHUNK_SWEEP>), sweep_grid, sweep_blk, 0, stream, a, ca);
-                else hipLaunchKernelGGL((seqik_chunk_kernel<false, CHUNK_SWEEP>), sweep_grid, sweep_blk, 0, stream, a, ca);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        if (ca.guard) {  // the chains the first verification gave up on: the serial walk, on the stage pipeline
-            const dim3 ser_grid((unsigned)(a.n_chains < 1024 ? a.n_chains : 1024));
-            if (a.n_chains <= 2 * 256) {
-                if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_SERIAL, 2>), ser_grid, pipe_blk, 0, stream, a, ca);
-                else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_SERIAL, 2>), ser_grid, pipe_blk, 0, stream, a, ca);
-            } else if (fk) hipLaunchKernelGGL((seqik_chunk_pipe_kernel<true, CHUNK_SERIAL, SEQIK_WAVES_PER_EU>), ser_grid, pipe_blk, 0, stream, a, ca);
-            else hipLaunchKernelGGL((seqik_chunk_pipe_kernel<false, CHUNK_SERIAL, SEQIK_WAVES_PER_EU>), ser_grid, pipe_blk, 0, stream, a, ca);
-            HIP_TRY(hipGetLastError());
-        }
-        if (opt->stage_events)
-            for (int k = 1; k <= 4; ++k) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[k]), stream));
+    p.roomy = n_waves <= 2 * 256 && pipe_opt != 4 && pipe_opt != 5;
+    a.frames = nullptr;  // stage hand-off workspace: the frame after the active links of stage k is the prefix of stage k + 1
+    if (!chunked) {
+        const bool fused = (p.piped || !staged) && first_stage == 1 && last_stage == 4 && !p.diag;
+        p.family = !fused ? Family::Staged : p.piped ? Family::Pipe : a.pool > 0 ? Family::Queue : Family::Fused;
+        if (last_stage > first_stage && !p.piped) p.ws_bytes = sizeof(double) * 12 * a.n_chains * n_frames;
         return SEQIK_OK;
     }
-    if (fused) {
-        if (opt && opt->stage_events) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[0]), stream));
-        if (piped) {
-            if (roomy) {
-                if (fk) hipLaunchKernelGGL((seqik_pipe_kernel<true, 2>), pipe_grid, pipe_blk, 0, stream, a);
-                else hipLaunchKernelGGL((seqik_pipe_kernel<false, 2>), pipe_grid, pipe_blk, 0, stream, a);
-            } else if (fk) hipLaunchKernelGGL((seqik_pipe_kernel<true, SEQIK_WAVES_PER_EU>), pipe_grid, pipe_blk, 0, stream, a);
-            else hipLaunchKernelGGL((seqik_pipe_kernel<false, SEQIK_WAVES_PER_EU>), pipe_grid, pipe_blk, 0, stream, a);
-        } else if (a.pool > 0) {
-            if (fk) hipLaunchKernelGGL((seqik_fused_queue_kernel<true>), grid, blk, 0, stream, a);
-            else hipLaunchKernelGGL((seqik_fused_queue_kernel<false>), grid, blk, 0, stream, a);
-        } else if (fk) hipLaunchKernelGGL((seqik_fused_kernel<true>), grid, blk, 0, stream, a);
-        else hipLaunchKernelGGL((seqik_fused_kernel<false>), grid, blk, 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        if (opt && opt->stage_events)  // one kernel: [0] in front of it, [1..4] behind it
-            for (int k = 1; k <= 4; ++k) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[k]), stream));
-    }
-    for (int stage = first_stage; stage <= last_stage && !fused; ++stage) {
-        const bool from_angles = (stage == first_stage) && stage > 1;
-        const bool handoff = stage < last_stage;
-        if (opt && opt->stage_events) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[stage - 1]), stream));
-        switch (stage) {
-        case 1: launch_stage<1>(a, false, diag, from_angles, handoff, grid, blk, stream); break;
-        case 2: launch_stage<2>(a, fk, diag, from_angles, handoff, grid, blk, stream); break;
-        case 3: launch_stage<3>(a, fk, diag, from_angles, handoff, grid, blk, stream); break;
-        default: launch_stage<4>(a, fk, diag, from_angles, handoff, grid, blk, stream); break;
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    if (opt && opt->stage_events && !fused) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[4]), stream));
-    if (a.frames && pool_workspace) HIP_TRY(hipFreeAsync(a.frames, stream));
+    ChunkArgs &ca = p.ca;
+    ca.n_chunks = n_chunks; ca.n_vseq = n_seq * n_chunks; ca.chunk = chunk; ca.halo = halo; ca.lead = lead;
+    ca.tol = (opt->chunk_tol > 0) ? opt->chunk_tol : (opt->chunk_tol < 0 ? 0.0 : 1e-6);
+    const int32_t rounds = (opt->chunk_rounds > 0) ? (opt->chunk_rounds < kMaxChunkRounds ? opt->chunk_rounds : kMaxChunkRounds) : 3;
+    ca.stats = opt->chunk_stats;
+    ca.flags = opt->chunk_flags;
+    ca.round = 0;
+    // chunk_resume: 0 = a whole call; 1 / 2 = resume (2: chunk 0 must continue d_init exactly); LOCKSTEP pieces of ONE call spread
+    // over the GPUs of a frame-sharded recording, so that the ranks together run exactly the rounds one GPU would run:
+    // 3 = the speculative pass and the first verification only; 4 = ONE {scan, repair} round (chunk 0 against d_init, held back
+    // where CHUNK_FLAG_LEFT_BLOCKED says the chunk in front of it is about to change); 5 = the final scan + serial sweep only
+    const int mode = opt->chunk_resume;
+    if (mode < 0 || mode > 5) return fail(SEQIK_ERR_BAD_ARG, "chunk_resume must be 0 .. 5%s");
+    const bool resume = mode == 1 || mode == 2 || mode == 4 || mode == 5;
+    ca.resume = resume ? (mode == 2 ? 2 : 1) : 0;
+    if ((mode >= 3) && opt->frame_chunk <= 0)
+        return fail(SEQIK_ERR_BAD_ARG, "chunk_resume 3 / 4 / 5 (lockstep pieces) need an explicit frame_chunk > 0%s");
+    if (mode == 3 && !opt->chunk_states)
+        return fail(SEQIK_ERR_BAD_ARG, "chunk_resume = 3 needs chunk_states (the rounds that follow are other calls)%s");
+    ca.left_blocked = (mode == 4 && opt->chunk_flags) ? 1 : 0;
+    if (resume && !opt->chunk_states)
+        return fail(SEQIK_ERR_BAD_ARG, "chunk_resume needs the chunk_states of the call it resumes%s");
+    // chunk 0 is verified (and repaired) like the others when it started from a run-in and the caller says what the
+    // true state in front of it is
+    ca.k_first = ((lead > 0 || resume) && a.init) ? 0 : 1;
+    ChunkSchedule &s = p.sched;
+    s.speculate = !resume;
+    s.first_check = true;                        // in every mode (4 and 5 included)
+    s.repair_rounds = mode == 3 || mode == 5 ? 0 : mode == 4 ? 1 : rounds;
+    s.sweep = mode != 3 && mode != 4;            // 4: the sweep is another call (chunk_resume = 5)
+    // the guard against failed speculation belongs to the automatic mode of a whole recording
+    s.guard = opt->frame_chunk == -1 && lead == 0 && !resume;
+    ca.n_rounds = s.repair_rounds;               // (the scan counts repairs per round for the statistics)
+    ca.guard = s.guard ? 1 : 0;
+    p.ws_bytes = carve_chunk_workspace(0, a.n_chains, ca);
+    p.family = Family::Chunked;
     return SEQIK_OK;
+}
+
+// stage_events [first, last]
+int record_events(const SeqikOptions *opt, int first, int last, hipStream_t stream)
+{
+    if (opt && opt->stage_events)
+        for (int k = first; k <= last; ++k) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(opt->stage_events[k]), stream));
+    return SEQIK_OK;
+}
+
+// Frame chunks: the launch sequence of the comment "Frame chunks" above, as p.sched says, on the caller's stream
+int launch_chunked(LaunchPlan &p, const SeqikOptions *opt, hipStream_t stream)
+{
+    const KernelArgs &a = p.a;
+    ChunkArgs &ca = p.ca;
+    const ChunkSchedule &s = p.sched;
+    const int64_t n_vchains = ca.n_vseq * a.n_legs;
+    const dim3 b256(256);
+    carve_chunk_workspace(reinterpret_cast<uintptr_t>(a.frames), a.n_chains, ca);
+    if (opt->chunk_states) ca.start_state = opt->chunk_states;
+    if (int rc = record_events(opt, 0, 0, stream)) return rc;
+    if (int rc = launch_kernel(seqik_chunk_reset_kernel, dim3(1), dim3(64), stream, ca, (int32_t)(ca.n_chunks * a.n_chains))) return rc;
+    HIP_TRY(hipMemsetAsync(ca.chain_serial, 0, sizeof(int32_t) * 2 * (size_t)a.n_chains, stream));   // chain_serial | fail_count
+    if (s.speculate) {
+        const int rc = p.piped ? launch_kernel(chunk_pipe_kernel<CHUNK_SPEC>(p.fk, p.roomy), p.pipe_grid, b256, stream, a, ca)
+                               : launch_kernel(chunk_kernel<CHUNK_SPEC>(p.fk), p.grid, p.block, stream, a, ca);
+        if (rc) return rc;
+    }
+    const dim3 scan_grid((unsigned)((n_vchains + 255) / 256));
+    if (s.first_check) {
+        if (int rc = launch_kernel(seqik_chunk_verify_kernel, scan_grid, b256, stream, a, ca)) return rc;
+        if (int rc = launch_kernel(seqik_chunk_decide_kernel, dim3((unsigned)((a.n_chains + 255) / 256)), b256, stream, a, ca)) return rc;
+    }
+    const int64_t rep_waves = p.n_waves < 4096 ? p.n_waves : 4096;  // the work list is walked grid-stride
+    const dim3 rep_grid((unsigned)((rep_waves * 64 + p.block.x - 1) / p.block.x));
+    const dim3 rep_pipe_grid((unsigned)(p.n_waves < 1024 ? p.n_waves : 1024));
+    for (int32_t r = 0; r < s.repair_rounds; ++r) {
+        ca.round = r;
+        if (int rc = launch_kernel(seqik_chunk_scan_kernel, scan_grid, b256, stream, a, ca)) return rc;
+        const int rc = p.piped ? launch_kernel(chunk_pipe_kernel<CHUNK_REPAIR>(p.fk, p.roomy), rep_pipe_grid, b256, stream, a, ca)
+                               : launch_kernel(chunk_kernel<CHUNK_REPAIR>(p.fk), rep_grid, p.block, stream, a, ca);
+        if (rc) return rc;
+    }
+    if (s.sweep) {  // serial sweep: one wave per real chain
+        ca.round = s.repair_rounds;
+        if (int rc = launch_kernel(seqik_chunk_scan_kernel, scan_grid, b256, stream, a, ca)) return rc;
+        if (int rc = launch_kernel(chunk_kernel<CHUNK_SWEEP>(p.fk), dim3((unsigned)a.n_chains), dim3(64), stream, a, ca)) return rc;
+    }
+    if (s.guard) {  // the chains the first verification gave up on: the serial walk, on the stage pipeline
+        const dim3 ser_grid((unsigned)(a.n_chains < 1024 ? a.n_chains : 1024));
+        if (int rc = launch_kernel(chunk_pipe_kernel<CHUNK_SERIAL>(p.fk, a.n_chains <= 2 * 256), ser_grid, b256, stream, a, ca)) return rc;
+    }
+    return record_events(opt, 1, 4, stream);
+}
+
+int launch(const double *d_pose, int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
+           const seqik::LegConst *d_legs, int32_t first_stage, int32_t last_stage, double *d_angles,
+           double *d_fk, int32_t *d_status, int32_t *d_nfev, const double *d_init, const SeqikLayout *layout,
+           const SeqikOptions *opt, hipStream_t stream)
+{
+    KernelArgs a;
+    a.pose = d_pose; a.angles = d_angles; a.fk = d_fk; a.status = d_status; a.nfev = d_nfev; a.init = d_init;
+    a.legs = d_legs;
+    a.fault = fault_word(stream);
+    LaunchPlan p;
+    if (int rc = plan_launch(a, n_seq, n_legs, n_frames, legs, first_stage, last_stage, layout, opt, p)) return rc;
+    if (p.family == Family::None) return SEQIK_OK;
+    if (p.ws_bytes)
+        if (int rc = workspace_for(stream, p.ws_bytes, &p.a.frames)) return rc;
+    if (p.family == Family::Chunked) return launch_chunked(p, opt, stream);
+    if (p.family != Family::Staged) {  // one kernel: stage_events [0] in front of it, [1..4] behind it
+        if (int rc = record_events(opt, 0, 0, stream)) return rc;
+        const int rc = p.family == Family::Pipe ? launch_kernel(pipe_kernel(p.fk, p.roomy), p.pipe_grid, dim3(256), stream, p.a)
+                                                : launch_kernel(p.family == Family::Queue ? fused_queue_kernel(p.fk) : fused_kernel(p.fk),
+                                                                p.grid, p.block, stream, p.a);
+        return rc ? rc : record_events(opt, 1, 4, stream);
+    }
+    for (int stage = first_stage; stage <= last_stage; ++stage) {
+        if (int rc = record_events(opt, stage - 1, stage - 1, stream)) return rc;
+        const bool from_angles = (stage == first_stage) && stage > 1, handoff = stage < last_stage;
+        if (int rc = launch_kernel(kStageKernel[stage - 1](p.fk, p.diag, from_angles, handoff), p.grid, p.block, stream, p.a)) return rc;
+    }
+    return record_events(opt, 4, 4, stream);
 }
 
 }  // namespace
@@ -1627,15 +1685,8 @@ int seqik_validate_legs(const SeqikLegParams *legs, int32_t n_legs, int32_t firs
     if (!legs || n_legs <= 0) return fail(SEQIK_ERR_BAD_ARG, "null legs%s");
     if (first_stage < 1 || last_stage > 4 || first_stage > last_stage)
         return fail(SEQIK_ERR_BAD_STAGE, "Maximum stage number is 4 and the list should be strictly incremental.%s");
-    for (int l = 0; l < n_legs; ++l) {
-        int rc = seqik::validate_leg(legs[l], first_stage, last_stage);
-        if (rc == SEQIK_ERR_BAD_BOUNDS)
-            return fail(rc, "Each lower bound must be strictly less than each upper bound.%s");
-        if (rc == SEQIK_ERR_X0_OUT_OF_BOUNDS)
-            return fail(rc, "Initial guess is outside of provided bounds%s");
-        if (rc == SEQIK_ERR_BAD_ARG)
-            return fail(rc, "a joint limit is non-zero but smaller than 2^-600 in magnitude: not supported (DESIGN.md, floating-point contract)%s");
-    }
+    for (int l = 0; l < n_legs; ++l)
+        if (int rc = leg_error(seqik::validate_leg(legs[l], first_stage, last_stage))) return rc;
     return SEQIK_OK;
 }
 
@@ -1662,15 +1713,8 @@ int seqik_solve_seq_device(const double *d_pose, int64_t n_seq, int32_t n_legs, 
 int seqik_validate_legs_generic(const SeqikLegParams *legs, int32_t n_legs)
 {
     if (!legs || n_legs <= 0) return fail(SEQIK_ERR_BAD_ARG, "null legs%s");
-    for (int l = 0; l < n_legs; ++l) {
-        int rc = seqik::validate_leg_generic(legs[l]);
-        if (rc == SEQIK_ERR_BAD_BOUNDS)
-            return fail(rc, "Each lower bound must be strictly less than each upper bound.%s");
-        if (rc == SEQIK_ERR_X0_OUT_OF_BOUNDS)
-            return fail(rc, "Initial guess is outside of provided bounds%s");
-        if (rc == SEQIK_ERR_BAD_ARG)
-            return fail(rc, "a joint limit is non-zero but smaller than 2^-600 in magnitude: not supported (DESIGN.md, floating-point contract)%s");
-    }
+    for (int l = 0; l < n_legs; ++l)
+        if (int rc = leg_error(seqik::validate_leg_generic(legs[l]))) return rc;
     return SEQIK_OK;
 }
 
@@ -1679,39 +1723,27 @@ int seqik_solve_generic_device(const double *d_pose, int64_t n_seq, int32_t n_le
                                int32_t *d_nfev, const double *d_init_angles, const SeqikLayout *layout,
                                const SeqikAffine *affine, const SeqikOptions *opt, void *hip_stream)
 {
-    if (!legs || !d_pose || !d_angles) return fail(SEQIK_ERR_BAD_ARG, "null pointer argument%s");
-    if (n_seq < 0 || n_frames < 0 || n_legs <= 0 || n_legs > kMaxLegs)
-        return fail(SEQIK_ERR_BAD_ARG, "bad sizes (n_legs must be 1..8)%s");
-    int rc = seqik_validate_legs_generic(legs, n_legs);
+    int rc = check_generic_args(n_seq, n_legs, n_frames, legs, d_pose, d_angles);
     if (rc != SEQIK_OK) return rc;
     GenericKernelArgs a;
     a.pose = d_pose; a.angles = d_angles; a.fk = d_fk; a.status = d_status; a.nfev = d_nfev; a.init = d_init_angles;
     a.n_chains = n_seq * (int64_t)n_legs; a.n_frames = n_frames; a.n_legs = n_legs;
-    if (layout) {
-        a.pose_chain = layout->pose_chain; a.pose_row = layout->pose_row; a.pose_frame = layout->pose_frame;
-        a.ang_chain = layout->ang_chain; a.ang_dof = layout->ang_dof; a.ang_frame = layout->ang_frame;
-    } else {
-        a.pose_chain = n_frames * 15; a.pose_row = 3; a.pose_frame = 15;
-        a.ang_chain = n_frames * 7; a.ang_dof = 1; a.ang_frame = 7;
-    }
+    set_strides(a, layout, n_frames);   // (taken as they are: this path has no check of the strides)
     if (a.n_chains == 0 || n_frames == 0) return SEQIK_OK;
     rc = device_generic_table(legs, affine, n_legs, &a.legs);
     if (rc != SEQIK_OK) return rc;
-    int block = (opt && opt->block_size > 0) ? opt->block_size : 64;
-    if (block % 64 != 0 || block > kMaxBlock) return fail(SEQIK_ERR_BAD_ARG, "block_size must be a multiple of 64, <= 256%s");
+    int block;
+    if ((rc = block_size(opt, &block)) != SEQIK_OK) return rc;
     a.n_seq = n_seq;
     a.leg_order = make_leg_order(legs, n_legs);
     a.lanes_per_wave = pick_lanes_per_wave(a.n_chains, opt);
     a.lane_groups = (opt && opt->reserved[3] == 3) ? 0 : 1;  // 3: thin waves without lane groups (measurements)
-    int64_t n_waves = ((n_seq + a.lanes_per_wave - 1) / a.lanes_per_wave) * n_legs;
-    if (opt && opt->reserved[2] == 1) {
-        n_waves = (a.n_chains + a.lanes_per_wave - 1) / a.lanes_per_wave;
-        a.lanes_per_wave = -a.lanes_per_wave;
-    }
+    const int64_t n_waves = wave_count(n_seq, n_legs, opt, a.lanes_per_wave);
     const dim3 grid((unsigned)((n_waves * 64 + block - 1) / block)), blk(block);
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int W_abs = a.lanes_per_wave < 0 ? -a.lanes_per_wave : a.lanes_per_wave;
     const bool grouped = a.lane_groups != 0 && W_abs <= 8;  // lane_groups(W): the replication is then a multiple of 8
+    const bool diag = d_status || d_nfev;
     // Chain queue (SeqikOptions.reserved[1]: 0 = automatic, 1 = never, 2 = whenever full wavefronts are used): pays when the
     // batch has several times more chains than the GPU has lanes for this kernel (one wavefront per SIMD) -- with fewer
     // there is nothing to pull and the launch lasts as long as its slowest chain either way.  Measured on windows of the
@@ -1737,20 +1769,10 @@ int seqik_solve_generic_device(const double *d_pose, int64_t n_seq, int32_t n_le
             std::lock_guard<std::mutex> enqueue_lock(g_queue_enqueue_mutex);
             HIP_TRY(hipMemsetAsync(counters, 0, sizeof(int32_t) * kMaxLegs, stream));
             const int64_t q_waves = n_waves < slots ? n_waves : slots;
-            const dim3 q_grid((unsigned)q_waves), q_blk(64);
-            if (d_status || d_nfev) hipLaunchKernelGGL((seqik_generic_queue_kernel<true>), q_grid, q_blk, 0, stream, a, counters);
-            else hipLaunchKernelGGL((seqik_generic_queue_kernel<false>), q_grid, q_blk, 0, stream, a, counters);
-            HIP_TRY(hipGetLastError());
-            return SEQIK_OK;
+            return launch_kernel(generic_queue_kernel(diag), dim3((unsigned)q_waves), dim3(64), stream, a, counters);
         }
     }
-    if (d_status || d_nfev) {
-        if (grouped) hipLaunchKernelGGL((seqik_generic_kernel<true, true>), grid, blk, 0, stream, a);
-        else hipLaunchKernelGGL((seqik_generic_kernel<true, false>), grid, blk, 0, stream, a);
-    } else if (grouped) hipLaunchKernelGGL((seqik_generic_kernel<false, true>), grid, blk, 0, stream, a);
-    else hipLaunchKernelGGL((seqik_generic_kernel<false, false>), grid, blk, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return SEQIK_OK;
+    return launch_kernel(generic_kernel(diag, grouped), grid, blk, stream, a);
 }
 
 // device buffers of one host-buffer call, carved from a pooled context's arena
@@ -1767,20 +1789,11 @@ struct HostCall {
     }
 };
 
-#define TRY_OUT(expr)                                                                            \
-    {                                                                                            \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return fail(SEQIK_ERR_HIP, #expr ": %s", hipGetErrorString(e_));  \
-    }
-
 int seqik_solve_generic(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n_frames,
                         const SeqikLegParams *legs, double *angles, double *fk, int32_t *status, int32_t *nfev,
                         const double *init_angles, const SeqikAffine *affine, const SeqikOptions *opt)
 {
-    if (!legs || !pose || !angles) return fail(SEQIK_ERR_BAD_ARG, "null pointer argument%s");
-    if (n_seq < 0 || n_frames < 0 || n_legs <= 0 || n_legs > kMaxLegs)
-        return fail(SEQIK_ERR_BAD_ARG, "bad sizes (n_legs must be 1..8)%s");
-    int rc = seqik_validate_legs_generic(legs, n_legs);
+    int rc = check_generic_args(n_seq, n_legs, n_frames, legs, pose, angles);
     if (rc != SEQIK_OK) return rc;
     const size_t n_lf = (size_t)n_seq * n_legs * n_frames;
     if (n_lf == 0) return SEQIK_OK;
@@ -1802,16 +1815,16 @@ int seqik_solve_generic(const double *pose, int64_t n_seq, int32_t n_legs, int64
     double *d_fk = fk ? cur.take<double>(27 * n_lf) : nullptr;
     int32_t *d_status = status ? cur.take<int32_t>(n_lf) : nullptr, *d_nfev = nfev ? cur.take<int32_t>(n_lf) : nullptr;
     double *d_init = init_angles ? cur.take<double>(7 * n_ch) : nullptr;
-    if (d_init) TRY_OUT(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
-    TRY_OUT(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
+    if (d_init) HIP_TRY(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
     rc = seqik_solve_generic_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk, d_status, d_nfev, d_init,
                                     nullptr, affine, opt, stream);
     if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    TRY_OUT(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (fk) TRY_OUT(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (status) TRY_OUT(hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
-    if (nfev) TRY_OUT(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
-    TRY_OUT(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
+    if (fk) HIP_TRY(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
+    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return SEQIK_OK;
 }
 
@@ -1855,30 +1868,30 @@ int seqik_solve_seq(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n
     double *d_init = init_angles ? cur.take<double>(7 * n_ch) : nullptr;
     int32_t *d_stats = cur.take<int32_t>(16);
     uint8_t *d_flags = want_flags ? cur.take<uint8_t>(n_flags) : nullptr;
-    if (d_init) TRY_OUT(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
-    TRY_OUT(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
+    if (d_init) HIP_TRY(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
     // angles is in/out: columns of stages that do not run are inputs (earlier stages) or stay as they are
     if (first_stage > 1 || last_stage < 4)
-        TRY_OUT(hipMemcpyAsync(d_angles, angles, sizeof(double) * 7 * n_lf, hipMemcpyHostToDevice, stream));
-    if (d_status) TRY_OUT(hipMemsetAsync(d_status, 0xff, sizeof(int32_t) * 4 * n_lf, stream));
-    if (d_nfev) TRY_OUT(hipMemsetAsync(d_nfev, 0, sizeof(int32_t) * 4 * n_lf, stream));
+        HIP_TRY(hipMemcpyAsync(d_angles, angles, sizeof(double) * 7 * n_lf, hipMemcpyHostToDevice, stream));
+    if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0xff, sizeof(int32_t) * 4 * n_lf, stream));
+    if (d_nfev) HIP_TRY(hipMemsetAsync(d_nfev, 0, sizeof(int32_t) * 4 * n_lf, stream));
     SeqikOptions dev_opt;
     if (opt) dev_opt = *opt; else memset(&dev_opt, 0, sizeof(dev_opt));
     dev_opt.chunk_flags = d_flags;
     if (want_stats) {
-        TRY_OUT(hipMemsetAsync(d_stats, 0, sizeof(int32_t) * 16, stream));  // stays zero when the call is not chunked
+        HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(int32_t) * 16, stream));  // stays zero when the call is not chunked
         dev_opt.chunk_stats = d_stats;
     }
     rc = seqik_solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, first_stage, last_stage, d_angles,
                                 d_fk, d_status, d_nfev, d_init, nullptr, affine, opt ? &dev_opt : nullptr, stream);
     if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    if (want_stats) TRY_OUT(hipMemcpyAsync(opt->chunk_stats, d_stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, stream));
-    if (want_flags) TRY_OUT(hipMemcpyAsync(opt->chunk_flags, d_flags, n_flags, hipMemcpyDeviceToHost, stream));
-    TRY_OUT(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (want_fk) TRY_OUT(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (status) TRY_OUT(hipMemcpyAsync(status, d_status, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (nfev) TRY_OUT(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
-    TRY_OUT(hipStreamSynchronize(stream));
+    if (want_stats) HIP_TRY(hipMemcpyAsync(opt->chunk_stats, d_stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, stream));
+    if (want_flags) HIP_TRY(hipMemcpyAsync(opt->chunk_flags, d_flags, n_flags, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
+    if (want_fk) HIP_TRY(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
+    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
+    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return check_faults("seqik_solve_seq", known_slot(stream));
 }
 
@@ -1942,6 +1955,5 @@ int seqik_frame_chunk_plan(int64_t n_frames, const SeqikOptions *opt, int32_t *c
     if (n_chunks) *n_chunks = chunked ? k : 0;
     return SEQIK_OK;
 }
-#undef TRY_OUT
 
 }  // extern "C"
