@@ -1,0 +1,220 @@
+// seqik_fk.hip -- forward kinematics from joint angles: kernel and C ABI entry points (include/seqik_fk.h).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include "seqik_fk.hpp"
+#include "seqik_device_scope.hpp"
+#include "seqik_hostctx.hpp"
+#include "../../include/seqik_fk.h"
+
+extern "C" void seqik_set_error(int code, const char *msg);
+
+namespace {
+
+struct FkArgs {
+    const double *angles;  // [n_total][7]
+    const double *pose;    // nullable, [n_total][5][3]
+    const double *origin;  // nullable, [n_total][3]
+    double *fk;            // [n_total][9][3]
+    double *dist;          // nullable, [n_total][4]
+    int64_t n_frames;      // leg-frame i belongs to leg (i / n_frames) % n_legs
+    int64_t n_total;       // n_seq * n_legs * n_frames
+    int32_t n_legs;
+    int32_t pad_;
+    seqik::FkLeg legs[seqik::kFkMaxLegs];
+};
+
+constexpr int kFkRow = 27;           // doubles of FK per leg-frame
+constexpr int kFkWaveLds = 64 * kFkRow;  // doubles of LDS per wavefront (STAGED)
+
+// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (see seqik_head.hip)
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ const double *fk_origin(const FkArgs &a, int64_t i)
+{
+    return a.pose ? a.pose + i * 15 : (a.origin ? a.origin + i * 3 : nullptr);
+}
+
+__device__ __forceinline__ void fk_store_dist(const FkArgs &a, int64_t i, const double *row)
+{
+    if (a.dist) {
+        double d[4];
+        seqik::fk_fit_distances(row, a.pose + i * 15, d);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.dist[i * 4 + k] = d[k];
+    }
+}
+
+// One leg-frame per lane, grid-stride over the flat index (64-bit throughout).  Per leg-frame 56 B of angles in and
+// 216 B of FK out (+ 24 B origin / 120 B pose in, 32 B distances out): a map bound by memory, not by its few hundred FP64
+// operations.
+//   per lane (STAGED false): each lane loads its 7 angles and stores its 27 values itself; one store instruction of a
+//     wavefront then touches 64 records 216 B apart.
+//   STAGED: a wavefront's 64 consecutive leg-frames are one contiguous block per array; the angles come in as 7 fully
+//     coalesced loads into LDS, the lanes pick their 7 from there, write their 27 values back into the same LDS and the
+//     wavefront stores the block as 27 fully coalesced lines (non-temporal: written once).  Whole wavefronts only; the
+//     tail of the range takes the per-lane path.
+template <int KIND, bool STAGED>
+__global__ void __launch_bounds__(1024) seqik_fk_kernel(FkArgs a)
+{
+    extern __shared__ double s_fk[];  // STAGED: kFkWaveLds doubles per wavefront
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = a.n_total;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x; t0 < n; t0 += stride) {
+        const int64_t i = t0 + threadIdx.x;
+        const int64_t w0 = t0 + wave * 64;  // first leg-frame of this wavefront
+        if (STAGED && w0 + 64 <= n) {
+            double *st = s_fk + wave * kFkWaveLds;
+            const double *ga = a.angles + w0 * 7;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) st[k * 64 + lane] = __builtin_nontemporal_load(ga + k * 64 + lane);
+            wave_lds_fence();
+            double x[7];
+#pragma unroll
+            for (int d = 0; d < 7; ++d) x[d] = st[lane * 7 + d];
+            wave_lds_fence();  // every lane has its angles before any lane overwrites them with FK rows
+            const int leg = (int)((i / a.n_frames) % a.n_legs);
+            double *row = st + lane * kFkRow;
+            seqik::fk_leg_frame<KIND>(a.legs[leg], x, fk_origin(a, i), row);
+            fk_store_dist(a, i, row);
+            wave_lds_fence();
+            double *gf = a.fk + w0 * kFkRow;
+#pragma unroll
+            for (int k = 0; k < kFkRow; ++k) __builtin_nontemporal_store(st[k * 64 + lane], gf + k * 64 + lane);
+            wave_lds_fence();  // the next iteration's LDS writes stay behind these reads
+        } else if (i < n) {
+            const int leg = (int)((i / a.n_frames) % a.n_legs);
+            double row[kFkRow];
+            seqik::fk_leg_frame<KIND>(a.legs[leg], a.angles + i * 7, fk_origin(a, i), row);
+            fk_store_dist(a, i, row);
+            double *gf = a.fk + i * kFkRow;
+#pragma unroll
+            for (int k = 0; k < kFkRow; ++k) gf[k] = row[k];
+        }
+    }
+}
+
+int hip_fail(hipError_t e, const char *what)
+{
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
+    seqik_set_error(SEQIK_ERR_HIP, buf);
+    return SEQIK_ERR_HIP;
+}
+
+#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
+
+int bad_arg(const char *msg)
+{
+    seqik_set_error(SEQIK_ERR_BAD_ARG, msg);
+    return SEQIK_ERR_BAD_ARG;
+}
+
+// The checks both entry points make before anything touches HIP; *n_total receives n_seq * n_legs * n_frames.
+int fk_validate(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
+                int32_t kind, const double *pose, const double *origin, const double *fk, const double *dist,
+                int64_t *n_total)
+{
+    if (n_legs < 1 || n_legs > seqik::kFkMaxLegs)
+        return bad_arg("seqik_forward_kinematics: n_legs must lie in 1..8");
+    if (n_seq < 0 || n_frames < 0) return bad_arg("seqik_forward_kinematics: negative n_seq or n_frames");
+    if (!angles || !fk) return bad_arg("seqik_forward_kinematics: angles and fk must not be null");
+    if (!legs) return bad_arg("seqik_forward_kinematics: legs must not be null");
+    if (kind != SEQIK_FK_KIND_SEQ && kind != SEQIK_FK_KIND_GENERIC)
+        return bad_arg("seqik_forward_kinematics: kind must be 0 (sequential chain) or 1 (generic chain)");
+    if (pose && origin) return bad_arg("seqik_forward_kinematics: pass pose or origin, not both");
+    if (dist && !pose) return bad_arg("seqik_forward_kinematics: dist needs pose (the key points to measure against)");
+    for (int l = 0; l < n_legs; ++l)
+        for (int k = 0; k < 4; ++k)
+            if (!seqik::is_finite(legs[l].seg[k])) return bad_arg("seqik_forward_kinematics: non-finite segment length");
+    // the largest array has 27 doubles per leg-frame: its byte count must fit in 63 bits
+    const int64_t lim = INT64_MAX / (8 * kFkRow);
+    if (n_seq != 0 && n_frames != 0 && (n_seq > lim / n_legs || n_seq * n_legs > lim / n_frames))
+        return bad_arg("seqik_forward_kinematics: too many leg-frames");
+    *n_total = n_seq * n_legs * n_frames;
+    return SEQIK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int seqik_forward_kinematics_device(const double *d_angles, int64_t n_seq, int32_t n_legs, int64_t n_frames,
+                                    const SeqikLegParams *legs, int32_t kind, const double *d_pose,
+                                    const double *d_origin, double *d_fk, double *d_dist, void *hip_stream)
+{
+    int64_t n = 0;
+    int rc = fk_validate(d_angles, n_seq, n_legs, n_frames, legs, kind, d_pose, d_origin, d_fk, d_dist, &n);
+    if (rc != SEQIK_OK) return rc;
+    if (n == 0) return SEQIK_OK;
+    FkArgs a;
+    a.angles = d_angles; a.pose = d_pose; a.origin = d_origin; a.fk = d_fk; a.dist = d_dist;
+    a.n_frames = n_frames; a.n_total = n; a.n_legs = n_legs; a.pad_ = 0;
+    for (int l = 0; l < seqik::kFkMaxLegs; ++l) seqik::make_fk_leg(legs[l < n_legs ? l : 0], a.legs[l]);
+    // LDS-staged by default: 6 M leg-frames in 0.296 ms = 1.00 x a copy of the same traffic, the per-lane kernel 0.508 ms =
+    // 0.58 x (profiles/fk_bench_r07.json, EXPERIMENTS.md 7.1).  SEQIK_FK_STAGED = 0 / 1 and SEQIK_FK_BLOCK (threads per
+    // workgroup, 64..1024) select variants for measurements and tests; read per call so that one process can run both.
+    const char *env_staged = getenv("SEQIK_FK_STAGED"), *env_block = getenv("SEQIK_FK_BLOCK");
+    const bool staged = env_staged ? atoi(env_staged) != 0 : true;
+    int block = env_block ? atoi(env_block) : 256;
+    if (block < 64 || block > 1024 || block % 64) block = 256;
+    if (staged && block > 256) block = 256;  // 13.5 KiB of LDS per wavefront: at most 54 KiB per workgroup
+    int64_t blocks = (n + block - 1) / block;
+    if (blocks > 256 * 64) blocks = 256 * 64;  // grid-stride beyond 64 workgroups per CU (as seqik_head.hip)
+    const size_t lds = staged ? sizeof(double) * kFkWaveLds * (block / 64) : 0;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+#define FK_LAUNCH(K, ST) hipLaunchKernelGGL((seqik_fk_kernel<K, ST>), dim3((unsigned)blocks), dim3(block), lds, s, a)
+    if (kind == SEQIK_FK_KIND_SEQ) { if (staged) FK_LAUNCH(0, true); else FK_LAUNCH(0, false); }
+    else { if (staged) FK_LAUNCH(1, true); else FK_LAUNCH(1, false); }
+#undef FK_LAUNCH
+    HTRY(hipGetLastError());
+    return SEQIK_OK;
+}
+
+int seqik_forward_kinematics(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_frames,
+                             const SeqikLegParams *legs, int32_t kind, const double *pose, const double *origin,
+                             double *fk, double *dist, int32_t device)
+{
+    int64_t n = 0;
+    int rc = fk_validate(angles, n_seq, n_legs, n_frames, legs, kind, pose, origin, fk, dist, &n);
+    if (rc != SEQIK_OK) return rc;
+    if (n == 0) return SEQIK_OK;
+    seqik::DeviceScope scope;
+    HTRY(scope.enter(device));
+    const size_t b_ang = sizeof(double) * 7 * (size_t)n, b_fk = sizeof(double) * kFkRow * (size_t)n;
+    const size_t b_pose = pose ? sizeof(double) * 15 * (size_t)n : 0, b_org = origin ? sizeof(double) * 3 * (size_t)n : 0;
+    const size_t b_dist = dist ? sizeof(double) * 4 * (size_t)n : 0;
+    seqik::HostLeaseGuard g;
+    rc = seqik::host_lease_acquire(&g.lease);
+    if (rc != SEQIK_OK) return rc;
+    rc = seqik::host_lease_reserve(&g.lease, seqik::arena_padded(b_ang) + seqik::arena_padded(b_fk) +
+                                                 seqik::arena_padded(b_pose) + seqik::arena_padded(b_org) +
+                                                 seqik::arena_padded(b_dist));
+    if (rc != SEQIK_OK) return rc;
+    hipStream_t stream = g.lease.stream;
+    char *p = g.lease.arena;
+    double *d_ang = reinterpret_cast<double *>(p); p += seqik::arena_padded(b_ang);
+    double *d_fk = reinterpret_cast<double *>(p); p += seqik::arena_padded(b_fk);
+    double *d_pose = pose ? reinterpret_cast<double *>(p) : nullptr; p += seqik::arena_padded(b_pose);
+    double *d_org = origin ? reinterpret_cast<double *>(p) : nullptr; p += seqik::arena_padded(b_org);
+    double *d_dist = dist ? reinterpret_cast<double *>(p) : nullptr;
+    HTRY(hipMemcpyAsync(d_ang, angles, b_ang, hipMemcpyHostToDevice, stream));
+    if (d_pose) HTRY(hipMemcpyAsync(d_pose, pose, b_pose, hipMemcpyHostToDevice, stream));
+    if (d_org) HTRY(hipMemcpyAsync(d_org, origin, b_org, hipMemcpyHostToDevice, stream));
+    rc = seqik_forward_kinematics_device(d_ang, n_seq, n_legs, n_frames, legs, kind, d_pose, d_org, d_fk, d_dist, stream);
+    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
+    HTRY(hipMemcpyAsync(fk, d_fk, b_fk, hipMemcpyDeviceToHost, stream));
+    if (d_dist) HTRY(hipMemcpyAsync(dist, d_dist, b_dist, hipMemcpyDeviceToHost, stream));
+    HTRY(hipStreamSynchronize(stream));
+    return SEQIK_OK;
+}
+
+}  // extern "C"

@@ -22,9 +22,10 @@ _NATIVE = os.path.join(_PKG, "_native")
 _IN_TREE = not os.path.isfile(os.path.join(_NATIVE, "libseqik_hip.so")) and os.path.isfile(os.path.join(CSRC, "seqik_hip.hip"))
 _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
-SOURCES = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_core.hpp",
-           "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_hostctx.hpp"]
-COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip"]
+SOURCES = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
+           "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
+           "seqik_hostctx.hpp", "seqik_fk.hpp"]
+COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -342,6 +343,14 @@ def load():
         for name in ("seqik_align_stats_reset", "seqik_align_stats_close"):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [ctypes.c_void_p]
+        L.seqik_forward_kinematics.restype = ctypes.c_int
+        L.seqik_forward_kinematics.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                               ctypes.c_int32]
+        L.seqik_forward_kinematics_device.restype = ctypes.c_int
+        L.seqik_forward_kinematics_device.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                                      ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _lib = L
         return _lib
 
@@ -357,6 +366,69 @@ EXPORTED_SYMBOLS = ["seqik_abi_version", "seqik_device_count", "seqik_last_error
                     "seqik_stream_open", "seqik_stream_submit", "seqik_stream_wait", "seqik_stream_reset_carry", "seqik_stream_set_carry",
                     "seqik_stream_close", "seqik_align_stats_open", "seqik_align_stats_add",
                     "seqik_align_stats_finish", "seqik_align_stats_reset", "seqik_align_stats_close"]
+
+#: entry points of include/seqik_fk.h (forward kinematics from joint angles), kept apart from the ABI-7 set of seqik.h
+FK_EXPORTED_SYMBOLS = ["seqik_forward_kinematics", "seqik_forward_kinematics_device"]
+FK_KINDS = {"seq": 0, "generic": 1}
+
+
+def _fk_kind(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in FK_KINDS:
+            raise ValueError(f"kind must be one of {sorted(FK_KINDS)}, got {kind!r}")
+        return FK_KINDS[kind]
+    return int(kind)
+
+
+def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_dist=False, device=-1):
+    """``seqik_forward_kinematics`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(fk (S, L, N, 9, 3),
+    dist (S, L, N, 4) or None), the rows the solvers write (``solve_seq`` / ``solve_generic``).
+
+    ``kind``: ``"seq"`` (KinematicChainSeq) or ``"generic"`` (KinematicChainGeneric) -- the chain that produced the angles.
+    The origin of each leg-frame is key point 0 of ``pose`` (S, L, N, 5, 3), or ``origin`` (anything that broadcasts to
+    (S, L, N, 3); the fused alignment's origin is ``template_coxa``), or 0 when neither is given (leg-local positions).
+    ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  A non-finite angle makes that
+    leg-frame's rows NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
+    angles = np.ascontiguousarray(angles, dtype=np.float64)
+    if angles.ndim != 4 or angles.shape[3] != 7:
+        raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
+    S, L, N = angles.shape[:3]
+    if len(legs) != L:
+        raise ValueError("one SeqikLegParams per leg expected")
+    k = _fk_kind(kind)
+    if pose is not None and origin is not None:
+        raise ValueError("pass pose or origin, not both")
+    if want_dist and pose is None:
+        raise ValueError("want_dist needs pose (the key points to measure against)")
+    if pose is not None:
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        if pose.shape != (S, L, N, 5, 3):
+            raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    if origin is not None:
+        origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64), (S, L, N, 3)))
+    fk = np.full((S, L, N, 9, 3), np.nan)
+    dist = np.full((S, L, N, 4), np.nan) if want_dist else None
+    rc = load().seqik_forward_kinematics(angles.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs), k,
+                                         pose.ctypes.data_as(_dp) if pose is not None else None,
+                                         origin.ctypes.data_as(_dp) if origin is not None else None,
+                                         fk.ctypes.data_as(_dp), dist.ctypes.data_as(_dp) if dist is not None else None,
+                                         int(device))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    return dict(fk=fk, dist=dist)
+
+
+def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kind="seq", d_pose=0, d_origin=0, d_dist=0,
+                              stream=0):
+    """``seqik_forward_kinematics_device``: raw device pointers (ints) in the dense layouts of ``forward_kinematics``,
+    asynchronous on ``stream`` (a hipStream_t as int; 0 = the default stream) of the current device."""
+    arr = (SeqikLegParams * n_legs)(*legs)
+    rc = load().seqik_forward_kinematics_device(ctypes.c_void_p(int(d_angles) or None), int(n_seq), int(n_legs),
+                                                int(n_frames), arr, _fk_kind(kind), ctypes.c_void_p(int(d_pose) or None),
+                                                ctypes.c_void_p(int(d_origin) or None), ctypes.c_void_p(int(d_fk) or None),
+                                                ctypes.c_void_p(int(d_dist) or None), ctypes.c_void_p(int(stream) or None))
+    if rc != SEQIK_OK:
+        _raise(rc)
 
 
 class AlignStats:

@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .data import DOFS, INITIAL_ANGLES
+from .data import DOFS, INITIAL_ANGLES, SEGMENTS
 from .kinematic_chain import Chain, KinematicChainBase, KinematicChainGeneric, KinematicChainSeq, LEG_NAMES
 from .utils import save_file
 
@@ -181,6 +181,96 @@ class LegInvKinBase(ABC):
             out.append((segment_name, leg_name, segment_array))
         return out
 
+    # -- forward kinematics from joint angles (include/seqik_fk.h) ------------------------
+    #: chain kind of the angles this class produces (``_lib.forward_kinematics``)
+    _fk_kind = "seq"
+
+    def _fk_leg_params(self, leg_name):
+        """SeqikLegParams carrying only what forward kinematics reads: the segment lengths."""
+        lp = _lib.SeqikLegParams()
+        for i, seg in enumerate(SEGMENTS):
+            lp.seg[i] = float(self.kinematic_chain_class.body_size[f"{leg_name}_{seg}"])
+        return lp
+
+    def _fk_angles(self, joint_angles, leg_name):
+        """(N, 7) array in DOFS order from ``Angle_<leg>_<dof>`` entries."""
+        cols = []
+        for dof in DOFS:
+            key = f"Angle_{leg_name}_{dof}"
+            if key not in joint_angles:
+                raise ValueError(f"joint angles have no entry {key!r}")
+            cols.append(np.asarray(joint_angles[key], dtype=np.float64).reshape(-1))
+        if len({c.shape[0] for c in cols}) != 1:
+            raise ValueError(f"the joint angles of {leg_name} have different frame counts: "
+                             f"{sorted({c.shape[0] for c in cols})}")
+        return np.stack(cols, axis=1)
+
+    def _fk_key_points(self, leg_name, segment_array):
+        """(N, 5, 3) key points the solver of this class fits: origin, then the four end effectors."""
+        return np.asarray(segment_array, dtype=np.float64)[:, :5, :]
+
+    def _fk_batches(self, joint_angles, origin=None, want_pose=False):
+        """Per group of legs with the same frame count: (items, angles (1, L, N, 7), origin or pose array)."""
+        ja = self.joint_angles_dict if joint_angles is None else joint_angles
+        groups = {}
+        for segment_name, leg_name, arr in self._leg_segments():
+            ang = self._fk_angles(ja, leg_name)
+            groups.setdefault(ang.shape[0], []).append((segment_name, leg_name, arr, ang))
+        for n, items in groups.items():
+            per_leg = []
+            for segment_name, leg_name, arr, _ in items:
+                if origin is not None and not want_pose:
+                    o = np.asarray(origin, dtype=np.float64)
+                    if o.shape not in ((3,), (n, 3)):
+                        raise ValueError(f"origin must have shape (3,) or ({n}, 3), got {o.shape}")
+                    per_leg.append(np.broadcast_to(o, (n, 3)))
+                    continue
+                n_pos = np.asarray(arr).shape[0]
+                if n_pos != n:
+                    raise ValueError(f"{segment_name}: the joint angles have {n} frames, aligned_pos has {n_pos}")
+                kp = self._fk_key_points(leg_name, arr)
+                per_leg.append(kp if want_pose else kp[:, 0])
+            yield items, np.stack([a for *_, a in items])[None], np.stack(per_leg)[None]
+
+    def run_fk(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, export_path: Union[Path, str] = None,
+               origin: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+        """Forward kinematics of every leg from joint angles alone, on the GPU (``seqik_forward_kinematics``).
+
+        The reference obtains joint positions only inside its IK loop (``calculate_fk`` per frame and stage,
+        leg_inverse_kinematics.py:71-77, stored for stage 4 at :279-282); this computes the same ``(N, 9, 3)`` rows for
+        angles from any source -- an earlier run's ``leg_joint_angles.pkl``, ``utils.interpolate_joint_angles``, edited
+        angles.  ``joint_angles`` defaults to ``self.joint_angles_dict`` (``Angle_<leg>_<dof>`` entries; a missing one
+        raises ``ValueError``); the chain kind follows the class.  ``origin`` defaults to key point 0 of ``aligned_pos``
+        (whose frame count must match) -- ``template_coxa`` for a ``LegInvKinSeq`` with ``leg_affine``; an explicit
+        ``(3,)`` or ``(N, 3)`` array is used for every leg.  After ``run_ik_and_fk`` the result equals its forward
+        kinematics dict bit for bit.  ``export_path``: writes ``forward_kinematics.pkl`` there.
+        Returns ``{segment_name: (N, 9, 3)}`` in the order of ``aligned_pos``."""
+        out = {}
+        for items, angles, org in self._fk_batches(joint_angles, origin):
+            legs = [self._fk_leg_params(leg_name) for _, leg_name, _, _ in items]
+            fk = _lib.forward_kinematics(angles, legs, kind=self._fk_kind, origin=org, device=self.device)["fk"]
+            for li, (segment_name, *_) in enumerate(items):
+                out[segment_name] = fk[0, li].copy()
+        out = {name: out[name] for name, _, _ in self._leg_segments()}
+        if export_path is not None:
+            save_file(Path(export_path) / "forward_kinematics.pkl", out)
+            self.logger.info("Forward kinematics are saved at %s", export_path)
+        return out
+
+    def fit_error(self, joint_angles: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+        """How far the reconstructed CTr, FTi, TiTa and claw lie from the key points they were fitted to:
+        ``{segment_name: (N, 4)}`` Euclidean distances of forward-kinematics rows 4, 6, 7, 8 from key points 1..4 of
+        ``aligned_pos`` (the targets of stages 1-4, leg_inverse_kinematics.py:279-282; the generic chain's claw target
+        is the last key point).  Computed on the GPU with the forward kinematics (``seqik_forward_kinematics``, ``dist``)."""
+        out = {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._fk_leg_params(leg_name) for _, leg_name, _, _ in items]
+            d = _lib.forward_kinematics(angles, legs, kind=self._fk_kind, pose=pose, want_dist=True,
+                                        device=self.device)["dist"]
+            for li, (segment_name, *_) in enumerate(items):
+                out[segment_name] = d[0, li].copy()
+        return {name: out[name] for name, _, _ in self._leg_segments()}
+
     def _export(self, export_path, forward_kinematics_dict):
         if export_path is not None:
             save_file(Path(export_path) / "forward_kinematics.pkl", forward_kinematics_dict)
@@ -247,6 +337,19 @@ class LegInvKinSeq(LegInvKinBase):
         self.frame_chunk_stats = {}
         #: per leg, where a chunked run was hard (see ``run_ik_and_fk``); empty after a serial walk
         self.frame_chunk_report = {}
+
+    def _fk_key_points(self, leg_name, segment_array):
+        """Key points in the frame the solver works in: with ``leg_affine`` ``aligned_pos`` holds RAW key points and the
+        fused alignment (``AlignPose.align_leg``) is applied here with the kernels' operations: row 0 = template_coxa,
+        rows 1..4 = (raw - fixed_coxa) * scale + template_coxa."""
+        kp = super()._fk_key_points(leg_name, segment_array)
+        if self.leg_affine is None:
+            return kp
+        fixed, scale, template = (np.asarray(v, dtype=np.float64) for v in self.leg_affine[leg_name])
+        out = np.empty_like(kp)
+        out[:, 0] = template
+        out[:, 1:] = (kp[:, 1:] - fixed) * scale + template
+        return out
 
     def _leg_params(self, leg_name, initial_angles=None):
         kc = self.kinematic_chain_class
@@ -410,6 +513,13 @@ class LegInvKinGeneric(LegInvKinBase):
                  log_level: Literal["DEBUG", "INFO", "WARNING", "ERROR"] = "INFO") -> None:
         super().__init__(aligned_pos, kinematic_chain_class, initial_angles, log_level)
         self.joint_angles_dict = {}
+
+    _fk_kind = "generic"
+
+    def _fk_key_points(self, leg_name, segment_array):
+        arr = np.asarray(segment_array, dtype=np.float64)
+        # the claw (last key point) is the end effector (:587), as in run_ik_and_fk
+        return arr[:, [0, 1, 2, 3, -1], :] if arr.shape[1] >= 5 else arr
 
     def _leg_params(self, leg_name, seed9):
         kc = self.kinematic_chain_class

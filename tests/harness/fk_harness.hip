@@ -1,0 +1,25 @@
+// TEST INFRASTRUCTURE ONLY -- not part of the product, never loaded by seqikpy_amd.
+//
+// Runs the forward-kinematics device function (csrc/seqik_fk.hpp, `__host__ __device__`) on the HOST, one leg-frame
+// after the other, so that the CPU-only test tier can compare it bit for bit with the FK rows the solvers' device code
+// writes (tests/harness/host_harness.hip) and with the oracle.  Built by tests/test_forward_kinematics.py with
+// `hipcc --offload-host-only`.
+#include "../../sequential-inverse-kinematics_amd/csrc/seqik_fk.hpp"
+
+// angles [n][7] (DOFS order), origin nullable [n][origin_stride] (15: a pose array, its key point 0; 3: origins),
+// fk [n][9][3], dist nullable [n][4] (needs origin_stride 15: measured against that pose)
+extern "C" int harness_fk(const double *angles, int64_t n, const SeqikLegParams *leg, int32_t kind, const double *origin,
+                          int64_t origin_stride, double *fk, double *dist)
+{
+    if (kind != seqik::FK_KIND_SEQ && kind != seqik::FK_KIND_GENERIC) return SEQIK_ERR_BAD_ARG;
+    if (dist && (!origin || origin_stride != 15)) return SEQIK_ERR_BAD_ARG;
+    seqik::FkLeg fl;
+    seqik::make_fk_leg(*leg, fl);
+    for (int64_t i = 0; i < n; ++i) {
+        const double *o = origin ? origin + i * origin_stride : nullptr;
+        if (kind == seqik::FK_KIND_SEQ) seqik::fk_leg_frame<seqik::FK_KIND_SEQ>(fl, angles + i * 7, o, fk + i * 27);
+        else seqik::fk_leg_frame<seqik::FK_KIND_GENERIC>(fl, angles + i * 7, o, fk + i * 27);
+        if (dist) seqik::fk_fit_distances(fk + i * 27, o, dist + i * 4);
+    }
+    return SEQIK_OK;
+}
