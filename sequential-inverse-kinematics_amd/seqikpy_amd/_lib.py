@@ -23,9 +23,10 @@ _IN_TREE = not os.path.isfile(os.path.join(_NATIVE, "libseqik_hip.so")) and os.p
 _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 SOURCES = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
-           "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
-           "seqik_hostctx.hpp", "seqik_fk.hpp"]
-COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip"]
+           "seqik_gaps.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp",
+           "seqik_device_scope.hpp", "seqik_hostctx.hpp", "seqik_fk.hpp", "seqik_gaps.hpp"]
+COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
+                 "seqik_gaps.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -351,6 +352,22 @@ def load():
         L.seqik_forward_kinematics_device.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                                       ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        _vp = ctypes.c_void_p
+        L.seqik_gaps_compact_device.restype = ctypes.c_int
+        L.seqik_gaps_compact_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                ctypes.POINTER(SeqikLegParams), _vp, _vp, _vp, _vp]
+        L.seqik_gaps_expand_device.restype = ctypes.c_int
+        L.seqik_gaps_expand_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.seqik_solve_seq_gaps.restype = ctypes.c_int
+        L.seqik_solve_seq_gaps.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                           ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_int32,
+                                           _dp, _dp, _ip, _ip, _dp, ctypes.POINTER(SeqikAffine),
+                                           ctypes.POINTER(SeqikOptions), _ip]
+        L.seqik_solve_generic_gaps.restype = ctypes.c_int
+        L.seqik_solve_generic_gaps.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.POINTER(SeqikLegParams), _dp, _dp, _ip, _ip, _dp,
+                                               ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikOptions), _ip]
         _lib = L
         return _lib
 
@@ -429,6 +446,121 @@ def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kin
                                                 ctypes.c_void_p(int(d_dist) or None), ctypes.c_void_p(int(stream) or None))
     if rc != SEQIK_OK:
         _raise(rc)
+
+
+#: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h
+GAPS_EXPORTED_SYMBOLS = ["seqik_gaps_compact_device", "seqik_gaps_expand_device", "seqik_solve_seq_gaps",
+                         "seqik_solve_generic_gaps"]
+#: status of a missing leg-frame in skip mode (``SEQIK_STATUS_MISSING``; scipy's statuses are -1..4)
+STATUS_MISSING = -100
+GAPS_SEQ, GAPS_GENERIC, GAPS_AFFINE = 0, 1, 2
+MISSING_MODES = ("raise", "skip")
+
+
+def check_missing_mode(missing) -> bool:
+    """True for ``"skip"``, False for ``"raise"``; anything else is a ``ValueError``."""
+    if missing not in MISSING_MODES:
+        raise ValueError(f"missing key points: expected one of {MISSING_MODES}, got {missing!r}")
+    return missing == "skip"
+
+
+def _ptr(x, name="buffer", shape=None, dtype="float64"):
+    """A raw device pointer (int) or a tensor's ``data_ptr()``; 0 / None = NULL.  A tensor is checked against what the
+    kernel will read or write through the pointer: a contiguous GPU tensor of ``dtype`` with ``shape``'s element count."""
+    if x is None:
+        return None
+    if hasattr(x, "data_ptr"):
+        if str(x.dtype) != f"torch.{dtype}":
+            raise ValueError(f"{name}: expected a {dtype} tensor, got {x.dtype}")
+        if shape is not None and x.numel() != int(np.prod(shape)):
+            raise ValueError(f"{name}: expected {int(np.prod(shape))} elements {tuple(shape)}, got {x.numel()} "
+                             f"{tuple(x.shape)}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor")
+        if not x.is_cuda:
+            raise ValueError(f"{name}: expected a GPU tensor, got one on {x.device}")
+        return ctypes.c_void_p(x.data_ptr() or None)
+    return ctypes.c_void_p(int(x) or None)
+
+
+def _gaps_flags(kind, affine) -> int:
+    return (GAPS_GENERIC if _fk_kind(kind) == 1 else GAPS_SEQ) | (GAPS_AFFINE if affine else 0)
+
+
+def gaps_compact_device(d_pose, n_seq, n_legs, n_frames, legs, d_cpose, d_map, d_n_valid, kind="seq", affine=False,
+                        stream=0):
+    """``seqik_gaps_compact_device``: pose (S, L, N, 5, 3) float64 -> the compacted and padded pose (same shape), the
+    frame map (S, L, N) int32 (compact slot, -1 = missing) and n_valid (S, L) int32.  Raw device pointers (ints) or torch
+    tensors; asynchronous on ``stream`` (a hipStream_t as int, or a torch stream).  ``kind`` ("seq" / "generic") and
+    ``affine`` (the solve will use the fused alignment) decide which key points count (include/seqik_gaps.h)."""
+    arr = (SeqikLegParams * n_legs)(*legs)
+    lf, ch = (n_seq, n_legs, n_frames), (n_seq, n_legs)
+    rc = load().seqik_gaps_compact_device(_ptr(d_pose, "pose", lf + (5, 3)), int(n_seq), int(n_legs), int(n_frames),
+                                          _gaps_flags(kind, affine), arr, _ptr(d_cpose, "cpose", lf + (5, 3)),
+                                          _ptr(d_map, "map", lf, "int32"), _ptr(d_n_valid, "n_valid", ch, "int32"),
+                                          _stream_ptr(stream))
+    if rc != SEQIK_OK:
+        _raise(rc)
+
+
+def gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cfk=0, d_fk=0, d_cstatus=0, d_status=0,
+                       d_cnfev=0, d_nfev=0, kind="seq", stream=0):
+    """``seqik_gaps_expand_device``: compact angles / fk / status / nfev back to original frame order; NaN,
+    ``STATUS_MISSING`` and 0 at the missing frames.  fk, status and nfev are optional pairs."""
+    lf = (n_seq, n_legs, n_frames)
+    sw = (1,) if _fk_kind(kind) == 1 else (4,)
+    rc = load().seqik_gaps_expand_device(_ptr(d_map, "map", lf, "int32"), int(n_seq), int(n_legs), int(n_frames),
+                                         _gaps_flags(kind, False), _ptr(d_cangles, "cangles", lf + (7,)),
+                                         _ptr(d_cfk, "cfk", lf + (9, 3)), _ptr(d_cstatus, "cstatus", lf + sw, "int32"),
+                                         _ptr(d_cnfev, "cnfev", lf + sw, "int32"), _ptr(d_angles, "angles", lf + (7,)),
+                                         _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_status, "status", lf + sw, "int32"),
+                                         _ptr(d_nfev, "nfev", lf + sw, "int32"), _stream_ptr(stream))
+    if rc != SEQIK_OK:
+        _raise(rc)
+
+
+def _stream_ptr(stream):
+    if stream is None:
+        return None
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    return ctypes.c_void_p(s or None)
+
+
+def solve_seq_gaps_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_cpose, d_map, d_n_valid, d_cangles,
+                          d_fk=0, d_cfk=0, d_status=0, d_cstatus=0, d_nfev=0, d_cnfev=0, affine=None, d_init=0, stream=0,
+                          **solve_options):
+    """Skip mode on device buffers: compact -> ``solve_seq_device`` -> expand, enqueued on ``stream`` from caller-provided
+    buffers (raw pointers or torch tensors): the compacted pose, map and n_valid of ``gaps_compact_device`` and compact
+    angles / fk / status / nfev of the solver's shapes.  ``solve_options``: the frame-chunk and launch options of
+    ``solve_seq_device``.  Equals ``solve_seq(..., missing="skip")`` bit for bit."""
+    def raw(x, name, shape, dtype="float64"):
+        p = _ptr(x, name, shape, dtype)
+        return p.value or 0 if p is not None else 0
+    lf = (n_seq, n_legs, n_frames)
+    def given(x):
+        return x is not None and (hasattr(x, "data_ptr") or int(x) != 0)
+    for a, b, name in ((d_fk, d_cfk, "fk"), (d_status, d_cstatus, "status"), (d_nfev, d_cnfev, "nfev")):
+        if given(a) != given(b):
+            raise ValueError(f"{name} and c{name} are a pair: give both or neither")
+    # every buffer is checked here, before anything is enqueued
+    c_ptrs = (raw(d_cpose, "cpose", lf + (5, 3)), raw(d_cangles, "cangles", lf + (7,)), raw(d_cfk, "cfk", lf + (9, 3)),
+              raw(d_cstatus, "cstatus", lf + (4,), "int32"), raw(d_cnfev, "cnfev", lf + (4,), "int32"),
+              raw(d_init, "init", (n_seq, n_legs, 7)))
+    for x, name, shape, dt in ((d_pose, "pose", lf + (5, 3), "float64"), (d_angles, "angles", lf + (7,), "float64"),
+                               (d_map, "map", lf, "int32"), (d_n_valid, "n_valid", (n_seq, n_legs), "int32"),
+                               (d_fk, "fk", lf + (9, 3), "float64"), (d_status, "status", lf + (4,), "int32"),
+                               (d_nfev, "nfev", lf + (4,), "int32")):
+        raw(x, name, shape, dt)
+    if not raw(d_pose, "pose", lf + (5, 3)) or not raw(d_angles, "angles", lf + (7,)) or not c_ptrs[0] or not c_ptrs[1]:
+        raise ValueError("pose, angles, cpose and cangles must be given")
+    s = _stream_ptr(stream)
+    s = s.value or 0 if s is not None else 0
+    gaps_compact_device(d_pose, n_seq, n_legs, n_frames, legs, d_cpose, d_map, d_n_valid, kind="seq",
+                        affine=affine is not None, stream=s)
+    solve_seq_device(c_ptrs[0], n_seq, n_legs, n_frames, legs, c_ptrs[1], c_ptrs[2], c_ptrs[3], c_ptrs[4], stream=s,
+                     affine=affine, d_init=c_ptrs[5], **solve_options)
+    gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cfk, d_fk, d_cstatus, d_status, d_cnfev,
+                       d_nfev, kind="seq", stream=s)
 
 
 class AlignStats:
@@ -567,18 +699,22 @@ def device_attributes(device=0):
 
 
 def solve_generic(pose, legs, want_fk=True, want_diag=False, device=-1, block_size=0, affine=None, init_angles=None,
-                  lanes_per_wave=0, lane_groups=True, chain_queue=0):
+                  lanes_per_wave=0, lane_groups=True, chain_queue=0, missing="raise"):
     """``seqik_solve_generic`` on host arrays: pose (S, L, N, 5, 3) -> dict(angles (S, L, N, 7),
     fk (S, L, N, 9, 3) or None, status / nfev (S, L, N) or None).  ``chain_queue`` (``SeqikOptions.reserved[1]``): batches
     of full wavefronts on persistent wavefronts whose lanes pull chains from a per-leg counter -- 0 = automatic (at least
-    four chains per lane of the GPU), 1 = never, 2 = whenever full wavefronts are used; same bits either way."""
+    four chains per lane of the GPU), 1 = never, 2 = whenever full wavefronts are used; same bits either way.
+    ``missing``: ``"raise"`` or ``"skip"`` as for ``solve_seq`` (``seqik_solve_generic_gaps``; rows 0 and 4 count, row 4
+    only with ``affine``); skip mode adds ``n_valid`` (S, L)."""
+    skip = check_missing_mode(missing)
     pose = np.ascontiguousarray(pose, dtype=np.float64)
     if pose.ndim != 5 or pose.shape[3:] != (5, 3):
         raise ValueError(f"pose must have shape (S, L, N, 5, 3), got {pose.shape}")
     S, L, N = pose.shape[:3]
     if len(legs) != L:
         raise ValueError("one SeqikLegParams per leg expected")
-    _check_finite(pose)
+    if not skip:
+        _check_finite(pose)
     angles = np.zeros((S, L, N, 7))
     fk = np.full((S, L, N, 9, 3), np.nan) if want_fk else None
     status = np.full((S, L, N), -1, dtype=np.int32) if want_diag else None
@@ -593,15 +729,23 @@ def solve_generic(pose, legs, want_fk=True, want_diag=False, device=-1, block_si
     opt.reserved[0] = lanes_per_wave
     opt.reserved[1] = chain_queue
     opt.reserved[3] = 0 if lane_groups else 3  # measurements: thin waves without the split over groups of 8 lanes
-    rc = load().seqik_solve_generic(pose.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs),
-                                    angles.ctypes.data_as(_dp), fk.ctypes.data_as(_dp) if fk is not None else None,
-                                    status.ctypes.data_as(_ip) if status is not None else None,
-                                    nfev.ctypes.data_as(_ip) if nfev is not None else None,
-                                    init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
-                                    _affine_array(affine, L), ctypes.byref(opt))
+    args = (pose.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs),
+            angles.ctypes.data_as(_dp), fk.ctypes.data_as(_dp) if fk is not None else None,
+            status.ctypes.data_as(_ip) if status is not None else None,
+            nfev.ctypes.data_as(_ip) if nfev is not None else None,
+            init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
+            _affine_array(affine, L), ctypes.byref(opt))
+    if skip:
+        n_valid = np.zeros((S, L), dtype=np.int32)
+        rc = load().seqik_solve_generic_gaps(*args, n_valid.ctypes.data_as(_ip))
+    else:
+        rc = load().seqik_solve_generic(*args)
     if rc != SEQIK_OK:
         _raise(rc)
-    return dict(angles=angles, fk=fk, status=status, nfev=nfev)
+    out = dict(angles=angles, fk=fk, status=status, nfev=nfev)
+    if skip:
+        out["n_valid"] = n_valid
+    return out
 
 
 def head_angles(r_head, l_head, neck, rest_head_pitch, rest_antenna_pitch, compute_ant=True, device=-1, head_roll=None):
@@ -722,7 +866,8 @@ def _affine_array(affine, n_legs):
 
 def solve_seq(pose, legs, first_stage=1, last_stage=4, angles=None, want_fk=True, want_diag=False,
               device=-1, block_size=0, affine=None, init_angles=None, lanes_per_wave=0, staged=0, interleave_legs=0,
-              frame_chunk=0, frame_halo=0, chunk_tol=0.0, chunk_rounds=0, pipeline=0, want_chunk_flags=False):
+              frame_chunk=0, frame_halo=0, chunk_tol=0.0, chunk_rounds=0, pipeline=0, want_chunk_flags=False,
+              missing="raise"):
     """``seqik_solve_seq`` on host arrays.
 
     pose: (S, L, N, 5, 3) float64; legs: list of L ``SeqikLegParams``; angles: optional
@@ -737,15 +882,26 @@ def solve_seq(pose, legs, first_stage=1, last_stage=4, angles=None, want_fk=True
     ``device``: HIP device ordinal, -1 = the calling thread's current device.
     ``want_chunk_flags``: also return the per-chunk report ``chunk_flags`` (S, L, K) uint8 (``CHUNK_FLAG_*`` bits: failed
     the first verification / repaired / swept / chain walked serially); None when the call was not chunked.
+    ``missing``: ``"raise"`` (default) refuses non-finite key points as the reference does; ``"skip"`` solves every chain
+    as if its leg-frames with a non-finite key point were not in the recording (``seqik_solve_seq_gaps``,
+    include/seqik_gaps.h): those get NaN angles and FK, status ``STATUS_MISSING`` and nfev 0, the others equal the solve
+    of the compacted recording bit for bit.  Skip mode needs all four stages and no ``want_chunk_flags``; it adds
+    ``n_valid`` (S, L) int32 to the result.
     Returns dict(angles, fk or None, status or None, nfev or None, chunk_stats, chunk_flags).
     """
+    skip = check_missing_mode(missing)
     pose = np.ascontiguousarray(pose, dtype=np.float64)
     if pose.ndim != 5 or pose.shape[3:] != (5, 3):
         raise ValueError(f"pose must have shape (S, L, N, 5, 3), got {pose.shape}")
     S, L, N = pose.shape[:3]
     if len(legs) != L:
         raise ValueError("one SeqikLegParams per leg expected")
-    _check_finite(pose)
+    if skip and (first_stage, last_stage) != (1, 4):
+        raise ValueError("missing='skip' needs all four stages (first_stage=1, last_stage=4)")
+    if skip and want_chunk_flags:
+        raise ValueError("missing='skip' does not report chunk_flags")
+    if not skip:
+        _check_finite(pose)
     if angles is None:
         angles = np.zeros((S, L, N, 7), dtype=np.float64)
     else:
@@ -777,16 +933,23 @@ def solve_seq(pose, legs, first_stage=1, last_stage=4, angles=None, want_fk=True
         if k > 0:
             flags = np.zeros((S, L, k), dtype=np.uint8)
             opt.chunk_flags = flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-    rc = lib.seqik_solve_seq(pose.ctypes.data_as(_dp), S, L, N, arr, first_stage, last_stage,
-                             angles.ctypes.data_as(_dp),
-                             fk.ctypes.data_as(_dp) if fk is not None else None,
-                             status.ctypes.data_as(_ip) if status is not None else None,
-                             nfev.ctypes.data_as(_ip) if nfev is not None else None,
-                             init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
-                             _affine_array(affine, L), ctypes.byref(opt))
+    common = (angles.ctypes.data_as(_dp), fk.ctypes.data_as(_dp) if fk is not None else None,
+              status.ctypes.data_as(_ip) if status is not None else None,
+              nfev.ctypes.data_as(_ip) if nfev is not None else None,
+              init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
+              _affine_array(affine, L), ctypes.byref(opt))
+    if skip:
+        n_valid = np.zeros((S, L), dtype=np.int32)
+        rc = lib.seqik_solve_seq_gaps(pose.ctypes.data_as(_dp), S, L, N, arr, first_stage, last_stage, *common,
+                                      n_valid.ctypes.data_as(_ip))
+    else:
+        rc = lib.seqik_solve_seq(pose.ctypes.data_as(_dp), S, L, N, arr, first_stage, last_stage, *common)
     if rc != SEQIK_OK:
         _raise(rc)
-    return dict(angles=angles, fk=fk, status=status, nfev=nfev, chunk_stats=chunk_stats_dict(stats), chunk_flags=flags)
+    out = dict(angles=angles, fk=fk, status=status, nfev=nfev, chunk_stats=chunk_stats_dict(stats), chunk_flags=flags)
+    if skip:
+        out["n_valid"] = n_valid
+    return out
 
 
 def solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk=0, d_status=0, d_nfev=0,

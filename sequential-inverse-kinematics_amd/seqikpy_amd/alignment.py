@@ -49,8 +49,16 @@ def convert_from_df3dpp_to_dict(pose_3d: Dict[str, Dict[str, np.ndarray]],
     return {segment: dict_to_nparray_pose(pose_3d[segment], claw_is_end_effector=True) for segment in segments}
 
 
-def _mean_quantile(vector: np.ndarray, quantile_diff: float = 0.05) -> float:
-    """Mean of the 0.45 and 0.55 quantiles (reference ``_get_mean_quantile``, alignment.py:83-87)."""
+def _mean_quantile(vector: np.ndarray, quantile_diff: float = 0.05, skip_missing: bool = False) -> float:
+    """Mean of the 0.45 and 0.55 quantiles (reference ``_get_mean_quantile``, alignment.py:83-87).  ``skip_missing``:
+    the non-finite values of the series are left out (``np.nanquantile`` with the same "linear" method); a series
+    without any finite value gives NaN, as ``np.nanquantile`` does (a leg that was never triangulated: all its aligned
+    frames are then missing)."""
+    if skip_missing:
+        vector = np.asarray(vector)
+        vector = vector[np.isfinite(vector)]
+        if vector.size == 0:
+            return np.nan
     return 0.5 * (np.quantile(vector, q=0.5 - quantile_diff) + np.quantile(vector, q=0.5 + quantile_diff))
 
 
@@ -81,12 +89,19 @@ class AlignPose:
 
     Parameters mirror the reference: ``pose_data_dict`` (``"<leg>_leg" -> (N, 5, 3)``), ``legs_list``,
     ``include_claw``, ``body_template``, ``body_size``, ``log_level``.
+    ``missing_key_points``: ``"raise"`` (default, the reference's statistics: a NaN anywhere in a series makes that
+    constant NaN) or ``"skip"``: the whole-recording statistics (fixed coxa, mean segment lengths) leave the non-finite
+    values of each series out.  Aligned frames with a missing key point stay non-finite either way, so that
+    ``LegInvKinSeq.run_ik_and_fk(missing_key_points="skip")`` finds them (row 0 is replaced by the template's coxa).
     """
 
     def __init__(self, pose_data_dict: Dict[str, np.ndarray], legs_list: List[str],
                  include_claw: Optional[bool] = False, body_template: Optional[Dict[str, np.ndarray]] = None,
                  body_size: Optional[Dict[str, float]] = None,
-                 log_level: Literal["DEBUG", "INFO", "WARNING", "ERROR"] = "INFO") -> None:
+                 log_level: Literal["DEBUG", "INFO", "WARNING", "ERROR"] = "INFO",
+                 missing_key_points: Literal["raise", "skip"] = "raise") -> None:
+        from ._lib import check_missing_mode
+        self.skip_missing = check_missing_mode(missing_key_points)
         self.pose_data_dict = pose_data_dict
         self.include_claw = include_claw
         self.body_template = NMF_TEMPLATE if body_template is None else body_template
@@ -110,15 +125,15 @@ class AlignPose:
 
     # -- statistics (host) ---------------------------------------------------------------
     @staticmethod
-    def get_fixed_pos(points_3d: np.ndarray) -> np.ndarray:
+    def get_fixed_pos(points_3d: np.ndarray, skip_missing: bool = False) -> np.ndarray:
         """Per-axis mean of the 0.45 / 0.55 quantiles of a key point over the recording."""
-        return np.array([_mean_quantile(points_3d[:, 0]), _mean_quantile(points_3d[:, 1]),
-                         _mean_quantile(points_3d[:, 2])])
+        return np.array([_mean_quantile(points_3d[:, a], skip_missing=skip_missing) for a in range(3)])
 
     def get_mean_length(self, segment_array: np.ndarray, segment_is_leg: bool = True) -> Dict[str, float]:
         lengths = np.linalg.norm(np.diff(segment_array, axis=1), axis=2)
         names = ["coxa", "femur", "tibia", "tarsus"] if segment_is_leg else ["antenna"]
-        return {name: _mean_quantile(lengths[:, i]) for i, name in enumerate(names)}
+        return {name: _mean_quantile(lengths[:, i], skip_missing=getattr(self, "skip_missing", False))
+                for i, name in enumerate(names)}
 
     def find_scale_leg(self, leg_name: str, mean_length: Dict[str, float]) -> float:
         model = self.body_size[leg_name] if self.include_claw else (
@@ -129,7 +144,7 @@ class AlignPose:
 
     def leg_affine(self, leg_array: np.ndarray, leg_name: str) -> Tuple[np.ndarray, float, np.ndarray]:
         """``(fixed_coxa, scale, template_coxa)`` of one leg -- the constants of ``align_leg``."""
-        fixed_coxa = AlignPose.get_fixed_pos(leg_array[:, 0, :])
+        fixed_coxa = AlignPose.get_fixed_pos(leg_array[:, 0, :], getattr(self, "skip_missing", False))
         scale = self.find_scale_leg(leg_name, self.get_mean_length(leg_array, segment_is_leg=True))
         self.logger.info("Scale factor for %s leg: %s", leg_name, scale)
         return fixed_coxa, float(scale), np.asarray(self.body_template[f"{leg_name}_Coxa"], dtype=np.float64)

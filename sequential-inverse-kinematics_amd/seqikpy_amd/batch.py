@@ -23,7 +23,7 @@ def run_ik_and_fk_many(recordings: Sequence[Dict[str, np.ndarray]], kinematic_ch
                        initial_angles: Optional[Dict[str, Dict[str, np.ndarray]]] = None,
                        pad_to_multiple: int = 0, device: int = -1,
                        leg_affine: Optional[Dict[str, tuple]] = None, frame_parallel=None,
-                       reports: Optional[list] = None
+                       reports: Optional[list] = None, missing_key_points: str = "raise"
                        ) -> List[Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]]:
     """``LegInvKinSeq(rec, kinematic_chain_class, initial_angles).run_ik_and_fk(frame_parallel=...)`` for every ``rec``.
 
@@ -31,13 +31,15 @@ def run_ik_and_fk_many(recordings: Sequence[Dict[str, np.ndarray]], kinematic_ch
     also the faster choice once a call carries enough recordings to fill the GPU by itself -- some 40 000 chains: the chunks'
     run-in frames are extra work).  With ``"auto"`` the chunk geometry depends on a recording's length only, so every recording gets the bits it would get alone (with
     ``pad_to_multiple`` it is the PADDED length that counts).  ``reports``: a list that receives one
-    ``frame_chunk_report`` dict per recording.
+    ``frame_chunk_report`` dict per recording.  ``missing_key_points``: ``"raise"`` (default) or ``"skip"``, as for
+    ``LegInvKinSeq.run_ik_and_fk``: frames with a non-finite key point come back as NaN angles and NaN FK rows.
 
     recordings: dicts ``"<leg>_leg" -> (N_i, 5, 3)`` holding the same leg keys (other keys are ignored);
     all legs of one recording must have the same number of frames.  ``pad_to_multiple`` > 0 rounds the
     lengths up to that multiple so that recordings of similar length share a launch.
     Returns a list of ``(joint_angles_dict, forward_kinematics_dict)`` in input order."""
     from .leg_inverse_kinematics import chunk_report, default_frame_parallel
+    skip = _lib.check_missing_mode(missing_key_points)
     if initial_angles is None:
         initial_angles = INITIAL_ANGLES
     if frame_parallel is None:
@@ -46,7 +48,7 @@ def run_ik_and_fk_many(recordings: Sequence[Dict[str, np.ndarray]], kinematic_ch
     if frame_parallel:
         fp = frame_parallel if isinstance(frame_parallel, dict) else {}
         chunk_opts = dict(frame_chunk=int(fp.get("chunk", -1)), frame_halo=int(fp.get("halo", 0)),
-                          chunk_tol=float(fp.get("tol", 0.0)), chunk_rounds=int(fp.get("rounds", 0)), want_chunk_flags=True)
+                          chunk_tol=float(fp.get("tol", 0.0)), chunk_rounds=int(fp.get("rounds", 0)), want_chunk_flags=not skip)
     kc = kinematic_chain_class
     if not recordings:
         return []
@@ -74,7 +76,8 @@ def run_ik_and_fk_many(recordings: Sequence[Dict[str, np.ndarray]], kinematic_ch
                 a = np.asarray(recordings[i][name], dtype=np.float64)[:, :5, :]
                 pose[s, li, :lengths[i]] = a
                 pose[s, li, lengths[i]:] = a[-1] if lengths[i] else 0.0
-        out = _lib.solve_seq(pose, legs, want_fk=True, device=device, affine=affine, **chunk_opts) if n_pad else None
+        out = _lib.solve_seq(pose, legs, want_fk=True, device=device, affine=affine, missing=missing_key_points,
+                             **chunk_opts) if n_pad else None
         reps = chunk_report(out, [leg for _, leg in segs], n_pad) if n_pad else [{} for _ in idx]
         for s, i in enumerate(idx):
             n = lengths[i]

@@ -430,6 +430,14 @@ class LegInvKinSeq(LegInvKinBase):
         * a dict with any of ``chunk``, ``halo``, ``tol``, ``rounds``: explicit chunk parameters; an explicit ``chunk`` > 0
           runs WITHOUT the guard (the guard belongs to the automatic geometry, ``SeqikOptions.frame_chunk = -1``).
 
+        ``missing_key_points``: ``"raise"`` (default) refuses a recording with a non-finite key point (``ValueError``, as
+        scipy does in the reference); ``"skip"`` solves every leg as if its frames with a non-finite key point (rows 0-4,
+        rows 1-4 with ``leg_affine``) were not in the recording -- frame t warm-started from the last complete frame
+        before it (include/seqik_gaps.h).  Those frames get NaN angles and NaN FK rows (``run_fk`` / ``fit_error`` on the
+        returned angles give NaN rows there too), status ``_lib.STATUS_MISSING`` and nfev 0 with ``diagnostics``;
+        ``self.missing_frames[leg]`` holds the (N,) bool mask.  Skip mode needs ``stages=[1, 2, 3, 4]`` and works with
+        every ``frame_parallel`` setting.
+
         After a chunked run ``self.frame_chunk_stats`` holds the statistics of the last launch and
         ``self.frame_chunk_report[leg]`` says where the recording was hard: ``frames_per_chunk``, ``run_in_frames``,
         ``failed_first_check`` (first frames of the chunks whose run-in did not reproduce the true state -- chaotic
@@ -437,6 +445,9 @@ class LegInvKinSeq(LegInvKinBase):
         Returns ``(joint_angles_dict, forward_kinematics_dict)``."""
         stages = list(kwargs.get("stages", [1, 2, 3, 4]))
         diagnostics = bool(kwargs.get("diagnostics", False))
+        skip = _lib.check_missing_mode(kwargs.get("missing_key_points", "raise"))
+        if skip and stages != [1, 2, 3, 4]:
+            raise ValueError("missing_key_points='skip' needs stages=[1, 2, 3, 4]")
         frame_parallel = kwargs.get("frame_parallel", default_frame_parallel())
         chunk_opts = dict(frame_chunk=0)
         if frame_parallel is not False and frame_parallel is not None:
@@ -454,6 +465,7 @@ class LegInvKinSeq(LegInvKinBase):
         first_stage, last_stage = stages[0], stages[-1]
         forward_kinematics_dict = {}
         self.frame_chunk_stats, self.frame_chunk_report = {}, {}   # describe THIS run only (empty after a serial walk)
+        self.missing_frames = {}
         self.logger.info("Computing joint angles and forward kinematics...")
 
         segments = self._leg_segments()
@@ -470,7 +482,12 @@ class LegInvKinSeq(LegInvKinBase):
                 affine = [_lib.make_affine(*self.leg_affine[leg_name]) for _, leg_name, _ in items]
             out = _lib.solve_seq(pose, legs, first_stage, last_stage, angles=prior, want_fk=True,
                                  want_diag=diagnostics, device=self.device, affine=affine,
-                                 want_chunk_flags=chunk_opts["frame_chunk"] != 0, **chunk_opts)
+                                 want_chunk_flags=chunk_opts["frame_chunk"] != 0 and not skip,
+                                 missing="skip" if skip else "raise", **chunk_opts)
+            if skip:
+                rows = pose[0][:, :, 1:] if affine is not None else pose[0]
+                for li, (_, leg_name, _) in enumerate(items):
+                    self.missing_frames[leg_name] = ~np.isfinite(rows[li]).all(axis=(1, 2))
             self.frame_chunk_stats = out["chunk_stats"]
             self.frame_chunk_report.update(chunk_report(out, [leg_name for _, leg_name, _ in items], n_frames)[0])
             if out["chunk_stats"].get("chunks"):
@@ -553,7 +570,13 @@ class LegInvKinGeneric(LegInvKinBase):
 
     def run_ik_and_fk(self, export_path: Union[Path, str] = None, **kwargs
                       ) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
-        """Inverse and forward kinematics of every leg with the generic chain."""
+        """Inverse and forward kinematics of every leg with the generic chain.
+
+        ``missing_key_points``: ``"raise"`` (default) or ``"skip"``, as for ``LegInvKinSeq.run_ik_and_fk``; here a frame is
+        missing when its origin (key point 0) or its claw (the last key point) holds a non-finite coordinate.
+        ``self.missing_frames[leg]`` holds the (N,) bool mask after a run."""
+        skip = _lib.check_missing_mode(kwargs.get("missing_key_points", "raise"))
+        self.missing_frames = {}
         forward_kinematics_dict = {}
         self.logger.info("Computing joint angles and forward kinematics...")
         segments = self._leg_segments()
@@ -565,7 +588,10 @@ class LegInvKinGeneric(LegInvKinBase):
             # the claw (last key point) is the end effector (:587)
             pose = np.stack([np.asarray(arr, dtype=np.float64)[:, [0, 1, 2, 3, -1], :] if np.asarray(arr).shape[1] >= 5
                              else np.asarray(arr, dtype=np.float64) for _, _, arr in items])[None]
-            out = _lib.solve_generic(pose, legs, device=self.device)
+            out = _lib.solve_generic(pose, legs, device=self.device, missing="skip" if skip else "raise")
+            if skip:
+                for li, (_, leg_name, _) in enumerate(items):
+                    self.missing_frames[leg_name] = ~np.isfinite(pose[0, li][:, [0, 4]]).all(axis=(1, 2))
             for li, (segment_name, leg_name, _) in enumerate(items):
                 self._store(leg_name, out["angles"][0, li])
                 forward_kinematics_dict[segment_name] = out["fk"][0, li].copy()

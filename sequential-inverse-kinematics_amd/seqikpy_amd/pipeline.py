@@ -20,12 +20,19 @@ from .kinematic_chain import KinematicChainSeq
 
 def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: KinematicChainSeq,
                 body_template: Dict[str, np.ndarray], initial_angles: Optional[Dict] = None, device: int = -1,
-                frame_parallel=None, stats: Optional[dict] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+                frame_parallel=None, stats: Optional[dict] = None,
+                missing_key_points: str = "raise") -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
     """Returns ``(body_joint_angles, forward_kinematics)``: the 7 head / antenna angles (when ``R_head``, ``L_head``
     and ``Neck`` are present) + 7 angles per leg, and the ``"<leg>_leg" -> (N, 9, 3)`` joint positions.
     ``frame_parallel``: as ``LegInvKinSeq.run_ik_and_fk`` -- None / ``"auto"`` (default: verified frame chunks; the same
     device-side per-leg guard as every other entry point) or ``False`` (the reference's serial walk).  ``stats``: a dict
-    that receives the chunk statistics of the launch."""
+    that receives the chunk statistics of the launch.
+    ``missing_key_points``: ``"raise"`` (default: a non-finite leg key point raises ``ValueError``, as scipy does in the
+    reference) or ``"skip"``: every leg is solved as ``LegInvKinSeq.run_ik_and_fk(missing_key_points="skip")`` solves it
+    -- frames with a non-finite key point are left out of the warm-start chain and come back as NaN angles and NaN FK
+    rows (compact -> solve -> expand on the leg stream, ``_lib.solve_seq_gaps_device``).  It applies to the legs only:
+    the head and antenna angles keep their behaviour in either mode (they are computed per frame, and a non-finite head
+    key point gives non-finite angles for that frame)."""
     import torch
     from .leg_inverse_kinematics import default_frame_parallel
     if frame_parallel is None:
@@ -39,7 +46,9 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
         raise ValueError("no leg of aligned_pos is covered by the kinematic chain's body_size")
     legs = [_lib.make_leg_params(leg, kc.bounds_dof, kc.body_size, initial_angles) for _, leg in segs]
     pose = np.stack([np.asarray(aligned_pos[name], dtype=np.float64)[:, :5, :] for name, _ in segs])[None]
-    _lib._check_finite(pose)
+    skip = _lib.check_missing_mode(missing_key_points)
+    if not skip:
+        _lib._check_finite(pose)
     n = pose.shape[2]
     with_head = all(k in aligned_pos for k in ("R_head", "L_head", "Neck"))
     lib = _lib.load()
@@ -53,9 +62,19 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
         d_stats = torch.zeros(_lib.N_CHUNK_STATS, dtype=torch.int32, device="cuda")
         cur = torch.cuda.current_stream()
         leg_stream.wait_stream(cur)
-        _lib.solve_seq_device(d_pose.data_ptr(), 1, len(segs), n, legs, d_ang.data_ptr(), d_fk.data_ptr(),
-                              stream=leg_stream.cuda_stream, frame_chunk=-1 if frame_parallel else 0,
-                              d_chunk_stats=d_stats.data_ptr())
+        if skip:
+            L = len(segs)
+            f64 = dict(dtype=torch.float64, device="cuda")
+            gaps = dict(d_cpose=torch.empty_like(d_pose), d_map=torch.empty((1, L, n), dtype=torch.int32, device="cuda"),
+                        d_n_valid=torch.empty((1, L), dtype=torch.int32, device="cuda"),
+                        d_cangles=torch.empty((1, L, n, 7), **f64), d_cfk=torch.empty((1, L, n, 9, 3), **f64))
+            _lib.solve_seq_gaps_device(d_pose, 1, L, n, legs, d_ang, d_fk=d_fk, stream=leg_stream,
+                                       frame_chunk=-1 if frame_parallel else 0, d_chunk_stats=d_stats.data_ptr(),
+                                       **gaps)
+        else:
+            _lib.solve_seq_device(d_pose.data_ptr(), 1, len(segs), n, legs, d_ang.data_ptr(), d_fk.data_ptr(),
+                                  stream=leg_stream.cuda_stream, frame_chunk=-1 if frame_parallel else 0,
+                                  d_chunk_stats=d_stats.data_ptr())
         if with_head:
             hk = HeadInverseKinematics(aligned_pos, body_template, log_level="ERROR")
             r = np.ascontiguousarray(aligned_pos["R_head"], dtype=np.float64)
