@@ -23,10 +23,11 @@ _IN_TREE = not os.path.isfile(os.path.join(_NATIVE, "libseqik_hip.so")) and os.p
 _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 SOURCES = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
-           "seqik_gaps.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp",
-           "seqik_device_scope.hpp", "seqik_hostctx.hpp", "seqik_fk.hpp", "seqik_gaps.hpp"]
+           "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
+           "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_hostctx.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
+           "seqik_resample.hpp"]
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
-                 "seqik_gaps.hip"]
+                 "seqik_gaps.hip", "seqik_resample.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -368,6 +369,18 @@ def load():
         L.seqik_solve_generic_gaps.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
                                                ctypes.POINTER(SeqikLegParams), _dp, _dp, _ip, _ip, _dp,
                                                ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikOptions), _ip]
+        L.seqik_resample_count.restype = ctypes.c_int64
+        L.seqik_resample_count.argtypes = [ctypes.c_int64, ctypes.c_double, ctypes.c_double]
+        L.seqik_resample_workspace_bytes.restype = ctypes.c_size_t
+        L.seqik_resample_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
+        L.seqik_resample_pchip.restype = ctypes.c_int
+        L.seqik_resample_pchip.argtypes = [_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int64,
+                                           ctypes.c_int32]
+        L.seqik_resample_pchip_device.restype = ctypes.c_int
+        L.seqik_resample_pchip_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                  _vp, _vp]
         _lib = L
         return _lib
 
@@ -561,6 +574,88 @@ def solve_seq_gaps_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_cpo
                      affine=affine, d_init=c_ptrs[5], **solve_options)
     gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cfk, d_fk, d_cstatus, d_status, d_cnfev,
                        d_nfev, kind="seq", stream=s)
+
+
+#: entry points of include/seqik_resample.h (PCHIP resampling of joint angles), kept apart from the ABI-7 set of seqik.h
+RESAMPLE_EXPORTED_SYMBOLS = ["seqik_resample_count", "seqik_resample_workspace_bytes", "seqik_resample_pchip",
+                             "seqik_resample_pchip_device"]
+RESAMPLE_BRIDGE = 1
+RESAMPLE_MODES = ("error", "bridge")
+RESAMPLE_MAX_WIDTH = 16
+
+
+def resample_count(n_frames, original_ts, new_ts) -> int:
+    """``seqik_resample_count``: samples per chain, ``len(np.arange(0, n_frames * original_ts, new_ts))``.  No GPU
+    needed.  ``ValueError`` for fewer than 2 frames or time steps that are not finite and positive."""
+    n = load().seqik_resample_count(int(n_frames), float(original_ts), float(new_ts))
+    if n < 0:
+        _raise(int(n))
+    return int(n)
+
+
+def _resample_flags(missing, max_gap):
+    if missing not in RESAMPLE_MODES:
+        raise ValueError(f"missing: expected one of {RESAMPLE_MODES}, got {missing!r}")
+    if max_gap is not None and missing != "bridge":
+        raise ValueError("max_gap needs missing='bridge'")
+    if max_gap is not None and (int(max_gap) != max_gap or max_gap < 0 or max_gap > 2**31 - 1):
+        raise ValueError(f"max_gap must be None (unlimited) or an integer in 0 .. 2^31 - 1, got {max_gap!r}")
+    return (RESAMPLE_BRIDGE if missing == "bridge" else 0), (-1 if max_gap is None else int(max_gap))
+
+
+def resample_pchip(y, original_ts, new_ts, missing="error", max_gap=None, device=-1):
+    """``seqik_resample_pchip`` on a host array: records ``(..., N, W)`` float64 (W in 1..16) at time step
+    ``original_ts`` -> ``(..., n_out, W)`` at ``new_ts`` with scipy's PCHIP (``pchip_interpolate``), every leading index a
+    chain of its own.  Knot j sits at ``j * original_ts``, sample i at ``i * new_ts``, ``n_out = resample_count(...)``;
+    the samples behind the last knot continue the last cubic, as scipy does.
+
+    ``missing``: ``"error"`` (default) refuses non-finite input with ``ValueError``, as scipy does; ``"bridge"`` treats a
+    record with a non-finite value as a missing knot and resamples every chain over its valid knots alone
+    (``pchip_interpolate(x[valid], y[valid], u)``): NaN in front of the first valid knot, from one ``original_ts`` behind
+    the last one, and throughout a chain with fewer than two valid knots.  ``max_gap`` (bridge mode): samples strictly
+    inside an interval that spans more than ``max_gap`` missing knots stay NaN; None = no limit."""
+    flags, gap = _resample_flags(missing, max_gap)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim < 2:
+        raise ValueError(f"y must have shape (..., N, W), got {y.shape}")
+    N, W = y.shape[-2:]
+    if not 1 <= W <= RESAMPLE_MAX_WIDTH:
+        raise ValueError(f"the record width must lie in 1..{RESAMPLE_MAX_WIDTH}, got {W}")
+    if N < 2:
+        raise ValueError("The number of knots must be at least 2 (scipy: `x` must contain at least 2 elements)")
+    if not flags and not np.isfinite(y).all():
+        raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
+    n_out = resample_count(N, original_ts, new_ts)
+    C = int(np.prod(y.shape[:-2], dtype=np.int64))
+    out = np.full(y.shape[:-2] + (n_out, W), np.nan)
+    rc = load().seqik_resample_pchip(y.ctypes.data_as(_dp), C, N, W, float(original_ts), float(new_ts), flags, gap,
+                                     out.ctypes.data_as(_dp), n_out, int(device))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    return out
+
+
+def resample_workspace_bytes(n_chains, n_frames, missing="error") -> int:
+    """``seqik_resample_workspace_bytes``: size of the workspace ``resample_pchip_device`` needs (8 B per knot in bridge
+    mode, else 0)."""
+    return int(load().seqik_resample_workspace_bytes(int(n_chains), int(n_frames), _resample_flags(missing, None)[0]))
+
+
+def resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d_out, missing="error", max_gap=None,
+                          d_workspace=0, stream=0):
+    """``seqik_resample_pchip_device``: ``d_y`` (C, N, W) -> ``d_out`` (C, n_out, W) float64, raw device pointers (ints) or
+    torch tensors, asynchronous on ``stream`` (a hipStream_t as int, or a torch stream).  Nothing is checked per frame:
+    in the default mode a non-finite knot makes the samples whose stencil touches it NaN.  ``d_workspace`` (bridge mode):
+    ``resample_workspace_bytes`` bytes; as a tensor, int32 of ``2 * C * N`` elements (prev, then next).  Returns n_out."""
+    flags, gap = _resample_flags(missing, max_gap)
+    n_out = resample_count(n_frames, original_ts, new_ts)
+    ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
+    rc = load().seqik_resample_pchip_device(_ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
+                                            int(width), float(original_ts), float(new_ts), flags, gap,
+                                            _ptr(d_out, "out", (n_chains, n_out, width)), n_out, ws, _stream_ptr(stream))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    return n_out
 
 
 class AlignStats:

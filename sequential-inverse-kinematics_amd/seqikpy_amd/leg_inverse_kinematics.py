@@ -271,6 +271,93 @@ class LegInvKinBase(ABC):
                 out[segment_name] = d[0, li].copy()
         return {name: out[name] for name, _, _ in self._leg_segments()}
 
+    # -- resampling of the joint angles (include/seqik_resample.h) --------------------------
+    def run_resample(self, original_ts, new_ts, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                     missing: str = "error", max_gap: Optional[int] = None, with_fk: bool = False,
+                     origin: Optional[np.ndarray] = None, export_path: Union[Path, str] = None):
+        """The legs' joint angles resampled from time step ``original_ts`` to ``new_ts`` on the GPU with the reference's
+        interpolant (``utils.interpolate_joint_angles``: scipy's PCHIP; ``seqik_resample_pchip``).
+
+        The angles (``joint_angles``, default: the last run's ``self.joint_angles_dict``) go as ``(L, N, 7)`` records in
+        one call per frame count, so with ``missing="bridge"`` a leg-frame is bridged as a whole: the NaN frames that
+        ``missing_key_points="skip"`` leaves are filled from the solved frames around them (``max_gap``: the longest run
+        of missing frames that is filled; None: any).  ``missing="error"`` refuses non-finite angles as scipy does.
+        Returns the resampled ``{"Angle_<leg>_<dof>": (n_out,)}`` dictionary (entries of other legs are not touched and
+        not returned).
+
+        ``with_fk=True`` also computes the forward kinematics of the resampled angles, from the device buffer the
+        resampling wrote (``seqik_forward_kinematics_device``, no host round trip), and returns ``(angles,
+        {segment_name: (n_out, 9, 3)})``.  ``origin``: one ``(3,)`` point per call, used for every leg; default: each
+        leg's key point 0 as in ``run_fk`` when it is the same in every frame that has one, else ``ValueError`` (a moving
+        origin cannot be resampled here).  ``export_path``: writes ``leg_joint_angles_resampled.pkl`` (and
+        ``forward_kinematics_resampled.pkl``) there."""
+        ja = self.joint_angles_dict if joint_angles is None else joint_angles
+        groups = {}
+        for segment_name, leg_name, arr in self._leg_segments():
+            ang = self._fk_angles(ja, leg_name)
+            groups.setdefault(ang.shape[0], []).append((segment_name, leg_name, arr, ang))
+        angles_out, fk_out = {}, {}
+        for n, items in groups.items():
+            y = np.stack([a for *_, a in items])
+            if not with_fk:
+                res = _lib.resample_pchip(y, original_ts, new_ts, missing=missing, max_gap=max_gap, device=self.device)
+                fk = None
+            else:
+                origins = np.stack([self._resample_origin(origin, segment_name, leg_name, arr)
+                                    for segment_name, leg_name, arr, _ in items])
+                legs = [self._fk_leg_params(leg_name) for _, leg_name, _, _ in items]
+                res, fk = self._resample_with_fk(y, original_ts, new_ts, missing, max_gap, legs, origins)
+            for li, (segment_name, leg_name, _, _) in enumerate(items):
+                for di, dof in enumerate(DOFS):
+                    angles_out[f"Angle_{leg_name}_{dof}"] = res[li, :, di].copy()
+                if fk is not None:
+                    fk_out[segment_name] = fk[li].copy()
+        if export_path is not None:
+            save_file(Path(export_path) / "leg_joint_angles_resampled.pkl", angles_out)
+            if with_fk:
+                save_file(Path(export_path) / "forward_kinematics_resampled.pkl", fk_out)
+        if not with_fk:
+            return angles_out
+        return angles_out, {name: fk_out[name] for name, _, _ in self._leg_segments()}
+
+    def _resample_origin(self, origin, segment_name, leg_name, segment_array):
+        if origin is not None:
+            o = np.asarray(origin, dtype=np.float64)
+            if o.shape != (3,):
+                raise ValueError(f"origin must have shape (3,), got {o.shape}")
+            return o
+        kp0 = self._fk_key_points(leg_name, segment_array)[:, 0]
+        rows = kp0[np.isfinite(kp0).all(axis=1)]
+        if rows.shape[0] == 0 or not (rows == rows[0]).all():
+            raise ValueError(f"{segment_name}: key point 0 is not the same in every frame; pass origin=(3,)")
+        return rows[0].copy()
+
+    def _resample_with_fk(self, y, original_ts, new_ts, missing, max_gap, legs, origins):
+        """(L, N, 7) host angles -> resampled (L, n_out, 7) and FK (L, n_out, 9, 3), both computed on device buffers."""
+        import torch
+        flags, _ = _lib._resample_flags(missing, max_gap)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        L, N = y.shape[:2]
+        if N < 2:
+            raise ValueError("The number of knots must be at least 2")
+        if not flags and not np.isfinite(y).all():
+            raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
+        n_out = _lib.resample_count(N, original_ts, new_ts)
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device < 0 else self.device)
+        with torch.cuda.device(dev):
+            d_y = torch.from_numpy(y).to(dev)
+            d_out = torch.empty((L, n_out, 7), dtype=torch.float64, device=dev)
+            d_ws = torch.empty((2, L, N), dtype=torch.int32, device=dev) if flags else 0
+            d_org = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(origins[:, None, :], (L, n_out, 3)))).to(dev)
+            d_fk = torch.empty((L, n_out, 9, 3), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.resample_pchip_device(d_y, L, N, 7, original_ts, new_ts, d_out, missing=missing, max_gap=max_gap,
+                                       d_workspace=d_ws, stream=stream)
+            _lib.forward_kinematics_device(d_out.data_ptr(), 1, L, n_out, legs, d_fk.data_ptr(), kind=self._fk_kind,
+                                           d_origin=d_org.data_ptr(), stream=stream)
+            torch.cuda.synchronize(dev)
+            return d_out.cpu().numpy(), d_fk.cpu().numpy()
+
     def _export(self, export_path, forward_kinematics_dict):
         if export_path is not None:
             save_file(Path(export_path) / "forward_kinematics.pkl", forward_kinematics_dict)

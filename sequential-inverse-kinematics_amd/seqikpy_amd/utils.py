@@ -73,10 +73,36 @@ def dict_to_nparray_angle(angle_dict, leg, claw_is_end_effector):
     return np.stack([np.asarray(angle_dict[f"{leg}_leg"][d], dtype=np.float64) for d in dofs], axis=1)
 
 
-def interpolate_signal(signal, original_ts, new_ts):
+def _reference_grid_check(n_frames, original_ts):
+    """The reference builds its knots with ``np.arange(0, N * original_ts, original_ts)``; rounding can make that grid one
+    element longer than the series (3 frames at 0.1 s, 1000 at 1/30 s), and scipy then refuses the pair."""
+    n_knots = len(np.arange(0, n_frames * original_ts, original_ts))
+    if n_knots != n_frames:
+        raise ValueError(f"x and y arrays must be equal in length along interpolation axis: np.arange(0, "
+                         f"{n_frames} * {original_ts!r}, {original_ts!r}) holds {n_knots} knots for {n_frames} samples")
+
+
+def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error", max_gap=None):
     """Resamples one series from time step ``original_ts`` to ``new_ts`` with a shape-preserving cubic (PCHIP) over
     ``[0, N * original_ts)`` (``seqikpy/utils.py:332-349``).  As there: if the interpolation fails, infinities and the
-    last sample are zeroed IN the caller's array and it is tried once more."""
+    last sample are zeroed IN the caller's array and it is tried once more.
+
+    ``on_gpu=True`` runs the same interpolant on the GPU (``_lib.resample_pchip``, include/seqik_resample.h) and never
+    modifies ``signal``: where the reference raises (non-finite values, fewer than 2 samples, a knot grid that
+    ``np.arange`` makes longer than the series) it raises ``ValueError`` before anything is launched.
+    ``missing="bridge"`` (GPU only) resamples over the finite samples alone and so fills the NaN frames of
+    ``missing_key_points="skip"``; ``max_gap``: longest run of missing frames that is filled (None: any)."""
+    if on_gpu:
+        from . import _lib
+        y = np.asarray(signal, dtype=np.float64)
+        if y.ndim != 1:
+            raise ValueError(f"signal must be one series (N,), got shape {y.shape}")
+        if y.shape[0] < 2:
+            raise ValueError("`x` must contain at least 2 elements.")
+        _reference_grid_check(y.shape[0], original_ts)
+        return _lib.resample_pchip(y[:, None], original_ts, new_ts, missing=missing, max_gap=max_gap)[:, 0]
+    if missing != "error" or max_gap is not None:
+        raise ValueError("missing / max_gap need on_gpu=True (the host path is the reference's own)")
     from scipy.interpolate import pchip_interpolate
     total = signal.shape[0] * original_ts
     x_old, x_new = np.arange(0, total, original_ts), np.arange(0, total, new_ts)
@@ -90,5 +116,31 @@ def interpolate_signal(signal, original_ts, new_ts):
 
 def interpolate_joint_angles(joint_angles_dict, **kwargs):
     """``interpolate_signal`` over every series of a joint-angle dictionary (``run_ik_and_fk``'s first result);
-    ``original_ts`` / ``new_ts`` as keyword arguments (``seqikpy/utils.py:352-360``)."""
-    return {dof: interpolate_signal(signal=series, **kwargs) for dof, series in joint_angles_dict.items()}
+    ``original_ts`` / ``new_ts`` as keyword arguments (``seqikpy/utils.py:352-360``).  With ``on_gpu=True`` ALL series go
+    to the GPU in one call per series length (each series a chain of width 1) and the reference's dictionary comes
+    back; ``missing`` / ``max_gap`` as for ``interpolate_signal``."""
+    if not kwargs.get("on_gpu", False):
+        return {dof: interpolate_signal(signal=series, **kwargs) for dof, series in joint_angles_dict.items()}
+    from . import _lib
+    opts = dict(kwargs)
+    opts.pop("on_gpu")
+    original_ts, new_ts = opts.pop("original_ts"), opts.pop("new_ts")
+    missing, max_gap = opts.pop("missing", "error"), opts.pop("max_gap", None)
+    if opts:
+        raise TypeError(f"interpolate_signal() got an unexpected keyword argument {sorted(opts)[0]!r}")
+    groups = {}
+    for dof, series in joint_angles_dict.items():
+        y = np.asarray(series, dtype=np.float64)
+        if y.ndim != 1:
+            raise ValueError(f"{dof}: expected one series (N,), got shape {y.shape}")
+        if y.shape[0] < 2:
+            raise ValueError("`x` must contain at least 2 elements.")
+        _reference_grid_check(y.shape[0], original_ts)
+        groups.setdefault(y.shape[0], []).append((dof, y))
+    out = {}
+    for items in groups.values():
+        res = _lib.resample_pchip(np.stack([y for _, y in items])[:, :, None], original_ts, new_ts, missing=missing,
+                                  max_gap=max_gap)
+        for k, (dof, _) in enumerate(items):
+            out[dof] = res[k, :, 0].copy()
+    return {dof: out[dof] for dof in joint_angles_dict}
