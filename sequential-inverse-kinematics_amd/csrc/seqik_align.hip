@@ -16,30 +16,13 @@
 // not matter.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <stdio.h>
 #include <new>
-#include <vector>
 
-#include "../../include/seqik.h"
-#include "seqik_device_scope.hpp"
-
-extern "C" void seqik_set_error(int code, const char *msg);
+#include "seqik_runtime.hpp"
 
 namespace {
 
-int a_fail(int code, const char *what, const char *detail = "")
-{
-    char buf[384];
-    snprintf(buf, sizeof(buf), "%s%s%s", what, detail[0] ? ": " : "", detail);
-    seqik_set_error(code, buf);
-    return code;
-}
-
-#define ATRY(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) return a_fail(SEQIK_ERR_HIP, #expr, hipGetErrorString(e_)); \
-    } while (0)
+using seqik::bad_arg;
 
 constexpr int kSeries = 7;  // coxa x, y, z; coxa, femur, tibia, tarsus length
 
@@ -100,12 +83,12 @@ extern "C" {
 
 int seqik_align_stats_open(SeqikAlignStats **out, int32_t n_legs, int64_t capacity_frames, const SeqikOptions *opt)
 {
-    if (!out) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_open: null handle pointer");
+    if (!out) return bad_arg("seqik_align_stats_open", "null handle pointer");
     *out = nullptr;
     if (n_legs <= 0 || n_legs > 8 || capacity_frames <= 0)
-        return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_open: bad sizes (n_legs 1..8, capacity_frames > 0)");
+        return bad_arg("seqik_align_stats_open", "bad sizes (n_legs 1..8, capacity_frames > 0)");
     SeqikAlignStats *s = new (std::nothrow) SeqikAlignStats;
-    if (!s) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_open: out of host memory");
+    if (!s) return bad_arg("seqik_align_stats_open", "out of host memory");
     s->n_legs = n_legs;
     s->capacity = capacity_frames;
     seqik::DeviceScope scope;
@@ -115,7 +98,7 @@ int seqik_align_stats_open(SeqikAlignStats **out, int32_t n_legs, int64_t capaci
         e = hipMalloc(reinterpret_cast<void **>(&s->d_series), sizeof(double) * kSeries * n_legs * capacity_frames);
     if (e != hipSuccess) {
         delete s;
-        return a_fail(SEQIK_ERR_HIP, "seqik_align_stats_open", hipGetErrorString(e));
+        return seqik::hip_fail(e, "seqik_align_stats_open");
     }
     *out = s;
     return SEQIK_OK;
@@ -124,29 +107,29 @@ int seqik_align_stats_open(SeqikAlignStats **out, int32_t n_legs, int64_t capaci
 int seqik_align_stats_add(SeqikAlignStats *s, const double *pose, int32_t pose_on_device, int64_t n_seq,
                           int64_t n_frames, const SeqikLayout *layout, void *hip_stream)
 {
-    if (!s || !pose) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_add: null pointer");
-    if (n_seq < 0 || n_frames < 0) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_add: negative size");
+    if (!s || !pose) return bad_arg("seqik_align_stats_add", "null pointer");
+    if (n_seq < 0 || n_frames < 0) return bad_arg("seqik_align_stats_add", "negative size");
     const int64_t add = n_seq * n_frames;
     if (add == 0) return SEQIK_OK;
-    if (s->count + add > s->capacity) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_add: more frames than the capacity");
+    if (s->count + add > s->capacity) return bad_arg("seqik_align_stats_add", "more frames than the capacity");
     seqik::DeviceScope scope;
-    ATRY(scope.enter(s->device));
+    HIP_TRY(scope.enter(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     int64_t pc = n_frames * 15, pr = 3, pf = 15;
     if (layout) {
         if (layout->pose_chain < 0 || layout->pose_row <= 0 || layout->pose_frame <= 0)
-            return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_add: layout strides must be positive");
+            return bad_arg("seqik_align_stats_add", "layout strides must be positive");
         pc = layout->pose_chain; pr = layout->pose_row; pf = layout->pose_frame;
     }
     const double *d_pose = pose;
     if (!pose_on_device) {
         const size_t bytes = sizeof(double) * (size_t)pc * n_seq * s->n_legs;
         if (bytes > s->stage_bytes) {
-            if (s->d_stage) { ATRY(hipStreamSynchronize(stream)); (void)hipFree(s->d_stage); s->d_stage = nullptr; s->stage_bytes = 0; }
-            ATRY(hipMalloc(reinterpret_cast<void **>(&s->d_stage), bytes));
+            if (s->d_stage) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(s->d_stage); s->d_stage = nullptr; s->stage_bytes = 0; }
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_stage), bytes));
             s->stage_bytes = bytes;
         }
-        ATRY(hipMemcpyAsync(s->d_stage, pose, bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(s->d_stage, pose, bytes, hipMemcpyHostToDevice, stream));
         d_pose = s->d_stage;
     }
     const int64_t total = add * s->n_legs;
@@ -154,57 +137,53 @@ int seqik_align_stats_add(SeqikAlignStats *s, const double *pose, int32_t pose_o
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(seqik_align_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_pose, n_seq, s->n_legs,
                        n_frames, pc, pr, pf, s->d_series, s->capacity, s->count);
-    ATRY(hipGetLastError());
-    if (!pose_on_device) ATRY(hipStreamSynchronize(stream));  // the staging buffer / the caller's slab may be reused
+    HIP_TRY(hipGetLastError());
+    if (!pose_on_device) HIP_TRY(hipStreamSynchronize(stream));  // the staging buffer / the caller's slab may be reused
     s->count += add;
     return SEQIK_OK;
 }
 
 int seqik_align_stats_finish(SeqikAlignStats *s, const int64_t *ranks, int32_t n_ranks, double *out, void *hip_stream)
 {
-    if (!s || !ranks || !out) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_finish: null pointer");
-    if (n_ranks <= 0 || n_ranks > 16) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_finish: n_ranks must be 1..16");
-    if (s->count == 0) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_finish: no frames were added");
-    if (s->count > 0x7fffffffLL) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_finish: more than 2^31 frames per leg");
+    if (!s || !ranks || !out) return bad_arg("seqik_align_stats_finish", "null pointer");
+    if (n_ranks <= 0 || n_ranks > 16) return bad_arg("seqik_align_stats_finish", "n_ranks must be 1..16");
+    if (s->count == 0) return bad_arg("seqik_align_stats_finish", "no frames were added");
+    if (s->count > 0x7fffffffLL) return bad_arg("seqik_align_stats_finish", "more than 2^31 frames per leg");
     seqik::DeviceScope scope;
-    ATRY(scope.enter(s->device));
+    HIP_TRY(scope.enter(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int n_series = kSeries * s->n_legs;
     double *d_sorted = nullptr, *d_out = nullptr;
     int64_t *d_ranks = nullptr;
     void *d_tmp = nullptr;
-    int rc = SEQIK_OK;
-    do {
-#define AB(expr) { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = a_fail(SEQIK_ERR_HIP, #expr, hipGetErrorString(e_)); break; } }
-        AB(hipMalloc(reinterpret_cast<void **>(&d_sorted), sizeof(double) * (size_t)n_series * s->capacity));
-        AB(hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(double) * n_series * n_ranks));
-        AB(hipMalloc(reinterpret_cast<void **>(&d_ranks), sizeof(int64_t) * n_ranks));
-        AB(hipMemcpyAsync(d_ranks, ranks, sizeof(int64_t) * n_ranks, hipMemcpyHostToDevice, stream));
+    const int rc = [&]() -> int {  // (the temporaries are freed on every path out)
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_sorted), sizeof(double) * (size_t)n_series * s->capacity));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(double) * n_series * n_ranks));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_ranks), sizeof(int64_t) * n_ranks));
+        HIP_TRY(hipMemcpyAsync(d_ranks, ranks, sizeof(int64_t) * n_ranks, hipMemcpyHostToDevice, stream));
         size_t tmp_bytes = 0;
-        AB(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, s->d_series, d_sorted, (int)s->count, 0, 64, stream));
-        AB(hipMalloc(&d_tmp, tmp_bytes));
-        bool ok = true;
-        for (int i = 0; i < n_series && ok; ++i) {  // one full-width sort per series (a segmented sort would
+        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, s->d_series, d_sorted, (int)s->count, 0, 64, stream));
+        HIP_TRY(hipMalloc(&d_tmp, tmp_bytes));
+        for (int i = 0; i < n_series; ++i) {  // one full-width sort per series (a segmented sort would
             hipError_t e_ = hipcub::DeviceRadixSort::SortKeys(       // put one block on each of these huge segments)
                 d_tmp, tmp_bytes, s->d_series + (int64_t)i * s->capacity, d_sorted + (int64_t)i * s->capacity, (int)s->count,
                 0, 64, stream);
-            if (e_ != hipSuccess) { rc = a_fail(SEQIK_ERR_HIP, "hipcub::DeviceRadixSort::SortKeys", hipGetErrorString(e_)); ok = false; }
+            if (e_ != hipSuccess) return seqik::hip_fail(e_, "hipcub::DeviceRadixSort::SortKeys");
         }
-        if (!ok) break;
         hipLaunchKernelGGL(seqik_align_pick_kernel, dim3((n_series * n_ranks + 63) / 64), dim3(64), 0, stream, d_sorted,
                            s->capacity, s->count, d_ranks, n_ranks, n_series, d_out);
-        AB(hipGetLastError());
-        AB(hipMemcpyAsync(out, d_out, sizeof(double) * n_series * n_ranks, hipMemcpyDeviceToHost, stream));
-        AB(hipStreamSynchronize(stream));
-#undef AB
-    } while (0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_series * n_ranks, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return SEQIK_OK;
+    }();
     (void)hipFree(d_sorted); (void)hipFree(d_out); (void)hipFree(d_ranks); (void)hipFree(d_tmp);
     return rc;
 }
 
 int seqik_align_stats_reset(SeqikAlignStats *s)
 {
-    if (!s) return a_fail(SEQIK_ERR_BAD_ARG, "seqik_align_stats_reset: null handle");
+    if (!s) return bad_arg("seqik_align_stats_reset", "null handle");
     s->count = 0;
     return SEQIK_OK;
 }

@@ -398,6 +398,15 @@ SEQIK_HD double next_toward(double b, double toward)
 
 SEQIK_HD bool is_finite(double x) { return (x - x) == 0.0; }
 
+// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (the hardware completes a wave's LDS
+// operations in order; this is for the compiler)
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---------------------------------------------------------------------------
 // Wave-uniform fast paths.  make_strictly_feasible and the finite-difference step of _numdiff spend most of their
 // instructions on what happens AT or BEYOND a bound (14 compares and 10 selects per strictly_feasible call); a point that

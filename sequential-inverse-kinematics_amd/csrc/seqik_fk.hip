@@ -2,17 +2,17 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "seqik_fk.hpp"
-#include "seqik_device_scope.hpp"
-#include "seqik_hostctx.hpp"
+#include "seqik_runtime.hpp"
 #include "../../include/seqik_fk.h"
 
-extern "C" void seqik_set_error(int code, const char *msg);
-
 namespace {
+
+using seqik::bad_arg;
+using seqik::kFkRow;  // doubles of FK per leg-frame
+using seqik::wave_lds_fence;
 
 struct FkArgs {
     const double *angles;  // [n_total][7]
@@ -27,16 +27,7 @@ struct FkArgs {
     seqik::FkLeg legs[seqik::kFkMaxLegs];
 };
 
-constexpr int kFkRow = 27;           // doubles of FK per leg-frame
 constexpr int kFkWaveLds = 64 * kFkRow;  // doubles of LDS per wavefront (STAGED)
-
-// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (see seqik_head.hip)
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ const double *fk_origin(const FkArgs &a, int64_t i)
 {
@@ -102,21 +93,7 @@ __global__ void __launch_bounds__(1024) seqik_fk_kernel(FkArgs a)
     }
 }
 
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    seqik_set_error(SEQIK_ERR_HIP, buf);
-    return SEQIK_ERR_HIP;
-}
-
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
-
-int bad_arg(const char *msg)
-{
-    seqik_set_error(SEQIK_ERR_BAD_ARG, msg);
-    return SEQIK_ERR_BAD_ARG;
-}
+constexpr const char *kWho = "seqik_forward_kinematics";  // both entry points report under this name
 
 // The checks both entry points make before anything touches HIP; *n_total receives n_seq * n_legs * n_frames.
 int fk_validate(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs,
@@ -124,23 +101,16 @@ int fk_validate(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_f
                 int64_t *n_total)
 {
     if (n_legs < 1 || n_legs > seqik::kFkMaxLegs)
-        return bad_arg("seqik_forward_kinematics: n_legs must lie in 1..8");
-    if (n_seq < 0 || n_frames < 0) return bad_arg("seqik_forward_kinematics: negative n_seq or n_frames");
-    if (!angles || !fk) return bad_arg("seqik_forward_kinematics: angles and fk must not be null");
-    if (!legs) return bad_arg("seqik_forward_kinematics: legs must not be null");
+        return bad_arg(kWho, "n_legs must lie in 1..8");
+    if (n_seq < 0 || n_frames < 0) return bad_arg(kWho, "negative n_seq or n_frames");
+    if (!angles || !fk) return bad_arg(kWho, "angles and fk must not be null");
+    if (!legs) return bad_arg(kWho, "legs must not be null");
     if (kind != SEQIK_FK_KIND_SEQ && kind != SEQIK_FK_KIND_GENERIC)
-        return bad_arg("seqik_forward_kinematics: kind must be 0 (sequential chain) or 1 (generic chain)");
-    if (pose && origin) return bad_arg("seqik_forward_kinematics: pass pose or origin, not both");
-    if (dist && !pose) return bad_arg("seqik_forward_kinematics: dist needs pose (the key points to measure against)");
-    for (int l = 0; l < n_legs; ++l)
-        for (int k = 0; k < 4; ++k)
-            if (!seqik::is_finite(legs[l].seg[k])) return bad_arg("seqik_forward_kinematics: non-finite segment length");
-    // the largest array has 27 doubles per leg-frame: its byte count must fit in 63 bits
-    const int64_t lim = INT64_MAX / (8 * kFkRow);
-    if (n_seq != 0 && n_frames != 0 && (n_seq > lim / n_legs || n_seq * n_legs > lim / n_frames))
-        return bad_arg("seqik_forward_kinematics: too many leg-frames");
-    *n_total = n_seq * n_legs * n_frames;
-    return SEQIK_OK;
+        return bad_arg(kWho, "kind must be 0 (sequential chain) or 1 (generic chain)");
+    if (pose && origin) return bad_arg(kWho, "pass pose or origin, not both");
+    if (dist && !pose) return bad_arg(kWho, "dist needs pose (the key points to measure against)");
+    if (int rc = seqik::check_segments(kWho, legs, n_legs)) return rc;
+    return seqik::leg_frames_fit(kWho, n_seq, n_legs, n_frames, n_total);
 }
 
 }  // namespace
@@ -175,8 +145,7 @@ int seqik_forward_kinematics_device(const double *d_angles, int64_t n_seq, int32
     if (kind == SEQIK_FK_KIND_SEQ) { if (staged) FK_LAUNCH(0, true); else FK_LAUNCH(0, false); }
     else { if (staged) FK_LAUNCH(1, true); else FK_LAUNCH(1, false); }
 #undef FK_LAUNCH
-    HTRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 int seqik_forward_kinematics(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_frames,
@@ -187,34 +156,16 @@ int seqik_forward_kinematics(const double *angles, int64_t n_seq, int32_t n_legs
     int rc = fk_validate(angles, n_seq, n_legs, n_frames, legs, kind, pose, origin, fk, dist, &n);
     if (rc != SEQIK_OK) return rc;
     if (n == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HTRY(scope.enter(device));
-    const size_t b_ang = sizeof(double) * 7 * (size_t)n, b_fk = sizeof(double) * kFkRow * (size_t)n;
-    const size_t b_pose = pose ? sizeof(double) * 15 * (size_t)n : 0, b_org = origin ? sizeof(double) * 3 * (size_t)n : 0;
-    const size_t b_dist = dist ? sizeof(double) * 4 * (size_t)n : 0;
-    seqik::HostLeaseGuard g;
-    rc = seqik::host_lease_acquire(&g.lease);
-    if (rc != SEQIK_OK) return rc;
-    rc = seqik::host_lease_reserve(&g.lease, seqik::arena_padded(b_ang) + seqik::arena_padded(b_fk) +
-                                                 seqik::arena_padded(b_pose) + seqik::arena_padded(b_org) +
-                                                 seqik::arena_padded(b_dist));
-    if (rc != SEQIK_OK) return rc;
-    hipStream_t stream = g.lease.stream;
-    char *p = g.lease.arena;
-    double *d_ang = reinterpret_cast<double *>(p); p += seqik::arena_padded(b_ang);
-    double *d_fk = reinterpret_cast<double *>(p); p += seqik::arena_padded(b_fk);
-    double *d_pose = pose ? reinterpret_cast<double *>(p) : nullptr; p += seqik::arena_padded(b_pose);
-    double *d_org = origin ? reinterpret_cast<double *>(p) : nullptr; p += seqik::arena_padded(b_org);
-    double *d_dist = dist ? reinterpret_cast<double *>(p) : nullptr;
-    HTRY(hipMemcpyAsync(d_ang, angles, b_ang, hipMemcpyHostToDevice, stream));
-    if (d_pose) HTRY(hipMemcpyAsync(d_pose, pose, b_pose, hipMemcpyHostToDevice, stream));
-    if (d_org) HTRY(hipMemcpyAsync(d_org, origin, b_org, hipMemcpyHostToDevice, stream));
-    rc = seqik_forward_kinematics_device(d_ang, n_seq, n_legs, n_frames, legs, kind, d_pose, d_org, d_fk, d_dist, stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    HTRY(hipMemcpyAsync(fk, d_fk, b_fk, hipMemcpyDeviceToHost, stream));
-    if (d_dist) HTRY(hipMemcpyAsync(dist, d_dist, b_dist, hipMemcpyDeviceToHost, stream));
-    HTRY(hipStreamSynchronize(stream));
-    return SEQIK_OK;
+    seqik::HostCall call;
+    double *d_ang, *d_pose, *d_org, *d_fk, *d_dist;
+    call.upload(d_ang, 7 * (size_t)n, angles);
+    call.upload(d_pose, 15 * (size_t)n, pose);
+    call.upload(d_org, 3 * (size_t)n, origin);
+    call.download(d_fk, kFkRow * (size_t)n, fk);
+    call.download(d_dist, 4 * (size_t)n, dist);
+    if ((rc = call.begin(device)) != SEQIK_OK) return rc;
+    return call.finish(seqik_forward_kinematics_device(d_ang, n_seq, n_legs, n_frames, legs, kind, d_pose, d_org, d_fk, d_dist,
+                                                       call.stream()));
 }
 
 }  // extern "C"

@@ -19,25 +19,23 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "seqik_gaps.hpp"
-#include "seqik_device_scope.hpp"
-#include "seqik_hostctx.hpp"
+#include "seqik_runtime.hpp"
 #include "../../include/seqik_gaps.h"
-
-extern "C" void seqik_set_error(int code, const char *msg);
 
 namespace {
 
+using seqik::bad_arg;
+using seqik::kFkRow;
 using seqik::kGapsRec;
+using seqik::kMaxTiles;  // tiles per chain (scan: 16 rows of 64 lanes)
+using seqik::wave_lds_fence;
 
 constexpr int kMaxLegs = 8;
 constexpr int kBlock = 256;            // threads per workgroup: 4 independent wavefronts
 constexpr int kWaves = kBlock / 64;
-constexpr int kMaxTiles = 1024;        // tiles per chain (scan: 16 rows of 64 lanes)
-constexpr int kFkRow = 27;
 
 struct GapsGeom {
     int64_t n_frames;  // N
@@ -56,14 +54,6 @@ struct CompactArgs {
     int32_t *n_valid;
     seqik::GapsLeg legs[kMaxLegs];
 };
-
-// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (see seqik_fk.hip)
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
 
@@ -261,62 +251,16 @@ __global__ void __launch_bounds__(kBlock) seqik_gaps_expand_kernel(ExpandArgs a)
         expand_block<int32_t, SW>(a.cnfev + s0 * SW, a.nfev + i0 * SW, nv, nf, s_rank[wave], sti, (int32_t)0, lane);
 }
 
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    seqik_set_error(SEQIK_ERR_HIP, buf);
-    return SEQIK_ERR_HIP;
-}
-
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
-
-int bad_arg(const char *msg)
-{
-    seqik_set_error(SEQIK_ERR_BAD_ARG, msg);
-    return SEQIK_ERR_BAD_ARG;
-}
-
 // sizes shared by every entry point; *n_total receives n_seq * n_legs * n_frames
 int check_sizes(const char *who, int64_t n_seq, int32_t n_legs, int64_t n_frames, int32_t flags, int64_t *n_total)
 {
-    char buf[160];
-    if (n_legs < 1 || n_legs > kMaxLegs) {
-        snprintf(buf, sizeof(buf), "%s: n_legs must lie in 1..8", who);
-        return bad_arg(buf);
-    }
-    if (n_seq < 0 || n_frames < 0) { snprintf(buf, sizeof(buf), "%s: negative n_seq or n_frames", who); return bad_arg(buf); }
-    if (n_frames > INT32_MAX) {
-        snprintf(buf, sizeof(buf), "%s: n_frames must be below 2^31 (the frame map is int32)", who);
-        return bad_arg(buf);
-    }
-    if (flags & ~(SEQIK_GAPS_GENERIC | SEQIK_GAPS_AFFINE)) {
-        snprintf(buf, sizeof(buf), "%s: unknown flags (SEQIK_GAPS_SEQ / _GENERIC, | SEQIK_GAPS_AFFINE)", who);
-        return bad_arg(buf);
-    }
-    // the largest array has 27 doubles per leg-frame: its byte count must fit in 63 bits
-    const int64_t lim = INT64_MAX / (8 * kFkRow);
-    if (n_seq != 0 && n_frames != 0 && (n_seq > lim / n_legs || n_seq * n_legs > lim / n_frames)) {
-        snprintf(buf, sizeof(buf), "%s: too many leg-frames", who);
-        return bad_arg(buf);
-    }
-    *n_total = n_seq * n_legs * n_frames;
-    return SEQIK_OK;
+    if (n_legs < 1 || n_legs > kMaxLegs) return bad_arg(who, "n_legs must lie in 1..8");
+    if (n_seq < 0 || n_frames < 0) return bad_arg(who, "negative n_seq or n_frames");
+    if (n_frames > INT32_MAX) return bad_arg(who, "n_frames must be below 2^31 (the frame map is int32)");
+    if (flags & ~(SEQIK_GAPS_GENERIC | SEQIK_GAPS_AFFINE))
+        return bad_arg(who, "unknown flags (SEQIK_GAPS_SEQ / _GENERIC, | SEQIK_GAPS_AFFINE)");
+    return seqik::leg_frames_fit(who, n_seq, n_legs, n_frames, n_total);
 }
-
-int check_segments(const char *who, const SeqikLegParams *legs, int32_t n_legs)
-{
-    for (int l = 0; l < n_legs; ++l)
-        for (int k = 0; k < 4; ++k)
-            if (!seqik::is_finite(legs[l].seg[k])) {
-                char buf[160];
-                snprintf(buf, sizeof(buf), "%s: non-finite segment length", who);
-                return bad_arg(buf);
-            }
-    return SEQIK_OK;
-}
-
-int64_t blocks_for(int64_t waves) { return (waves + kWaves - 1) / kWaves; }
 
 }  // namespace
 
@@ -331,38 +275,34 @@ int seqik_gaps_compact_device(const double *d_pose, int64_t n_seq, int32_t n_leg
     int rc = check_sizes(who, n_seq, n_legs, n_frames, flags, &n);
     if (rc != SEQIK_OK) return rc;
     if (!d_pose || !d_cpose || !d_map || !d_n_valid || !legs)
-        return bad_arg("seqik_gaps_compact_device: pose, cpose, map, n_valid and legs must not be null");
-    if ((rc = check_segments(who, legs, n_legs)) != SEQIK_OK) return rc;
+        return bad_arg(who, "pose, cpose, map, n_valid and legs must not be null");
+    if ((rc = seqik::check_segments(who, legs, n_legs)) != SEQIK_OK) return rc;
     if (n == 0) return SEQIK_OK;
     CompactArgs a;
     memset(&a, 0, sizeof(a));
     a.g.n_frames = n_frames;
     a.g.n_chains = n_seq * n_legs;
-    const int64_t blocks64 = (n_frames + 63) / 64;
-    const int64_t k = (blocks64 + kMaxTiles - 1) / kMaxTiles;  // >= 1
-    a.g.tile = 64 * k;
-    a.g.tiles = (n_frames + a.g.tile - 1) / a.g.tile;
+    seqik::tile_geometry(n_frames, &a.g.tile, &a.g.tiles);
     a.g.n_legs = n_legs;
     a.g.rows = seqik::gaps_rows(flags);
     a.pose = d_pose; a.cpose = d_cpose; a.map = d_map; a.n_valid = d_n_valid;
     for (int l = 0; l < kMaxLegs; ++l) seqik::make_gaps_leg(legs[l < n_legs ? l : 0], a.legs[l]);
-    const int64_t tile_blocks = blocks_for(a.g.n_chains * a.g.tiles);
+    const int64_t tile_blocks = seqik::blocks_for(a.g.n_chains * a.g.tiles, kWaves);
     const int64_t pad_per_chain = (n_frames + kBlock - 1) / kBlock;
     if (tile_blocks > UINT32_MAX || a.g.n_chains * pad_per_chain > UINT32_MAX)
-        return bad_arg("seqik_gaps_compact_device: too many leg-frames for one launch");
+        return bad_arg(who, "too many leg-frames for one launch");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     hipLaunchKernelGGL(seqik_gaps_count_kernel, dim3((unsigned)tile_blocks), dim3(kBlock), 0, s, a);
-    HTRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (a.g.tiles > 1) {
-        hipLaunchKernelGGL(seqik_gaps_scan_kernel, dim3((unsigned)blocks_for(a.g.n_chains)), dim3(kBlock), 0, s, a);
-        HTRY(hipGetLastError());
+        hipLaunchKernelGGL(seqik_gaps_scan_kernel, dim3((unsigned)seqik::blocks_for(a.g.n_chains, kWaves)), dim3(kBlock), 0, s, a);
+        HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(seqik_gaps_permute_kernel, dim3((unsigned)tile_blocks), dim3(kBlock), 0, s, a);
-    HTRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(seqik_gaps_pad_kernel, dim3((unsigned)(a.g.n_chains * pad_per_chain)), dim3(kBlock), 0, s, a,
                        pad_per_chain);
-    HTRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 int seqik_gaps_expand_device(const int32_t *d_map, int64_t n_seq, int32_t n_legs, int64_t n_frames, int32_t flags,
@@ -370,13 +310,14 @@ int seqik_gaps_expand_device(const int32_t *d_map, int64_t n_seq, int32_t n_legs
                              const int32_t *d_cnfev, double *d_angles, double *d_fk, int32_t *d_status, int32_t *d_nfev,
                              void *hip_stream)
 {
+    const char *who = "seqik_gaps_expand_device";
     int64_t n = 0;
-    int rc = check_sizes("seqik_gaps_expand_device", n_seq, n_legs, n_frames, flags, &n);
+    int rc = check_sizes(who, n_seq, n_legs, n_frames, flags, &n);
     if (rc != SEQIK_OK) return rc;
     if (!d_map || !d_cangles || !d_angles)
-        return bad_arg("seqik_gaps_expand_device: map, compact angles and angles must not be null");
+        return bad_arg(who, "map, compact angles and angles must not be null");
     if (!d_cfk != !d_fk || !d_cstatus != !d_status || !d_cnfev != !d_nfev)
-        return bad_arg("seqik_gaps_expand_device: fk, status and nfev are pairs: compact and expanded both given or both null");
+        return bad_arg(who, "fk, status and nfev are pairs: compact and expanded both given or both null");
     if (n == 0) return SEQIK_OK;
     ExpandArgs a;
     a.map = d_map; a.cangles = d_cangles; a.cfk = d_cfk; a.cstatus = d_cstatus; a.cnfev = d_cnfev;
@@ -386,13 +327,12 @@ int seqik_gaps_expand_device(const int32_t *d_map, int64_t n_seq, int32_t n_legs
     a.blocks_per_chain = (n_frames + 63) / 64;
     const bool generic = flags & SEQIK_GAPS_GENERIC;
     a.status_width = generic ? 1 : 4;
-    const int64_t blocks = blocks_for(a.n_chains * a.blocks_per_chain);
-    if (blocks > UINT32_MAX) return bad_arg("seqik_gaps_expand_device: too many leg-frames for one launch");
+    const int64_t blocks = seqik::blocks_for(a.n_chains * a.blocks_per_chain, kWaves);
+    if (blocks > UINT32_MAX) return bad_arg(who, "too many leg-frames for one launch");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (generic) hipLaunchKernelGGL(seqik_gaps_expand_kernel<1>, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
     else hipLaunchKernelGGL(seqik_gaps_expand_kernel<4>, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    HTRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 }  // extern "C"
@@ -410,61 +350,39 @@ int solve_gaps(bool generic, const double *pose, int64_t n_seq, int32_t n_legs, 
     int64_t n = 0;
     int rc = check_sizes(who, n_seq, n_legs, n_frames, flags, &n);
     if (rc != SEQIK_OK) return rc;
-    char buf[200];
-    if (!pose || !angles || !legs) {
-        snprintf(buf, sizeof(buf), "%s: pose, angles and legs must not be null", who);
-        return bad_arg(buf);
-    }
-    if (first_stage != 1 || last_stage != 4) {
-        snprintf(buf, sizeof(buf), "%s: skip mode runs all four stages (first_stage 1, last_stage 4)", who);
-        return bad_arg(buf);
-    }
-    if (opt && (opt->frame_lead || opt->chunk_resume || opt->chunk_states || opt->chunk_flags)) {
-        snprintf(buf, sizeof(buf), "%s: frame_lead, chunk_resume, chunk_states and chunk_flags are not supported in skip mode",
-                 who);
-        return bad_arg(buf);
-    }
-    if ((rc = check_segments(who, legs, n_legs)) != SEQIK_OK) return rc;
+    if (!pose || !angles || !legs) return bad_arg(who, "pose, angles and legs must not be null");
+    if (first_stage != 1 || last_stage != 4)
+        return bad_arg(who, "skip mode runs all four stages (first_stage 1, last_stage 4)");
+    if (opt && (opt->frame_lead || opt->chunk_resume || opt->chunk_states || opt->chunk_flags))
+        return bad_arg(who, "frame_lead, chunk_resume, chunk_states and chunk_flags are not supported in skip mode");
+    if ((rc = seqik::check_segments(who, legs, n_legs)) != SEQIK_OK) return rc;
     if (n == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HTRY(scope.enter(opt ? opt->device : -1));
     const size_t n_lf = (size_t)n, n_ch = (size_t)n_seq * n_legs;
-    const int sw = generic ? 1 : 4;  // status / nfev entries per leg-frame
-    const size_t b_pose = sizeof(double) * kGapsRec * n_lf, b_map = sizeof(int32_t) * n_lf;
-    const size_t b_nv = sizeof(int32_t) * n_ch, b_ang = sizeof(double) * 7 * n_lf;
-    const size_t b_fk = fk ? sizeof(double) * kFkRow * n_lf : 0;
-    const size_t b_st = status ? sizeof(int32_t) * sw * n_lf : 0, b_nf = nfev ? sizeof(int32_t) * sw * n_lf : 0;
-    const size_t b_init = init_angles ? sizeof(double) * 7 * n_ch : 0, b_stats = sizeof(int32_t) * 16;
-    using seqik::arena_padded;
-    seqik::HostLeaseGuard g;
-    if ((rc = seqik::host_lease_acquire(&g.lease)) != SEQIK_OK) return rc;
-    rc = seqik::host_lease_reserve(&g.lease, 2 * arena_padded(b_pose) + arena_padded(b_map) + arena_padded(b_nv) +
-                                                 2 * arena_padded(b_ang) + 2 * arena_padded(b_fk) + 2 * arena_padded(b_st) +
-                                                 2 * arena_padded(b_nf) + arena_padded(b_init) + arena_padded(b_stats));
-    if (rc != SEQIK_OK) return rc;
-    hipStream_t stream = g.lease.stream;
-    char *p = g.lease.arena;
-    auto take = [&p](size_t bytes) { char *q = bytes ? p : nullptr; p += arena_padded(bytes); return q; };
-    double *d_pose = reinterpret_cast<double *>(take(b_pose)), *d_cpose = reinterpret_cast<double *>(take(b_pose));
-    int32_t *d_map = reinterpret_cast<int32_t *>(take(b_map)), *d_nv = reinterpret_cast<int32_t *>(take(b_nv));
-    double *d_cang = reinterpret_cast<double *>(take(b_ang)), *d_ang = reinterpret_cast<double *>(take(b_ang));
-    double *d_cfk = reinterpret_cast<double *>(take(b_fk)), *d_fk = reinterpret_cast<double *>(take(b_fk));
-    int32_t *d_cst = reinterpret_cast<int32_t *>(take(b_st)), *d_st = reinterpret_cast<int32_t *>(take(b_st));
-    int32_t *d_cnf = reinterpret_cast<int32_t *>(take(b_nf)), *d_nf = reinterpret_cast<int32_t *>(take(b_nf));
-    double *d_init = reinterpret_cast<double *>(take(b_init));
-    int32_t *d_stats = reinterpret_cast<int32_t *>(take(b_stats));
-    HTRY(hipMemcpyAsync(d_pose, pose, b_pose, hipMemcpyHostToDevice, stream));
-    if (d_init) HTRY(hipMemcpyAsync(d_init, init_angles, b_init, hipMemcpyHostToDevice, stream));
+    const size_t sw = generic ? 1 : 4;  // status / nfev entries per leg-frame
+    seqik::HostCall call;
+    double *d_pose, *d_init, *d_cpose, *d_cang, *d_cfk, *d_ang, *d_fk;
+    int32_t *d_map, *d_cst, *d_cnf, *d_stats, *d_st, *d_nf, *d_nv;
+    call.upload(d_pose, kGapsRec * n_lf, pose);
+    call.upload(d_init, 7 * n_ch, init_angles);
+    call.scratch(d_cpose, kGapsRec * n_lf);
+    call.scratch(d_map, n_lf);
+    call.scratch(d_cang, 7 * n_lf);
+    call.scratch(d_cfk, fk ? kFkRow * n_lf : 0);
     // as the solvers' host entry points: statuses start at -1, counts at 0
-    if (d_cst) HTRY(hipMemsetAsync(d_cst, 0xff, b_st, stream));
-    if (d_cnf) HTRY(hipMemsetAsync(d_cnf, 0, b_nf, stream));
+    call.scratch(d_cst, status ? sw * n_lf : 0).filled(0xff);
+    call.scratch(d_cnf, nfev ? sw * n_lf : 0).filled(0);
+    call.download(d_stats, 16, opt ? opt->chunk_stats : nullptr).filled(0);  // stays zero when the call is not chunked
+    call.download(d_ang, 7 * n_lf, angles);
+    call.download(d_fk, kFkRow * n_lf, fk);
+    call.download(d_st, sw * n_lf, status);
+    call.download(d_nf, sw * n_lf, nfev);
+    // (the compaction needs the counts whether or not the caller wants them)
+    call.produce(d_nv, n_ch, n_valid);
+    if ((rc = call.begin(opt ? opt->device : -1)) != SEQIK_OK) return rc;
+    hipStream_t stream = call.stream();
     SeqikOptions dev_opt;
     if (opt) dev_opt = *opt; else memset(&dev_opt, 0, sizeof(dev_opt));
-    const bool want_stats = opt && opt->chunk_stats;
-    if (want_stats) {
-        HTRY(hipMemsetAsync(d_stats, 0, b_stats, stream));  // stays zero when the call is not chunked
-        dev_opt.chunk_stats = d_stats;
-    }
+    dev_opt.chunk_stats = d_stats;
     rc = seqik_gaps_compact_device(d_pose, n_seq, n_legs, n_frames, flags, legs, d_cpose, d_map, d_nv, stream);
     if (rc == SEQIK_OK)
         rc = generic ? seqik_solve_generic_device(d_cpose, n_seq, n_legs, n_frames, legs, d_cang, d_cfk, d_cst, d_cnf,
@@ -474,15 +392,8 @@ int solve_gaps(bool generic, const double *pose, int64_t n_seq, int32_t n_legs, 
     if (rc == SEQIK_OK)
         rc = seqik_gaps_expand_device(d_map, n_seq, n_legs, n_frames, flags, d_cang, d_cfk, d_cst, d_cnf, d_ang, d_fk, d_st,
                                       d_nf, stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    if (want_stats) HTRY(hipMemcpyAsync(opt->chunk_stats, d_stats, b_stats, hipMemcpyDeviceToHost, stream));
-    HTRY(hipMemcpyAsync(angles, d_ang, b_ang, hipMemcpyDeviceToHost, stream));
-    if (fk) HTRY(hipMemcpyAsync(fk, d_fk, b_fk, hipMemcpyDeviceToHost, stream));
-    if (status) HTRY(hipMemcpyAsync(status, d_st, b_st, hipMemcpyDeviceToHost, stream));
-    if (nfev) HTRY(hipMemcpyAsync(nfev, d_nf, b_nf, hipMemcpyDeviceToHost, stream));
-    if (n_valid) HTRY(hipMemcpyAsync(n_valid, d_nv, b_nv, hipMemcpyDeviceToHost, stream));
-    HTRY(hipStreamSynchronize(stream));
-    return seqik_check_faults_stream(stream);
+    rc = call.finish(rc);
+    return rc ? rc : seqik_check_faults_stream(stream);
 }
 
 }  // namespace

@@ -1,28 +1,18 @@
 // seqik_head.hip -- head / antenna angle kernel and its C ABI entry points (include/seqik.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
 
+#include "seqik_core.hpp"
 #include "seqik_head.hpp"
-#include "seqik_device_scope.hpp"
-#include "seqik_hostctx.hpp"
-#include "../../include/seqik.h"
-
-extern "C" void seqik_set_error(int code, const char *msg);
+#include "seqik_runtime.hpp"
 
 namespace {
 
-typedef double d2 __attribute__((ext_vector_type(2)));
+using seqik::bad_arg;
+using seqik::wave_lds_fence;
 
-// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (the hardware completes a wave's LDS
-// operations in order; this is for the compiler)
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+typedef double d2 __attribute__((ext_vector_type(2)));
 
 // One frame per lane, grid-stride.  Per frame 96 B in (two AoS records of 48 B) and 56 B out (seven SoA rows): the
 // kernel is meant to run at the rate of a copy.  What that took (scripts/microbench/head_split.hip):
@@ -85,15 +75,17 @@ __global__ void __launch_bounds__(256) seqik_signed_angle_kernel(const double *v
         out[t] = seqik::signed_angle3(v1 + t * s1, v2 + t * s2, axis);
 }
 
-int hip_fail(hipError_t e, const char *what)
+// the checks of both head entry points
+int head_validate(const void *r_head, const void *l_head, const void *neck, const void *angles, int64_t n_frames,
+                  int64_t neck_stride, int32_t n_points, int32_t compute_ant)
 {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    seqik_set_error(SEQIK_ERR_HIP, buf);
-    return SEQIK_ERR_HIP;
+    if (!r_head || !l_head || !neck || !angles || n_frames < 0 || (neck_stride != 0 && neck_stride != 3) || n_points < 1)
+        return bad_arg("seqik_head_angles", "bad argument");
+    if (compute_ant && n_points < 2)
+        return bad_arg("seqik_head_angles", "the antenna angles need two key points per side "
+                                            "(antenna base and tip); pass compute_ant = 0 for single-point records");
+    return SEQIK_OK;
 }
-
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
 
 }  // namespace
 
@@ -112,16 +104,7 @@ int seqik_head_angles_ex_device(const double *d_r_head, const double *d_l_head, 
                                 double rest_antenna_pitch, int32_t compute_ant, const double *d_head_roll,
                                 double *d_angles, void *hip_stream)
 {
-    if (!d_r_head || !d_l_head || !d_neck || !d_angles || n_frames < 0 || (neck_stride != 0 && neck_stride != 3) ||
-        n_points < 1) {
-        seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_head_angles: bad argument");
-        return SEQIK_ERR_BAD_ARG;
-    }
-    if (compute_ant && n_points < 2) {
-        seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_head_angles: the antenna angles need two key points per side "
-                                           "(antenna base and tip); pass compute_ant = 0 for single-point records");
-        return SEQIK_ERR_BAD_ARG;
-    }
+    if (int rc = head_validate(d_r_head, d_l_head, d_neck, d_angles, n_frames, neck_stride, n_points, compute_ant)) return rc;
     if (n_frames == 0) return SEQIK_OK;
     seqik::HeadArgs a;
     a.r_head = d_r_head; a.l_head = d_l_head; a.neck = d_neck; a.neck_stride = neck_stride;
@@ -138,8 +121,7 @@ int seqik_head_angles_ex_device(const double *d_r_head, const double *d_l_head, 
     if (a.roll_in) hipLaunchKernelGGL((seqik_head_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
     else if (staged) hipLaunchKernelGGL(seqik_head_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
     else hipLaunchKernelGGL(seqik_head_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-    HTRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 int seqik_head_angles(const double *r_head, const double *l_head, int64_t n_frames, const double *neck,
@@ -154,81 +136,38 @@ int seqik_head_angles_ex(const double *r_head, const double *l_head, int64_t n_f
                          int64_t neck_stride, double rest_head_pitch, double rest_antenna_pitch, int32_t compute_ant,
                          const double *head_roll, double *angles, const SeqikOptions *opt)
 {
-    if (!r_head || !l_head || !neck || !angles || n_frames < 0 || (neck_stride != 0 && neck_stride != 3) || n_points < 1) {
-        seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_head_angles: bad argument");
-        return SEQIK_ERR_BAD_ARG;
-    }
-    if (compute_ant && n_points < 2) {
-        seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_head_angles: the antenna angles need two key points per side "
-                                           "(antenna base and tip); pass compute_ant = 0 for single-point records");
-        return SEQIK_ERR_BAD_ARG;
-    }
+    if (int rc = head_validate(r_head, l_head, neck, angles, n_frames, neck_stride, n_points, compute_ant)) return rc;
     if (n_frames == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HTRY(scope.enter(opt ? opt->device : -1));
-    const int n_out = compute_ant ? 7 : 3;
-    const size_t in_bytes = sizeof(double) * 3 * n_points * n_frames;
-    const size_t roll_bytes = (head_roll && compute_ant) ? sizeof(double) * n_frames : 0;
-    const size_t neck_bytes = sizeof(double) * (neck_stride ? 3 * n_frames : 3);
-    const size_t out_bytes = sizeof(double) * 7 * n_frames;
-    // a pooled context (stream + device arena) as the other host-buffer entry points: no hipMalloc / hipFree per call
-    seqik::HostLeaseGuard g;
-    int rc = seqik::host_lease_acquire(&g.lease);
-    if (rc != SEQIK_OK) return rc;
-    rc = seqik::host_lease_reserve(&g.lease, 2 * seqik::arena_padded(in_bytes) + seqik::arena_padded(neck_bytes) +
-                                                 seqik::arena_padded(out_bytes) + seqik::arena_padded(roll_bytes));
-    if (rc != SEQIK_OK) return rc;
-    hipStream_t stream = g.lease.stream;
-    char *p = g.lease.arena;
-    double *d_r = reinterpret_cast<double *>(p); p += seqik::arena_padded(in_bytes);
-    double *d_l = reinterpret_cast<double *>(p); p += seqik::arena_padded(in_bytes);
-    double *d_n = reinterpret_cast<double *>(p); p += seqik::arena_padded(neck_bytes);
-    double *d_a = reinterpret_cast<double *>(p); p += seqik::arena_padded(out_bytes);
-    double *d_roll = roll_bytes ? reinterpret_cast<double *>(p) : nullptr;
-    if (d_roll) HTRY(hipMemcpyAsync(d_roll, head_roll, roll_bytes, hipMemcpyHostToDevice, stream));
-    HTRY(hipMemcpyAsync(d_r, r_head, in_bytes, hipMemcpyHostToDevice, stream));
-    HTRY(hipMemcpyAsync(d_l, l_head, in_bytes, hipMemcpyHostToDevice, stream));
-    HTRY(hipMemcpyAsync(d_n, neck, neck_bytes, hipMemcpyHostToDevice, stream));
-    rc = seqik_head_angles_ex_device(d_r, d_l, n_frames, n_points, d_n, neck_stride, rest_head_pitch, rest_antenna_pitch,
-                                     compute_ant, d_roll, d_a, stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    HTRY(hipMemcpyAsync(angles, d_a, sizeof(double) * n_out * n_frames, hipMemcpyDeviceToHost, stream));
-    HTRY(hipStreamSynchronize(stream));
-    return SEQIK_OK;
+    const size_t n = (size_t)n_frames;
+    seqik::HostCall call;
+    double *d_roll, *d_r, *d_l, *d_n, *d_a;
+    call.upload(d_roll, n, compute_ant ? head_roll : nullptr);
+    call.upload(d_r, 3 * n_points * n, r_head);
+    call.upload(d_l, 3 * n_points * n, l_head);
+    call.upload(d_n, neck_stride ? 3 * n : 3, neck);
+    call.download(d_a, 7 * n, angles, (compute_ant ? 7 : 3) * n);
+    if (int rc = call.begin(opt ? opt->device : -1)) return rc;
+    return call.finish(seqik_head_angles_ex_device(d_r, d_l, n_frames, n_points, d_n, neck_stride, rest_head_pitch,
+                                                   rest_antenna_pitch, compute_ant, d_roll, d_a, call.stream()));
 }
 
 int seqik_signed_angles(const double *v1, int64_t v1_stride, const double *v2, int64_t v2_stride, const double *axis,
                         int64_t n, double *out, const SeqikOptions *opt)
 {
-    if (!v1 || !v2 || !axis || !out || n < 0 || (v1_stride != 0 && v1_stride != 3) || (v2_stride != 0 && v2_stride != 3)) {
-        seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_signed_angles: bad argument");
-        return SEQIK_ERR_BAD_ARG;
-    }
+    if (!v1 || !v2 || !axis || !out || n < 0 || (v1_stride != 0 && v1_stride != 3) || (v2_stride != 0 && v2_stride != 3))
+        return bad_arg("seqik_signed_angles", "bad argument");
     if (n == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HTRY(scope.enter(opt ? opt->device : -1));
-    const size_t b1 = sizeof(double) * (v1_stride ? 3 * n : 3), b2 = sizeof(double) * (v2_stride ? 3 * n : 3);
-    const size_t bo = sizeof(double) * n;
-    seqik::HostLeaseGuard g;
-    int rc = seqik::host_lease_acquire(&g.lease);
-    if (rc != SEQIK_OK) return rc;
-    rc = seqik::host_lease_reserve(&g.lease, seqik::arena_padded(b1) + seqik::arena_padded(b2) + seqik::arena_padded(bo));
-    if (rc != SEQIK_OK) return rc;
-    hipStream_t stream = g.lease.stream;
-    char *p = g.lease.arena;
-    double *d1 = reinterpret_cast<double *>(p); p += seqik::arena_padded(b1);
-    double *d2v = reinterpret_cast<double *>(p); p += seqik::arena_padded(b2);
-    double *d_o = reinterpret_cast<double *>(p);
-    HTRY(hipMemcpyAsync(d1, v1, b1, hipMemcpyHostToDevice, stream));
-    HTRY(hipMemcpyAsync(d2v, v2, b2, hipMemcpyHostToDevice, stream));
+    seqik::HostCall call;
+    double *d1, *d2v, *d_o;
+    call.upload(d1, v1_stride ? 3 * n : 3, v1);
+    call.upload(d2v, v2_stride ? 3 * n : 3, v2);
+    call.download(d_o, n, out);
+    if (int rc = call.begin(opt ? opt->device : -1)) return rc;
     int64_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(seqik_signed_angle_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d1, v1_stride, d2v, v2_stride,
-                       axis[0], axis[1], axis[2], n, d_o);
-    HTRY(hipGetLastError());
-    HTRY(hipMemcpyAsync(out, d_o, bo, hipMemcpyDeviceToHost, stream));
-    HTRY(hipStreamSynchronize(stream));
-    return SEQIK_OK;
+    hipLaunchKernelGGL(seqik_signed_angle_kernel, dim3((unsigned)blocks), dim3(256), 0, call.stream(), d1, v1_stride, d2v,
+                       v2_stride, axis[0], axis[1], axis[2], n, d_o);
+    return call.finish(seqik::launched());
 }
 
 }  // extern "C"

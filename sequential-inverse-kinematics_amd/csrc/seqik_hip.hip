@@ -11,8 +11,7 @@
 
 #include "seqik_core.hpp"
 #include "seqik_consts.hpp"
-#include "seqik_device_scope.hpp"
-#include "seqik_hostctx.hpp"
+#include "seqik_runtime.hpp"
 
 #if SEQIK_BLOCK_CYCLES
 namespace seqik { __device__ unsigned long long seqik_block_cycles[4][BLK_COUNT + 1]; }
@@ -62,13 +61,8 @@ constexpr int kMaxBlock = 256;
 #define SEQIK_WAVES_PER_EU 3
 #endif
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, const char *detail = "")
-{
-    snprintf(g_err, sizeof(g_err), fmt, detail);
-    return code;
-}
+using seqik::fail;
+using seqik::HostCall;
 
 // the message of a seqik::validate_leg* result (SEQIK_OK: none)
 int leg_error(int rc)
@@ -79,12 +73,6 @@ int leg_error(int rc)
         return fail(rc, "a joint limit is non-zero but smaller than 2^-600 in magnitude: not supported (DESIGN.md, floating-point contract)%s");
     return rc;
 }
-
-#define HIP_TRY(expr)                                                              \
-    do {                                                                           \
-        hipError_t e_ = (expr);                                                    \
-        if (e_ != hipSuccess) return fail(SEQIK_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Device faults.  The reference reports every failure as a Python exception and never returns silent garbage
@@ -168,10 +156,12 @@ int check_faults(const char *where, int slot)
         if (w != 0 && v == 0) v = w;
     }
     if (v == 0) return SEQIK_OK;
-    snprintf(g_err, sizeof(g_err),
+    char msg[512];
+    snprintf(msg, sizeof(msg),
              "%s: stage pipeline watchdog: a lane of stage %d waited more than %d passes for its neighbour wave; the "
              "remaining frames of its chain hold NaN -- the results of the calls since the last check are invalid",
              where, (int)v, (int)seqik::PIPE_SPIN_LIMIT);
+    seqik_set_error(SEQIK_ERR_HIP, msg);
     return SEQIK_ERR_HIP;
 }
 
@@ -961,8 +951,7 @@ template <typename... P, typename... A>
 int launch_kernel(void (*k)(P...), dim3 grid, dim3 block, hipStream_t stream, const A &...args)
 {
     hipLaunchKernelGGL(k, grid, block, 0, stream, args...);
-    HIP_TRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 using GenericLegTable = seqik::GenericLeg;   // { GenericConst gc; LegAffine aff; } (seqik_generic.hpp)
@@ -1210,69 +1199,6 @@ int workspace_for(hipStream_t stream, size_t bytes, double **out)
     *out = w->d;
     return SEQIK_OK;
 }
-
-// Context of a host-buffer call (seqik_solve_seq, seqik_solve_generic): a stream and one grow-only device arena
-// that the call's device buffers are carved from.  Contexts are pooled per device: a call takes a free one (or makes
-// one) and gives it back, so repeated calls neither create streams nor call hipMalloc / hipFree (which drains the
-// device), and -- because the stream lives on -- the hand-off workspace keyed by it (workspace_for) is reused instead
-// of stranded.  Concurrent host threads get distinct contexts; seqik_release_workspaces() frees the idle ones.
-struct HostCtx {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    char *arena = nullptr;
-    size_t arena_bytes = 0;
-    bool busy = false;
-};
-std::mutex g_ctx_mutex;
-std::vector<HostCtx *> g_ctx;
-
-int acquire_ctx(HostCtx **out)
-{
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_ctx_mutex);
-    for (HostCtx *c : g_ctx)
-        if (c->device == dev && !c->busy) { c->busy = true; *out = c; return SEQIK_OK; }
-    HostCtx *c = new HostCtx;
-    c->device = dev;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return fail(SEQIK_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-    c->busy = true;
-    g_ctx.push_back(c);
-    *out = c;
-    return SEQIK_OK;
-}
-
-void release_ctx(HostCtx *c)
-{
-    std::lock_guard<std::mutex> lock(g_ctx_mutex);
-    c->busy = false;
-}
-
-int ctx_reserve(HostCtx *c, size_t bytes)
-{
-    if (c->arena_bytes >= bytes) return SEQIK_OK;
-    if (c->arena) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipFree(c->arena));
-        c->arena = nullptr;
-        c->arena_bytes = 0;
-    }
-    const size_t want = bytes + bytes / 8;  // a little head room: slightly longer recordings do not reallocate
-    if (hipMalloc(reinterpret_cast<void **>(&c->arena), want) == hipSuccess) { c->arena_bytes = want; return SEQIK_OK; }
-    (void)hipGetLastError();
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c->arena), bytes));
-    c->arena_bytes = bytes;
-    return SEQIK_OK;
-}
-
-// bump allocator over the arena (256-byte aligned pieces)
-struct ArenaCursor {
-    char *base;
-    size_t off = 0;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    template <typename T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + off); off += padded(sizeof(T) * count); return p; }
-};
 
 // null pointers and sizes: the first check of every entry point of the leg and the generic solver
 int check_sizes(int64_t n_seq, int32_t n_legs, int64_t n_frames, const SeqikLegParams *legs, const void *pose,
@@ -1576,40 +1502,6 @@ int launch(const double *d_pose, int64_t n_seq, int32_t n_legs, int64_t n_frames
 
 }  // namespace
 
-// the pooled context for the other translation units (seqik_hostctx.hpp)
-namespace seqik {
-
-int host_lease_acquire(HostLease *lease)
-{
-    HostCtx *c = nullptr;
-    const int rc = acquire_ctx(&c);
-    if (rc != SEQIK_OK) return rc;
-    lease->ctx = c;
-    lease->stream = c->stream;
-    lease->arena = c->arena;
-    return SEQIK_OK;
-}
-
-int host_lease_reserve(HostLease *lease, size_t bytes)
-{
-    HostCtx *c = static_cast<HostCtx *>(lease->ctx);
-    const int rc = ctx_reserve(c, bytes);
-    lease->arena = c->arena;
-    return rc;
-}
-
-void host_lease_release(HostLease *lease)
-{
-    if (lease->ctx) {
-        // also on a failing path: work queued so far may still use the arena / the caller's buffers
-        (void)hipStreamSynchronize(static_cast<HostCtx *>(lease->ctx)->stream);
-        release_ctx(static_cast<HostCtx *>(lease->ctx));
-    }
-    lease->ctx = nullptr;
-}
-
-}  // namespace seqik
-
 extern "C" {
 
 int seqik_abi_version(void) { return SEQIK_ABI_VERSION; }
@@ -1620,8 +1512,6 @@ int seqik_device_count(void)
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-const char *seqik_last_error(void) { return g_err; }
 
 int seqik_release_workspaces(void)
 {
@@ -1637,19 +1527,7 @@ int seqik_release_workspaces(void)
     }
     g_ws.clear();
     bool any_busy = false;
-    {
-        std::lock_guard<std::mutex> ctx_lock(g_ctx_mutex);
-        for (size_t i = 0; i < g_ctx.size();) {
-            HostCtx *c = g_ctx[i];
-            if (c->busy) { any_busy = true; ++i; continue; }  // a call is running on another thread
-            HIP_TRY(hipSetDevice(c->device));
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            if (c->arena) HIP_TRY(hipFree(c->arena));
-            HIP_TRY(hipStreamDestroy(c->stream));
-            delete c;
-            g_ctx.erase(g_ctx.begin() + i);
-        }
-    }
+    if (int rc = seqik::release_idle_contexts(&any_busy)) return rc;
     HIP_TRY(hipSetDevice(prev));
     // the cached leg tables stay while a host-buffer call is running on another thread: it may have fetched its table
     // pointer already and not launched yet (they are freed by the next release that finds every context idle)
@@ -1668,9 +1546,6 @@ int seqik_device_attributes(int32_t device, int32_t *compute_units, int32_t *clo
     if (hbm_bytes) *hbm_bytes = (int64_t)prop.totalGlobalMem;
     return SEQIK_OK;
 }
-
-// used by the other translation units of the library (seqik_head.hip)
-void seqik_set_error(int code, const char *msg) { (void)fail(code, "%s", msg); }
 
 int seqik_check_faults(void) { return check_faults("seqik_check_faults", -1); }
 
@@ -1775,57 +1650,26 @@ int seqik_solve_generic_device(const double *d_pose, int64_t n_seq, int32_t n_le
     return launch_kernel(generic_kernel(diag, grouped), grid, blk, stream, a);
 }
 
-// device buffers of one host-buffer call, carved from a pooled context's arena
-struct HostCall {
-    HostCtx *ctx = nullptr;
-    hipStream_t stream = nullptr;
-    // (on every exit path, also the failing ones: copies and kernels queued so far may still be writing into the arena
-    // or the caller's buffers; the context goes back to the pool only once its stream is idle)
-    ~HostCall()
-    {
-        if (!ctx) return;
-        if (stream) (void)hipStreamSynchronize(stream);
-        release_ctx(ctx);
-    }
-};
-
 int seqik_solve_generic(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n_frames,
                         const SeqikLegParams *legs, double *angles, double *fk, int32_t *status, int32_t *nfev,
                         const double *init_angles, const SeqikAffine *affine, const SeqikOptions *opt)
 {
     int rc = check_generic_args(n_seq, n_legs, n_frames, legs, pose, angles);
     if (rc != SEQIK_OK) return rc;
-    const size_t n_lf = (size_t)n_seq * n_legs * n_frames;
+    const size_t n_lf = (size_t)n_seq * n_legs * n_frames, n_ch = (size_t)n_seq * n_legs;
     if (n_lf == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HIP_TRY(scope.enter(opt ? opt->device : -1));
     HostCall call;
-    if ((rc = acquire_ctx(&call.ctx)) != SEQIK_OK) return rc;
-    const size_t n_ch = (size_t)n_seq * n_legs;
-    const size_t need = ArenaCursor::padded(sizeof(double) * 15 * n_lf) + ArenaCursor::padded(sizeof(double) * 7 * n_lf) +
-                        (fk ? ArenaCursor::padded(sizeof(double) * 27 * n_lf) : 0) +
-                        (status ? ArenaCursor::padded(sizeof(int32_t) * n_lf) : 0) +
-                        (nfev ? ArenaCursor::padded(sizeof(int32_t) * n_lf) : 0) +
-                        (init_angles ? ArenaCursor::padded(sizeof(double) * 7 * n_ch) : 0);
-    if ((rc = ctx_reserve(call.ctx, need)) != SEQIK_OK) return rc;
-    hipStream_t stream = call.ctx->stream;
-    call.stream = stream;
-    ArenaCursor cur{call.ctx->arena};
-    double *d_pose = cur.take<double>(15 * n_lf), *d_angles = cur.take<double>(7 * n_lf);
-    double *d_fk = fk ? cur.take<double>(27 * n_lf) : nullptr;
-    int32_t *d_status = status ? cur.take<int32_t>(n_lf) : nullptr, *d_nfev = nfev ? cur.take<int32_t>(n_lf) : nullptr;
-    double *d_init = init_angles ? cur.take<double>(7 * n_ch) : nullptr;
-    if (d_init) HIP_TRY(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
-    rc = seqik_solve_generic_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk, d_status, d_nfev, d_init,
-                                    nullptr, affine, opt, stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    HIP_TRY(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (fk) HIP_TRY(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
-    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * n_lf, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return SEQIK_OK;
+    double *d_init, *d_pose, *d_angles, *d_fk;
+    int32_t *d_status, *d_nfev;
+    call.upload(d_init, 7 * n_ch, init_angles);
+    call.upload(d_pose, 15 * n_lf, pose);
+    call.download(d_angles, 7 * n_lf, angles);
+    call.download(d_fk, 27 * n_lf, fk);
+    call.download(d_status, n_lf, status);
+    call.download(d_nfev, n_lf, nfev);
+    if ((rc = call.begin(opt ? opt->device : -1)) != SEQIK_OK) return rc;
+    return call.finish(seqik_solve_generic_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk, d_status, d_nfev,
+                                                  d_init, nullptr, affine, opt, call.stream()));
 }
 
 int seqik_solve_seq(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n_frames,
@@ -1835,13 +1679,8 @@ int seqik_solve_seq(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n
 {
     int rc = check_args(n_seq, n_legs, n_frames, legs, first_stage, last_stage, pose, angles);
     if (rc != SEQIK_OK) return rc;
-    const size_t n_lf = (size_t)n_seq * n_legs * n_frames;  // leg-frames
+    const size_t n_lf = (size_t)n_seq * n_legs * n_frames, n_ch = (size_t)n_seq * n_legs;  // leg-frames, chains
     if (n_lf == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HIP_TRY(scope.enter(opt ? opt->device : -1));
-    HostCall call;
-    if ((rc = acquire_ctx(&call.ctx)) != SEQIK_OK) return rc;
-    const bool want_fk = fk && last_stage == 4;
     // frame chunks: statistics and the per-chunk report are produced on the device and copied back
     int32_t pl_chunk = 0, pl_halo = 0, pl_lead = 0;
     int64_t pl_k = 0;
@@ -1849,50 +1688,28 @@ int seqik_solve_seq(const double *pose, int64_t n_seq, int32_t n_legs, int64_t n
     const bool chunked = first_stage == 1 && last_stage == 4 && !diag && pick_frame_chunks(opt, n_frames, pl_chunk, pl_halo, pl_lead, pl_k);
     if (opt && (opt->chunk_states || opt->chunk_resume))
         return fail(SEQIK_ERR_BAD_ARG, "chunk_states / chunk_resume: device entry point only (seqik_solve_seq_device)%s");
-    const bool want_stats = opt && opt->chunk_stats;
-    const bool want_flags = opt && opt->chunk_flags && chunked;
-    const size_t n_ch = (size_t)n_seq * n_legs;
-    const size_t n_flags = want_flags ? n_ch * (size_t)pl_k : 0;
-    const size_t need = ArenaCursor::padded(sizeof(double) * 15 * n_lf) + ArenaCursor::padded(sizeof(double) * 7 * n_lf) +
-                        (want_fk ? ArenaCursor::padded(sizeof(double) * 27 * n_lf) : 0) +
-                        (status ? ArenaCursor::padded(sizeof(int32_t) * 4 * n_lf) : 0) +
-                        (nfev ? ArenaCursor::padded(sizeof(int32_t) * 4 * n_lf) : 0) +
-                        (init_angles ? ArenaCursor::padded(sizeof(double) * 7 * n_ch) : 0) + 256 + ArenaCursor::padded(n_flags);
-    if ((rc = ctx_reserve(call.ctx, need)) != SEQIK_OK) return rc;
-    hipStream_t stream = call.ctx->stream;
-    call.stream = stream;
-    ArenaCursor cur{call.ctx->arena};
-    double *d_pose = cur.take<double>(15 * n_lf), *d_angles = cur.take<double>(7 * n_lf);
-    double *d_fk = want_fk ? cur.take<double>(27 * n_lf) : nullptr;
-    int32_t *d_status = status ? cur.take<int32_t>(4 * n_lf) : nullptr, *d_nfev = nfev ? cur.take<int32_t>(4 * n_lf) : nullptr;
-    double *d_init = init_angles ? cur.take<double>(7 * n_ch) : nullptr;
-    int32_t *d_stats = cur.take<int32_t>(16);
-    uint8_t *d_flags = want_flags ? cur.take<uint8_t>(n_flags) : nullptr;
-    if (d_init) HIP_TRY(hipMemcpyAsync(d_init, init_angles, sizeof(double) * 7 * n_ch, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_pose, pose, sizeof(double) * 15 * n_lf, hipMemcpyHostToDevice, stream));
+    HostCall call;
+    double *d_init, *d_pose, *d_angles, *d_fk;
+    int32_t *d_status, *d_nfev, *d_stats;
+    uint8_t *d_flags;
+    call.upload(d_init, 7 * n_ch, init_angles);
+    call.upload(d_pose, 15 * n_lf, pose);
+    // (the small reports first: they are downloaded in front of the results)
+    call.download(d_stats, 16, opt ? opt->chunk_stats : nullptr).filled(0);  // stays zero when the call is not chunked
+    call.download(d_flags, n_ch * (size_t)pl_k, opt && chunked ? opt->chunk_flags : nullptr);
     // angles is in/out: columns of stages that do not run are inputs (earlier stages) or stay as they are
-    if (first_stage > 1 || last_stage < 4)
-        HIP_TRY(hipMemcpyAsync(d_angles, angles, sizeof(double) * 7 * n_lf, hipMemcpyHostToDevice, stream));
-    if (d_status) HIP_TRY(hipMemsetAsync(d_status, 0xff, sizeof(int32_t) * 4 * n_lf, stream));
-    if (d_nfev) HIP_TRY(hipMemsetAsync(d_nfev, 0, sizeof(int32_t) * 4 * n_lf, stream));
+    call.inout(d_angles, 7 * n_lf, angles, first_stage > 1 || last_stage < 4);
+    call.download(d_fk, 27 * n_lf, last_stage == 4 ? fk : nullptr);
+    call.download(d_status, 4 * n_lf, status).filled(0xff);
+    call.download(d_nfev, 4 * n_lf, nfev).filled(0);
+    if ((rc = call.begin(opt ? opt->device : -1)) != SEQIK_OK) return rc;
     SeqikOptions dev_opt;
     if (opt) dev_opt = *opt; else memset(&dev_opt, 0, sizeof(dev_opt));
     dev_opt.chunk_flags = d_flags;
-    if (want_stats) {
-        HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(int32_t) * 16, stream));  // stays zero when the call is not chunked
-        dev_opt.chunk_stats = d_stats;
-    }
-    rc = seqik_solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, first_stage, last_stage, d_angles,
-                                d_fk, d_status, d_nfev, d_init, nullptr, affine, opt ? &dev_opt : nullptr, stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    if (want_stats) HIP_TRY(hipMemcpyAsync(opt->chunk_stats, d_stats, sizeof(int32_t) * 16, hipMemcpyDeviceToHost, stream));
-    if (want_flags) HIP_TRY(hipMemcpyAsync(opt->chunk_flags, d_flags, n_flags, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(angles, d_angles, sizeof(double) * 7 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (want_fk) HIP_TRY(hipMemcpyAsync(fk, d_fk, sizeof(double) * 27 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
-    if (nfev) HIP_TRY(hipMemcpyAsync(nfev, d_nfev, sizeof(int32_t) * 4 * n_lf, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return check_faults("seqik_solve_seq", known_slot(stream));
+    dev_opt.chunk_stats = d_stats;
+    rc = call.finish(seqik_solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, first_stage, last_stage, d_angles, d_fk,
+                                            d_status, d_nfev, d_init, nullptr, affine, opt ? &dev_opt : nullptr, call.stream()));
+    return rc ? rc : check_faults("seqik_solve_seq", known_slot(call.stream()));
 }
 
 // Self-test hook of the floating-point contract: q[i] = div_(a[i], b[i]), r[i] = sqrt_(a[i]) on the device.
@@ -1906,19 +1723,15 @@ int seqik_selftest_div_sqrt(const double *a, const double *b, double *q, double 
 {
     if (!a || !b || !q || !r || n < 0) return fail(SEQIK_ERR_BAD_ARG, "null pointer argument%s");
     if (n == 0) return SEQIK_OK;
-    double *d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * 4 * n));
-    hipError_t e = hipMemcpy(d, a, sizeof(double) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + n, b, sizeof(double) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(seqik_selftest_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d, d + n, d + 2 * n, d + 3 * n, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(q, d + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(r, d + 3 * n, sizeof(double) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(SEQIK_ERR_HIP, "seqik_selftest_div_sqrt: %s", hipGetErrorString(e));
-    return SEQIK_OK;
+    HostCall call;
+    double *d_a, *d_b, *d_q, *d_r;
+    call.upload(d_a, n, a);
+    call.upload(d_b, n, b);
+    call.download(d_q, n, q);
+    call.download(d_r, n, r);
+    if (int rc = call.begin(-1)) return rc;
+    return call.finish(launch_kernel(seqik_selftest_div_sqrt_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), call.stream(),
+                                     d_a, d_b, d_q, d_r, n));
 }
 
 // r[i] = sqrt_pos_(a[i]): the select-free square root the Coleman-Li distances go through (run_stage, run_generic)
@@ -1932,17 +1745,13 @@ int seqik_selftest_sqrt_pos(const double *a, double *r, int64_t n)
 {
     if (!a || !r || n < 0) return fail(SEQIK_ERR_BAD_ARG, "null pointer argument%s");
     if (n == 0) return SEQIK_OK;
-    double *d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof(double) * 2 * n));
-    hipError_t e = hipMemcpy(d, a, sizeof(double) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(seqik_selftest_sqrt_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, d, d + n, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(r, d + n, sizeof(double) * n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(SEQIK_ERR_HIP, "seqik_selftest_sqrt_pos: %s", hipGetErrorString(e));
-    return SEQIK_OK;
+    HostCall call;
+    double *d_a, *d_r;
+    call.upload(d_a, n, a);
+    call.download(d_r, n, r);
+    if (int rc = call.begin(-1)) return rc;
+    return call.finish(launch_kernel(seqik_selftest_sqrt_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), call.stream(),
+                                     d_a, d_r, n));
 }
 
 int seqik_frame_chunk_plan(int64_t n_frames, const SeqikOptions *opt, int32_t *chunk, int32_t *halo, int64_t *n_chunks)

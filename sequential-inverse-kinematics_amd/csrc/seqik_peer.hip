@@ -12,28 +12,13 @@
 // No reference counterpart: the reference's "gather" is multiprocessing.Pool returning pickled dicts
 // (examples/example_leg_inv_kinematics_parallel.py:186-187).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <string.h>
 
-#include "../../include/seqik.h"
-
-extern "C" void seqik_set_error(int code, const char *msg);
+#include "seqik_runtime.hpp"
 
 namespace {
 
-int p_fail(const char *what, hipError_t e)
-{
-    char buf[384];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    seqik_set_error(SEQIK_ERR_HIP, buf);
-    return SEQIK_ERR_HIP;
-}
-
-#define PTRY(expr)                                      \
-    do {                                                \
-        hipError_t e_ = (expr);                         \
-        if (e_ != hipSuccess) return p_fail(#expr, e_); \
-    } while (0)
+using seqik::bad_arg;
 
 static_assert(sizeof(hipIpcMemHandle_t) == SEQIK_PEER_HANDLE_BYTES, "handle size of the ABI");
 
@@ -43,46 +28,46 @@ extern "C" {
 
 int seqik_peer_alloc(void **d_ptr, size_t bytes)
 {
-    if (!d_ptr || bytes == 0) { seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_peer_alloc: null pointer / zero size"); return SEQIK_ERR_BAD_ARG; }
-    PTRY(hipMalloc(d_ptr, bytes));  // its own allocation: an IPC handle names a whole allocation
+    if (!d_ptr || bytes == 0) return bad_arg("seqik_peer_alloc", "null pointer / zero size");
+    HIP_TRY(hipMalloc(d_ptr, bytes));  // its own allocation: an IPC handle names a whole allocation
     return SEQIK_OK;
 }
 
 int seqik_peer_free(void *d_ptr)
 {
-    if (d_ptr) PTRY(hipFree(d_ptr));
+    if (d_ptr) HIP_TRY(hipFree(d_ptr));
     return SEQIK_OK;
 }
 
 int seqik_peer_export(const void *d_ptr, unsigned char *handle)
 {
-    if (!d_ptr || !handle) { seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_peer_export: null pointer"); return SEQIK_ERR_BAD_ARG; }
+    if (!d_ptr || !handle) return bad_arg("seqik_peer_export", "null pointer");
     hipIpcMemHandle_t h;
-    PTRY(hipIpcGetMemHandle(&h, const_cast<void *>(d_ptr)));
+    HIP_TRY(hipIpcGetMemHandle(&h, const_cast<void *>(d_ptr)));
     memcpy(handle, &h, sizeof(h));
     return SEQIK_OK;
 }
 
 int seqik_peer_open(const unsigned char *handle, void **d_ptr)
 {
-    if (!handle || !d_ptr) { seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_peer_open: null pointer"); return SEQIK_ERR_BAD_ARG; }
+    if (!handle || !d_ptr) return bad_arg("seqik_peer_open", "null pointer");
     hipIpcMemHandle_t h;
     memcpy(&h, handle, sizeof(h));
-    PTRY(hipIpcOpenMemHandle(d_ptr, h, hipIpcMemLazyEnablePeerAccess));
+    HIP_TRY(hipIpcOpenMemHandle(d_ptr, h, hipIpcMemLazyEnablePeerAccess));
     return SEQIK_OK;
 }
 
 int seqik_peer_close(void *d_ptr)
 {
-    if (d_ptr) PTRY(hipIpcCloseMemHandle(d_ptr));
+    if (d_ptr) HIP_TRY(hipIpcCloseMemHandle(d_ptr));
     return SEQIK_OK;
 }
 
 int seqik_peer_copy(void *d_dst, const void *d_src, size_t bytes, void *hip_stream)
 {
-    if (!d_dst || !d_src) { seqik_set_error(SEQIK_ERR_BAD_ARG, "seqik_peer_copy: null pointer"); return SEQIK_ERR_BAD_ARG; }
+    if (!d_dst || !d_src) return bad_arg("seqik_peer_copy", "null pointer");
     if (bytes == 0) return SEQIK_OK;
-    PTRY(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
+    HIP_TRY(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
     return SEQIK_OK;
 }
 

@@ -24,26 +24,24 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include "seqik_resample.hpp"
-#include "seqik_device_scope.hpp"
-#include "seqik_hostctx.hpp"
+#include "seqik_runtime.hpp"
 #include "../../include/seqik_resample.h"
-
-extern "C" void seqik_set_error(int code, const char *msg);
 
 namespace {
 
+using seqik::bad_arg;
+using seqik::kMaxTiles;  // table tiles per chain (scan: 16 rows of 64 lanes)
 using seqik::PchipKnot;
 using seqik::ResampleParams;
+using seqik::wave_lds_fence;
 
 constexpr int kBlock = 256;       // threads per workgroup: 4 independent wavefronts
 constexpr int kWaves = kBlock / 64;
 constexpr int kStage = 256;       // doubles per LDS array and wavefront: 256 / width knots
 constexpr int kMaxRows = 64;      // 512-byte lines per tile (keeps the width division below exact, see div_w)
-constexpr int kMaxTiles = 1024;   // table tiles per chain (scan: 16 rows of 64 lanes)
 constexpr int kDivShift = 17;
 
 struct ResampleArgs {
@@ -56,14 +54,6 @@ struct ResampleArgs {
     uint32_t magic;  // ceil(2^17 / width)
     int64_t tab_tile, tab_tiles;  // F, tiles per chain of the table kernels
 };
-
-// orders a wavefront's LDS writes before its reads of what OTHER lanes wrote (see seqik_fk.hip)
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // x / width for x < 4200: magic = ceil(2^17 / width) errs by less than width <= 16 parts in 2^17
 __device__ __forceinline__ int div_w(int x, uint32_t magic) { return (int)(((uint32_t)x * magic) >> kDivShift); }
@@ -325,24 +315,6 @@ __global__ void __launch_bounds__(kBlock) seqik_resample_tables_fix_kernel(Resam
     if (j != ts && te + 1 < n && next[j] >= n) next[j] = next[te + 1];
 }
 
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-    seqik_set_error(SEQIK_ERR_HIP, buf);
-    return SEQIK_ERR_HIP;
-}
-
-#define HTRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return hip_fail(e_, #expr); } while (0)
-
-int bad_arg(const char *who, const char *msg)
-{
-    char buf[256];
-    snprintf(buf, sizeof(buf), "%s: %s", who, msg);
-    seqik_set_error(SEQIK_ERR_BAD_ARG, buf);
-    return SEQIK_ERR_BAD_ARG;
-}
-
 bool step_ok(double ts) { return ts == ts && ts >= 0x1p-500 && ts <= 0x1p500; }
 
 // n_out or a negative error code
@@ -373,8 +345,6 @@ int resample_validate(const char *who, const double *y, int64_t n_chains, int64_
     if (n_chains != 0 && (n_chains > lim / n_out || n_chains > lim / n_frames)) return bad_arg(who, "too many values");
     return SEQIK_OK;
 }
-
-int64_t blocks_for(int64_t waves) { return (waves + kWaves - 1) / kWaves; }
 
 }  // namespace
 
@@ -422,31 +392,28 @@ int seqik_resample_pchip_device(const double *d_y, int64_t n_chains, int64_t n_f
     a.rows = lines >= (double)kMaxRows ? kMaxRows : (lines >= 1.0 ? (int32_t)lines : 1);
     a.magic = ((1u << kDivShift) + (uint32_t)width - 1u) / (uint32_t)width;
     a.tiles_per_chain = (a.chain_elems + 64 * (int64_t)a.rows - 1) / (64 * (int64_t)a.rows);
-    const int64_t blocks64 = (n_frames + 63) / 64;
-    a.tab_tile = 64 * ((blocks64 + kMaxTiles - 1) / kMaxTiles);
-    a.tab_tiles = (n_frames + a.tab_tile - 1) / a.tab_tile;
-    const int64_t blocks = blocks_for(n_chains * a.tiles_per_chain);
-    const int64_t tab_blocks = blocks_for(n_chains * a.tab_tiles), fix_per_chain = (n_frames + kBlock - 1) / kBlock;
+    seqik::tile_geometry(n_frames, &a.tab_tile, &a.tab_tiles);
+    const int64_t blocks = seqik::blocks_for(n_chains * a.tiles_per_chain, kWaves);
+    const int64_t tab_blocks = seqik::blocks_for(n_chains * a.tab_tiles, kWaves), fix_per_chain = (n_frames + kBlock - 1) / kBlock;
     if (blocks > INT32_MAX || (bridge && (tab_blocks > INT32_MAX || n_chains * fix_per_chain > INT32_MAX)))
         return bad_arg(who, "too many values for one launch");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (bridge) {
         hipLaunchKernelGGL(seqik_resample_tables_tile_kernel, dim3((unsigned)tab_blocks), dim3(kBlock), 0, s, a);
-        HTRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (a.tab_tiles > 1) {
-            hipLaunchKernelGGL(seqik_resample_tables_scan_kernel, dim3((unsigned)blocks_for(n_chains)), dim3(kBlock), 0, s,
+            hipLaunchKernelGGL(seqik_resample_tables_scan_kernel, dim3((unsigned)seqik::blocks_for(n_chains, kWaves)), dim3(kBlock), 0, s,
                                a);
-            HTRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(seqik_resample_tables_fix_kernel, dim3((unsigned)(n_chains * fix_per_chain)), dim3(kBlock),
                                0, s, a, fix_per_chain);
-            HTRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(seqik_resample_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
     } else {
         hipLaunchKernelGGL(seqik_resample_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
     }
-    HTRY(hipGetLastError());
-    return SEQIK_OK;
+    return seqik::launched();
 }
 
 int seqik_resample_pchip(const double *y, int64_t n_chains, int64_t n_frames, int32_t width, double original_ts,
@@ -455,28 +422,16 @@ int seqik_resample_pchip(const double *y, int64_t n_chains, int64_t n_frames, in
     int rc = resample_validate("seqik_resample_pchip", y, n_chains, n_frames, width, original_ts, new_ts, flags, out, n_out);
     if (rc != SEQIK_OK) return rc;
     if (n_chains == 0) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    HTRY(scope.enter(device));
-    const size_t b_y = sizeof(double) * (size_t)width * (size_t)n_chains * (size_t)n_frames;
-    const size_t b_out = sizeof(double) * (size_t)width * (size_t)n_chains * (size_t)n_out;
-    const size_t b_ws = seqik_resample_workspace_bytes(n_chains, n_frames, flags);
-    using seqik::arena_padded;
-    seqik::HostLeaseGuard g;
-    if ((rc = seqik::host_lease_acquire(&g.lease)) != SEQIK_OK) return rc;
-    if ((rc = seqik::host_lease_reserve(&g.lease, arena_padded(b_y) + arena_padded(b_out) + arena_padded(b_ws))) != SEQIK_OK)
-        return rc;
-    hipStream_t stream = g.lease.stream;
-    char *p = g.lease.arena;
-    double *d_y = reinterpret_cast<double *>(p); p += arena_padded(b_y);
-    double *d_out = reinterpret_cast<double *>(p); p += arena_padded(b_out);
-    void *d_ws = b_ws ? p : nullptr;
-    HTRY(hipMemcpyAsync(d_y, y, b_y, hipMemcpyHostToDevice, stream));
-    rc = seqik_resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, flags, max_gap, d_out, n_out, d_ws,
-                                     stream);
-    if (rc != SEQIK_OK) { (void)hipStreamSynchronize(stream); return rc; }
-    HTRY(hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, stream));
-    HTRY(hipStreamSynchronize(stream));
-    return SEQIK_OK;
+    const size_t n_rows = (size_t)width * (size_t)n_chains;
+    seqik::HostCall call;
+    double *d_y, *d_out;
+    char *d_ws;
+    call.upload(d_y, n_rows * (size_t)n_frames, y);
+    call.download(d_out, n_rows * (size_t)n_out, out);
+    call.scratch(d_ws, seqik_resample_workspace_bytes(n_chains, n_frames, flags));
+    if ((rc = call.begin(device)) != SEQIK_OK) return rc;
+    return call.finish(seqik_resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, flags, max_gap, d_out,
+                                                   n_out, d_ws, call.stream()));
 }
 
 }  // extern "C"

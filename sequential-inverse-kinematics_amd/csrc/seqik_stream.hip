@@ -24,31 +24,15 @@
 // slab k + 1 is warm-started from the last frame of slab k (kept on the device, no host round
 // trip), exactly as the reference's frame loop would have continued (:272).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <string.h>
 #include <new>
 #include <vector>
 
-#include "../../include/seqik.h"
-#include "seqik_device_scope.hpp"
-
-extern "C" void seqik_set_error(int code, const char *msg);
+#include "seqik_runtime.hpp"
 
 namespace {
 
-int s_fail(int code, const char *what, const char *detail = "")
-{
-    char buf[384];
-    snprintf(buf, sizeof(buf), "%s%s%s", what, detail[0] ? ": " : "", detail);
-    seqik_set_error(code, buf);
-    return code;
-}
-
-#define STRY(expr)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) return s_fail(SEQIK_ERR_HIP, #expr, hipGetErrorString(e_)); \
-    } while (0)
+using seqik::bad_arg;
 
 // last-frame joint angles of every chain -> init block [chain][7] of the next slab
 __global__ void __launch_bounds__(256) seqik_carry_kernel(const double *angles, double *init, int64_t n_chains,
@@ -115,30 +99,30 @@ void destroy(SeqikStream *s)
 int open_impl(SeqikStream *s)
 {
     seqik::DeviceScope scope;
-    STRY(seqik::resolve_device(s->device, &s->device));
-    STRY(scope.enter(s->device));
-    STRY(hipStreamCreateWithFlags(&s->h2d, hipStreamNonBlocking));
+    HIP_TRY(seqik::resolve_device(s->device, &s->device));
+    HIP_TRY(scope.enter(s->device));
+    HIP_TRY(hipStreamCreateWithFlags(&s->h2d, hipStreamNonBlocking));
     // carried slabs depend on each other: one in-order stream.  Otherwise one compute stream per slot, up to three
     // (10 M frames x 6 legs with FK: 1 stream 0.47 s, 2 0.40 s, 3 0.38 s; without FK 2 0.26 s, 3 0.24 s).  That is
     // five streams with the copies: they only overlap on separate hardware queues, i.e. with GPU_MAX_HW_QUEUES >= 8
     // (HIP's default of 4 made the third compute stream a loss: 1.48e8 -> 1.19e8 leg-frames/s).
     s->n_compute = s->carry ? 1 : (int)(s->slots.size() < 3 ? s->slots.size() : 3);
-    for (int i = 0; i < s->n_compute; ++i) STRY(hipStreamCreateWithFlags(&s->compute[i], hipStreamNonBlocking));
-    STRY(hipStreamCreateWithFlags(&s->d2h, hipStreamNonBlocking));
+    for (int i = 0; i < s->n_compute; ++i) HIP_TRY(hipStreamCreateWithFlags(&s->compute[i], hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&s->d2h, hipStreamNonBlocking));
     const size_t lf = (size_t)s->slab_seq * s->n_legs * s->n_frames;
     // a custom layout may pad a chain's block (chain stride > dense size): the slots hold whole chain blocks
     const size_t n_ch = (size_t)s->slab_seq * s->n_legs;
     const size_t pose_elems = s->have_layout ? (size_t)s->layout.pose_chain * n_ch : 15 * lf;
     const size_t ang_elems = s->have_layout ? (size_t)s->layout.ang_chain * n_ch : 7 * lf;
     for (Slot &q : s->slots) {
-        STRY(hipMalloc(reinterpret_cast<void **>(&q.d_pose), sizeof(double) * pose_elems));
-        STRY(hipMalloc(reinterpret_cast<void **>(&q.d_angles), sizeof(double) * ang_elems));
-        if (s->want_fk) STRY(hipMalloc(reinterpret_cast<void **>(&q.d_fk), sizeof(double) * 27 * lf));
-        STRY(hipEventCreateWithFlags(&q.up, hipEventDisableTiming));
-        STRY(hipEventCreateWithFlags(&q.solved, hipEventDisableTiming));
-        STRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&q.d_pose), sizeof(double) * pose_elems));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&q.d_angles), sizeof(double) * ang_elems));
+        if (s->want_fk) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&q.d_fk), sizeof(double) * 27 * lf));
+        HIP_TRY(hipEventCreateWithFlags(&q.up, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&q.solved, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
     }
-    if (s->carry) STRY(hipMalloc(reinterpret_cast<void **>(&s->d_init), sizeof(double) * 7 * s->slab_seq * s->n_legs));
+    if (s->carry) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_init), sizeof(double) * 7 * s->slab_seq * s->n_legs));
     return SEQIK_OK;
 }
 
@@ -150,7 +134,7 @@ void *seqik_host_alloc(size_t bytes)
 {
     void *p = nullptr;
     if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-        s_fail(SEQIK_ERR_HIP, "hipHostMalloc failed");
+        (void)seqik::fail(SEQIK_ERR_HIP, "hipHostMalloc failed%s");
         return nullptr;
     }
     return p;
@@ -163,15 +147,15 @@ void seqik_host_free(void *p)
 
 int seqik_host_register(void *p, size_t bytes)
 {
-    if (!p) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_host_register: null pointer");
-    STRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
+    if (!p) return bad_arg("seqik_host_register", "null pointer");
+    HIP_TRY(hipHostRegister(p, bytes, hipHostRegisterDefault));
     return SEQIK_OK;
 }
 
 int seqik_host_unregister(void *p)
 {
-    if (!p) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_host_unregister: null pointer");
-    STRY(hipHostUnregister(p));
+    if (!p) return bad_arg("seqik_host_unregister", "null pointer");
+    HIP_TRY(hipHostUnregister(p));
     return SEQIK_OK;
 }
 
@@ -179,14 +163,14 @@ int seqik_stream_open(SeqikStream **out, int32_t n_legs, const SeqikLegParams *l
                       int64_t slab_seq, int64_t n_frames, const SeqikLayout *layout, int32_t want_fk,
                       int32_t n_slots, int32_t carry, int32_t generic, const SeqikOptions *opt)
 {
-    if (!out) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_open: null handle pointer");
+    if (!out) return bad_arg("seqik_stream_open", "null handle pointer");
     *out = nullptr;
     if (!legs || n_legs <= 0 || n_legs > 8 || slab_seq <= 0 || n_frames <= 0 || n_slots < 1 || n_slots > 16)
-        return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_open: bad sizes (n_legs 1..8, slab_seq > 0, n_frames > 0, n_slots 1..16)");
+        return bad_arg("seqik_stream_open", "bad sizes (n_legs 1..8, slab_seq > 0, n_frames > 0, n_slots 1..16)");
     int rc = generic ? seqik_validate_legs_generic(legs, n_legs) : seqik_validate_legs(legs, n_legs, 1, 4);
     if (rc != SEQIK_OK) return rc;
     SeqikStream *s = new (std::nothrow) SeqikStream;
-    if (!s) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_open: out of host memory");
+    if (!s) return bad_arg("seqik_stream_open", "out of host memory");
     s->device = opt ? opt->device : -1;  // resolved to the current device in open_impl
     s->n_legs = n_legs; s->slab_seq = slab_seq; s->n_frames = n_frames;
     s->want_fk = want_fk != 0; s->carry = carry != 0; s->generic = generic != 0;
@@ -201,7 +185,7 @@ int seqik_stream_open(SeqikStream **out, int32_t n_legs, const SeqikLegParams *l
                         6 * layout->ang_dof + (T - 1) * layout->ang_frame + 1 <= layout->ang_chain;
         if (!ok) {
             delete s;
-            return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_open: layout strides must be positive and every key point / "
+            return bad_arg("seqik_stream_open", "layout strides must be positive and every key point / "
                                               "angle of a chain must lie inside its chain stride");
         }
         s->layout = *layout;
@@ -221,28 +205,28 @@ int seqik_stream_open(SeqikStream **out, int32_t n_legs, const SeqikLegParams *l
 
 int seqik_stream_submit(SeqikStream *s, const double *pose, int64_t n_seq, double *angles, double *fk)
 {
-    if (!s || !pose || !angles) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_submit: null pointer");
-    if (n_seq < 0 || n_seq > s->slab_seq) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_submit: n_seq exceeds the slab size");
-    if (s->want_fk && !fk) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_submit: the stream was opened with want_fk but fk is null");
+    if (!s || !pose || !angles) return bad_arg("seqik_stream_submit", "null pointer");
+    if (n_seq < 0 || n_seq > s->slab_seq) return bad_arg("seqik_stream_submit", "n_seq exceeds the slab size");
+    if (s->want_fk && !fk) return bad_arg("seqik_stream_submit", "the stream was opened with want_fk but fk is null");
     if (n_seq == 0) return SEQIK_OK;
     if (s->carry) {
         if (s->carry_seq >= 0 && s->carry_seq != n_seq)
-            return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_submit: a carried run needs the same n_seq in every slab");
+            return bad_arg("seqik_stream_submit", "a carried run needs the same n_seq in every slab");
         s->carry_seq = n_seq;
     }
     seqik::DeviceScope scope;
-    STRY(scope.enter(s->device));
+    HIP_TRY(scope.enter(s->device));
     Slot &q = s->slots[s->submitted % (int64_t)s->slots.size()];
-    if (q.in_flight) { STRY(hipEventSynchronize(q.done)); q.in_flight = false; }
+    if (q.in_flight) { HIP_TRY(hipEventSynchronize(q.done)); q.in_flight = false; }
     const size_t lf = (size_t)n_seq * s->n_legs * s->n_frames;
     // a custom layout may leave gaps only inside a chain block (chain stride >= dense size), so the
     // slab is copied as the contiguous block of n_seq * n_legs chains in either case
     const size_t pose_elems = s->have_layout ? (size_t)s->layout.pose_chain * n_seq * s->n_legs : 15 * lf;
     const size_t ang_elems = s->have_layout ? (size_t)s->layout.ang_chain * n_seq * s->n_legs : 7 * lf;
-    STRY(hipMemcpyAsync(q.d_pose, pose, sizeof(double) * pose_elems, hipMemcpyHostToDevice, s->h2d));
-    STRY(hipEventRecord(q.up, s->h2d));
+    HIP_TRY(hipMemcpyAsync(q.d_pose, pose, sizeof(double) * pose_elems, hipMemcpyHostToDevice, s->h2d));
+    HIP_TRY(hipEventRecord(q.up, s->h2d));
     hipStream_t compute = s->compute[s->submitted % s->n_compute];
-    STRY(hipStreamWaitEvent(compute, q.up, 0));
+    HIP_TRY(hipStreamWaitEvent(compute, q.up, 0));
     const SeqikLayout *lay = s->have_layout ? &s->layout : nullptr;
     const SeqikAffine *aff = s->affine.empty() ? nullptr : s->affine.data();
     const double *d_init = (s->carry && s->have_init) ? s->d_init : nullptr;
@@ -260,14 +244,14 @@ int seqik_stream_submit(SeqikStream *s, const double *pose, int64_t n_seq, doubl
         const unsigned blocks = (unsigned)((n_chains * 7 + 255) / 256);
         hipLaunchKernelGGL(seqik_carry_kernel, dim3(blocks), dim3(256), 0, compute, q.d_angles, s->d_init, n_chains,
                            s->n_frames, ac, ad, af);
-        STRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         s->have_init = true;
     }
-    STRY(hipEventRecord(q.solved, compute));
-    STRY(hipStreamWaitEvent(s->d2h, q.solved, 0));
-    STRY(hipMemcpyAsync(angles, q.d_angles, sizeof(double) * ang_elems, hipMemcpyDeviceToHost, s->d2h));
-    if (s->want_fk) STRY(hipMemcpyAsync(fk, q.d_fk, sizeof(double) * 27 * lf, hipMemcpyDeviceToHost, s->d2h));
-    STRY(hipEventRecord(q.done, s->d2h));
+    HIP_TRY(hipEventRecord(q.solved, compute));
+    HIP_TRY(hipStreamWaitEvent(s->d2h, q.solved, 0));
+    HIP_TRY(hipMemcpyAsync(angles, q.d_angles, sizeof(double) * ang_elems, hipMemcpyDeviceToHost, s->d2h));
+    if (s->want_fk) HIP_TRY(hipMemcpyAsync(fk, q.d_fk, sizeof(double) * 27 * lf, hipMemcpyDeviceToHost, s->d2h));
+    HIP_TRY(hipEventRecord(q.done, s->d2h));
     q.in_flight = true;
     s->submitted += 1;
     return SEQIK_OK;
@@ -275,11 +259,11 @@ int seqik_stream_submit(SeqikStream *s, const double *pose, int64_t n_seq, doubl
 
 int seqik_stream_wait(SeqikStream *s)
 {
-    if (!s) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_wait: null handle");
+    if (!s) return bad_arg("seqik_stream_wait", "null handle");
     seqik::DeviceScope scope;
-    STRY(scope.enter(s->device));
+    HIP_TRY(scope.enter(s->device));
     for (Slot &q : s->slots)
-        if (q.in_flight) { STRY(hipEventSynchronize(q.done)); q.in_flight = false; }
+        if (q.in_flight) { HIP_TRY(hipEventSynchronize(q.done)); q.in_flight = false; }
     // every slab is back: a watchdog fault in one of them must not pass silently (this pipeline's own streams only)
     int rc = SEQIK_OK;
     for (int i = 0; i < s->n_compute; ++i) {
@@ -291,7 +275,7 @@ int seqik_stream_wait(SeqikStream *s)
 
 int seqik_stream_reset_carry(SeqikStream *s)
 {
-    if (!s) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_reset_carry: null handle");
+    if (!s) return bad_arg("seqik_stream_reset_carry", "null handle");
     s->have_init = false;
     s->carry_seq = -1;
     return SEQIK_OK;
@@ -299,15 +283,15 @@ int seqik_stream_reset_carry(SeqikStream *s)
 
 int seqik_stream_set_carry(SeqikStream *s, const double *init, int64_t n_seq, int32_t on_device)
 {
-    if (!s || !init) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_set_carry: null pointer");
-    if (!s->carry) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_set_carry: the stream was not opened with carry");
-    if (n_seq <= 0 || n_seq > s->slab_seq) return s_fail(SEQIK_ERR_BAD_ARG, "seqik_stream_set_carry: n_seq exceeds the slab size");
+    if (!s || !init) return bad_arg("seqik_stream_set_carry", "null pointer");
+    if (!s->carry) return bad_arg("seqik_stream_set_carry", "the stream was not opened with carry");
+    if (n_seq <= 0 || n_seq > s->slab_seq) return bad_arg("seqik_stream_set_carry", "n_seq exceeds the slab size");
     seqik::DeviceScope scope;
-    STRY(scope.enter(s->device));
+    HIP_TRY(scope.enter(s->device));
     // ordered on the compute stream: behind the slab before (whose carry kernel writes the same buffer), in front of the next
-    STRY(hipMemcpyAsync(s->d_init, init, sizeof(double) * 7 * n_seq * s->n_legs,
+    HIP_TRY(hipMemcpyAsync(s->d_init, init, sizeof(double) * 7 * n_seq * s->n_legs,
                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->compute[0]));
-    if (!on_device) STRY(hipStreamSynchronize(s->compute[0]));  // the caller's host buffer may go away
+    if (!on_device) HIP_TRY(hipStreamSynchronize(s->compute[0]));  // the caller's host buffer may go away
     s->have_init = true;
     s->carry_seq = n_seq;
     return SEQIK_OK;

@@ -22,12 +22,12 @@ _NATIVE = os.path.join(_PKG, "_native")
 _IN_TREE = not os.path.isfile(os.path.join(_NATIVE, "libseqik_hip.so")) and os.path.isfile(os.path.join(CSRC, "seqik_hip.hip"))
 _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
-SOURCES = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
-           "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
-           "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_hostctx.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
+SOURCES = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip",
+           "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
+           "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
            "seqik_resample.hpp"]
-COMPILE_UNITS = ["seqik_hip.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip", "seqik_fk.hip",
-                 "seqik_gaps.hip", "seqik_resample.hip"]
+COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
+                 "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
