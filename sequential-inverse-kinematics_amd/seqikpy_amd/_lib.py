@@ -25,9 +25,9 @@ LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so")
 SOURCES = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip",
            "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
            "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
-           "seqik_resample.hpp"]
+           "seqik_resample.hpp", "seqik_frames.hip", "seqik_frames.hpp"]
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
-                 "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip"]
+                 "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -354,6 +354,12 @@ def load():
                                                       ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _vp = ctypes.c_void_p
+        L.seqik_link_frames.restype = ctypes.c_int
+        L.seqik_link_frames.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                        ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _dp, _dp, ctypes.c_int32]
+        L.seqik_link_frames_device.restype = ctypes.c_int
+        L.seqik_link_frames_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                               ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _vp, _vp, _vp]
         L.seqik_gaps_compact_device.restype = ctypes.c_int
         L.seqik_gaps_compact_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                                 ctypes.POINTER(SeqikLegParams), _vp, _vp, _vp, _vp]
@@ -457,6 +463,57 @@ def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kin
                                                 int(n_frames), arr, _fk_kind(kind), ctypes.c_void_p(int(d_pose) or None),
                                                 ctypes.c_void_p(int(d_origin) or None), ctypes.c_void_p(int(d_fk) or None),
                                                 ctypes.c_void_p(int(d_dist) or None), ctypes.c_void_p(int(stream) or None))
+    if rc != SEQIK_OK:
+        _raise(rc)
+
+
+#: entry points of include/seqik_frames.h (link frames from joint angles), kept apart from the ABI-7 set of seqik.h
+FRAMES_EXPORTED_SYMBOLS = ["seqik_link_frames", "seqik_link_frames_device"]
+
+
+def link_frames(angles, legs, kind="seq", origin=None, device=-1, rows3=False):
+    """``seqik_link_frames`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(frames (S, L, N, 9, 4, 4)),
+    the 4 x 4 frame of each of the nine links of the whole-leg chain in the chain's base frame -- what IKPy's
+    ``Chain.forward_kinematics(q, full_kinematics=True)`` returns, for every leg-frame of the batch.
+
+    ``kind``: ``"seq"`` (links base, ThC_yaw, ThC_pitch, ThC_roll, CTr_pitch, CTr_roll, FTi_pitch, TiTa_pitch, Claw) or
+    ``"generic"`` (base, ThC_roll, ThC_yaw, ThC_pitch, ...).  ``origin``: anything that broadcasts to (S, L, N, 3), added to
+    the translation column only; absent = leg-local frames.  The translation columns equal ``forward_kinematics``' rows
+    for the same angles, kind and origin bit for bit.  ``rows3=True`` returns the (S, L, N, 9, 3, 4) array as the library
+    wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  A non-finite angle makes that leg-frame's
+    frames NaN (with ``rows3=False`` the fourth row too)."""
+    angles = np.ascontiguousarray(angles, dtype=np.float64)
+    if angles.ndim != 4 or angles.shape[3] != 7:
+        raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
+    S, L, N = angles.shape[:3]
+    if len(legs) != L:
+        raise ValueError("one SeqikLegParams per leg expected")
+    k = _fk_kind(kind)
+    if origin is not None:
+        origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64), (S, L, N, 3)))
+    rows = np.full((S, L, N, 9, 3, 4), np.nan)
+    rc = load().seqik_link_frames(angles.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs), k,
+                                  origin.ctypes.data_as(_dp) if origin is not None else None,
+                                  rows.ctypes.data_as(_dp), int(device))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    if rows3:
+        return dict(frames=rows)
+    frames = np.empty((S, L, N, 9, 4, 4))
+    frames[..., :3, :] = rows
+    frames[..., 3, :] = (0.0, 0.0, 0.0, 1.0)
+    frames[..., 3, :][np.isnan(rows[..., 0, 0])] = np.nan
+    return dict(frames=frames)
+
+
+def link_frames_device(d_angles, n_seq, n_legs, n_frames, legs, d_frames, kind="seq", d_origin=0, stream=None):
+    """``seqik_link_frames_device``: raw device pointers (ints) in the dense layouts of ``include/seqik_frames.h``
+    (``d_frames``: (S, L, N, 9, 3, 4) doubles), asynchronous on ``stream`` (a hipStream_t as int; None / 0 = the default
+    stream) of the current device."""
+    arr = (SeqikLegParams * n_legs)(*legs)
+    rc = load().seqik_link_frames_device(ctypes.c_void_p(int(d_angles) or None), int(n_seq), int(n_legs), int(n_frames),
+                                         arr, _fk_kind(kind), ctypes.c_void_p(int(d_origin) or None),
+                                         ctypes.c_void_p(int(d_frames) or None), ctypes.c_void_p(int(stream or 0) or None))
     if rc != SEQIK_OK:
         _raise(rc)
 

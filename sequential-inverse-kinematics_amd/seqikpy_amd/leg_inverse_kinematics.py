@@ -17,35 +17,11 @@ import numpy as np
 
 from . import _lib
 from .data import DOFS, INITIAL_ANGLES, SEGMENTS
-from .kinematic_chain import Chain, KinematicChainBase, KinematicChainGeneric, KinematicChainSeq, LEG_NAMES
+from .kinematic_chain import (Chain, KinematicChainBase, KinematicChainGeneric, KinematicChainSeq, LEG_NAMES, STAGE_DOFS,
+                              STAGE_LINKS)
 from .utils import save_file
 
 logging.basicConfig(format=" %(asctime)s - %(levelname)s- %(message)s", handlers=[logging.StreamHandler()])
-
-#: joints stored by each stage (leg_inverse_kinematics.py:285-320)
-STAGE_DOFS = {1: ["ThC_yaw", "ThC_pitch"], 2: ["ThC_roll", "CTr_pitch"], 3: ["CTr_roll", "FTi_pitch"],
-              4: ["TiTa_pitch"]}
-STAGE_LINKS = {1: 4, 2: 6, 3: 8, 4: 9}
-
-
-def _rot(axis, a):
-    c, s = np.cos(a), np.sin(a)
-    x, y, z = axis
-    return np.array([[x * x + (1 - x * x) * c, x * y * (1 - c) - z * s, x * z * (1 - c) + y * s],
-                     [x * y * (1 - c) + z * s, y * y + (1 - y * y) * c, y * z * (1 - c) - x * s],
-                     [x * z * (1 - c) - y * s, y * z * (1 - c) + x * s, z * z + (1 - z * z) * c]])
-
-
-def _link_matrix(link, theta):
-    m = np.eye(4)
-    m[:3, 3] = link.origin_translation
-    r, p, y = link.origin_orientation
-    m[:3, :3] = _rot((0, 0, 1), y) @ _rot((0, 1, 0), p) @ _rot((1, 0, 0), r)
-    if link.has_rotation:
-        h = np.eye(4)
-        h[:3, :3] = _rot(tuple(link.rotation), theta)
-        m = m @ h
-    return m
 
 
 class LegInvKinBase(ABC):
@@ -80,76 +56,17 @@ class LegInvKinBase(ABC):
 
         One single-frame, single-stage launch of the HIP solver (the batched entry points are
         the fast path; this seam exists for API compatibility)."""
-        spec = kinematic_chain.spec
-        if spec.get("kind") == "generic":
-            return self._calculate_ik_generic(kinematic_chain, target_pos, initial_angles)
-        if spec.get("kind") != "seq":
-            raise ValueError("calculate_ik needs a chain made by KinematicChainSeq / KinematicChainGeneric")
-        stage, leg, factory = spec["stage"], spec["leg"], spec["factory"]
-        n = STAGE_LINKS[stage]
-        x0 = np.zeros(n) if initial_angles is None else np.asarray(initial_angles, dtype=np.float64)
-        if x0.shape != (n,):
-            raise ValueError(f"Your joints vector length is {x0.size} but you have {n} links")
-        seeds = {leg: {f"stage_{k}": np.zeros(STAGE_LINKS[k]) for k in (1, 2, 3, 4)}}
-        seeds[leg][f"stage_{stage}"] = x0
-        lp = _lib.make_leg_params(leg, factory.bounds_dof, factory.body_size, seeds)
-        pose = np.zeros((1, 1, 1, 5, 3))
-        pose[0, 0, 0, stage] = np.asarray(target_pos, dtype=np.float64)
-        angles = np.zeros((1, 1, 1, 7))
-        if spec["prior_angles"] is not None:
-            angles[0, 0, 0] = spec["prior_angles"]
-        out = _lib.solve_seq(pose, [lp], stage, stage, angles=angles, want_fk=False, device=self.device)
-        res = x0.copy()
-        lo = np.array([l.bounds[0] for l in kinematic_chain.links])
-        hi = np.array([l.bounds[1] for l in kinematic_chain.links])
-        # scipy shifts start entries that sit on a bound inwards by 1e-10 * max(1, |bound|)
-        with np.errstate(invalid="ignore"):  # the base link is unbounded (-inf, inf)
-            near_lo = np.isfinite(lo) & (res - lo <= np.minimum(hi - res, 1e-10 * np.maximum(1, np.abs(lo))))
-            near_hi = np.isfinite(hi) & (hi - res <= np.minimum(res - lo, 1e-10 * np.maximum(1, np.abs(hi))))
-            res[near_lo] = (lo + 1e-10 * np.maximum(1, np.abs(lo)))[near_lo]
-            res[near_hi] = (hi - 1e-10 * np.maximum(1, np.abs(hi)))[near_hi]
-        names = [l.name for l in kinematic_chain.links]
-        for dof in STAGE_DOFS[stage]:
-            res[names.index(f"{leg}_{dof}")] = out["angles"][0, 0, 0, DOFS.index(dof)]
-        return res
-
-    def _calculate_ik_generic(self, kinematic_chain: Chain, target_pos, initial_angles) -> np.ndarray:
-        """Per-frame seam for the 9-link generic chain (reference :62-69 works with any chain): one single-frame
-        launch of ``seqik_solve_generic``; returns the 9 link variables (base and claw keep their start values, made
-        strictly feasible as scipy does)."""
-        spec = kinematic_chain.spec
-        leg, factory = spec["leg"], spec["factory"]
-        x0 = np.zeros(9) if initial_angles is None else np.asarray(initial_angles, dtype=np.float64)
-        if x0.shape != (9,):
-            raise ValueError(f"Your joints vector length is {x0.size} but you have 9 links")
-        seeds = {leg: {f"stage_{k}": np.zeros(STAGE_LINKS[k]) for k in (1, 2, 3)}}
-        seeds[leg]["stage_4"] = x0
-        lp = _lib.make_leg_params(leg, factory.bounds_dof, factory.body_size, seeds)
-        pose = np.zeros((1, 1, 1, 5, 3))
-        pose[0, 0, 0, 4] = np.asarray(target_pos, dtype=np.float64)
-        out = _lib.solve_generic(pose, [lp], want_fk=False, device=self.device)
-        res = x0.copy()
-        lo = np.array([l.bounds[0] for l in kinematic_chain.links])
-        hi = np.array([l.bounds[1] for l in kinematic_chain.links])
-        with np.errstate(invalid="ignore"):  # the base link is unbounded (-inf, inf)
-            near_lo = np.isfinite(lo) & (res - lo <= np.minimum(hi - res, 1e-10 * np.maximum(1, np.abs(lo))))
-            near_hi = np.isfinite(hi) & (hi - res <= np.minimum(res - lo, 1e-10 * np.maximum(1, np.abs(hi))))
-            res[near_lo] = (lo + 1e-10 * np.maximum(1, np.abs(lo)))[near_lo]
-            res[near_hi] = (hi - 1e-10 * np.maximum(1, np.abs(hi)))[near_hi]
-        names = [l.name for l in kinematic_chain.links]
-        for d, dof in enumerate(DOFS):
-            res[names.index(f"{leg}_{dof}")] = out["angles"][0, 0, 0, d]
-        return res
+        return kinematic_chain.inverse_kinematics(target_position=target_pos, initial_position=initial_angles,
+                                                  device=self.device if kinematic_chain.device < 0 else None)
 
     def calculate_fk(self, kinematic_chain: Chain, joint_angles: np.ndarray) -> np.ndarray:
         """Positions of every link frame of ``kinematic_chain`` at ``joint_angles`` (n_links, 3)."""
         if len(joint_angles) != len(kinematic_chain.links):
             raise ValueError(f"Your joints vector length is {len(joint_angles)} but you have "
                              f"{len(kinematic_chain.links)} links")
-        frame = np.eye(4)
+        frames = kinematic_chain.forward_kinematics(joint_angles, full_kinematics=True)
         out = np.zeros((len(kinematic_chain.links), 3))
-        for i, (link, theta) in enumerate(zip(kinematic_chain.links, joint_angles)):
-            frame = frame @ _link_matrix(link, theta)
+        for i, frame in enumerate(frames):
             out[i] = frame[:3, 3]
         return out
 
@@ -255,6 +172,27 @@ class LegInvKinBase(ABC):
         if export_path is not None:
             save_file(Path(export_path) / "forward_kinematics.pkl", out)
             self.logger.info("Forward kinematics are saved at %s", export_path)
+        return out
+
+    def run_link_frames(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, origin: Optional[np.ndarray] = None,
+                        export_path: Union[Path, str] = None) -> Dict[str, np.ndarray]:
+        """The 4 x 4 frame -- position and orientation -- of every link of every leg from joint angles alone, on the GPU
+        (``seqik_link_frames``): ``{segment_name: (N, 9, 4, 4)}`` in the order of ``aligned_pos``, per frame what the
+        reference's ``chain.forward_kinematics(q, full_kinematics=True)`` returns for the whole-leg chain of this class
+        (link order: ``_lib.link_frames``), with the origin added to the translation column.
+
+        ``joint_angles`` and ``origin`` default as in ``run_fk``; with the default origin the translation columns
+        ``[..., :3, 3]`` equal ``run_fk``'s rows bit for bit.  ``export_path``: writes ``link_frames.pkl`` there."""
+        out = {}
+        for items, angles, org in self._fk_batches(joint_angles, origin):
+            legs = [self._fk_leg_params(leg_name) for _, leg_name, _, _ in items]
+            frames = _lib.link_frames(angles, legs, kind=self._fk_kind, origin=org, device=self.device)["frames"]
+            for li, (segment_name, *_) in enumerate(items):
+                out[segment_name] = frames[0, li].copy()
+        out = {name: out[name] for name, _, _ in self._leg_segments()}
+        if export_path is not None:
+            save_file(Path(export_path) / "link_frames.pkl", out)
+            self.logger.info("Link frames are saved at %s", export_path)
         return out
 
     def fit_error(self, joint_angles: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
