@@ -55,6 +55,22 @@ inline int check_segments(const char *who, const SeqikLegParams *legs, int32_t n
     return SEQIK_OK;
 }
 
+// The argument rules of the head / antenna entry points that take RAW key points (seqik_head_align.hip); the same rules
+// as seqik_head_angles_ex: one neck or one per frame, at least one key point per side, two for the antenna angles.
+inline int check_head_args(const char *who, const void *r_head, const void *l_head, const void *neck, const void *angles,
+                           const void *affine, int64_t n_frames, int64_t neck_stride, int32_t n_points, int32_t compute_ant)
+{
+    if (!r_head || !l_head || !neck || !angles || !affine) return bad_arg(who, "null pointer");
+    if (n_frames < 0 || n_frames > INT64_MAX / (8 * 3 * (int64_t)(n_points > 0 ? n_points : 1)))
+        return bad_arg(who, "n_frames is negative or too large");
+    if (neck_stride != 0 && neck_stride != 3) return bad_arg(who, "neck_stride must be 0 or 3");
+    if (n_points < 1) return bad_arg(who, "n_points must be at least 1");
+    if (compute_ant && n_points < 2)
+        return bad_arg(who, "the antenna angles need two key points per side (antenna base and tip); pass "
+                            "compute_ant = 0 for single-point records");
+    return SEQIK_OK;
+}
+
 // Tiles of F = 64 k frames of one chain for the one-wavefront-per-tile passes (seqik_gaps.hip, seqik_resample.hip): k = 1
 // unless a chain has more than 65 536 frames, then as small as keeps a chain at <= kMaxTiles tiles (their scan kernels
 // hold a chain's tiles in 16 rows of 64 lanes).

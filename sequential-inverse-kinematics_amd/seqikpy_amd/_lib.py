@@ -25,9 +25,10 @@ LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so")
 SOURCES = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip",
            "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
            "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
-           "seqik_resample.hpp", "seqik_frames.hip", "seqik_frames.hpp"]
+           "seqik_resample.hpp", "seqik_frames.hip", "seqik_frames.hpp", "seqik_head_align.hip", "seqik_head_align.hpp"]
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
-                 "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip"]
+                 "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
+                 "seqik_head_align.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -141,6 +142,21 @@ def make_affine(fixed_coxa, scale, template_coxa) -> SeqikAffine:
         a.fixed_coxa[i] = float(fixed_coxa[i])
         a.template_coxa[i] = float(template_coxa[i])
     a.scale = float(scale)
+    return a
+
+
+class SeqikHeadAffine(ctypes.Structure):
+    """Mirror of ``struct SeqikHeadAffine`` (include/seqik_head_align.h): fused AlignPose.align_head of one side."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("scale_base", ctypes.c_double), ("scale_tip", ctypes.c_double),
+                ("template_base", ctypes.c_double * 3)]
+
+
+def make_head_affine(origin, scale_base, scale_tip, template_base) -> SeqikHeadAffine:
+    a = SeqikHeadAffine()
+    for i in range(3):
+        a.origin[i] = float(origin[i])
+        a.template_base[i] = float(template_base[i])
+    a.scale_base, a.scale_tip = float(scale_base), float(scale_tip)
     return a
 
 
@@ -387,6 +403,25 @@ def load():
         L.seqik_resample_pchip_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
                                                   ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int64,
                                                   _vp, _vp]
+        _i64p = ctypes.POINTER(ctypes.c_int64)
+        L.seqik_head_align_stats_open.restype = ctypes.c_int
+        L.seqik_head_align_stats_open.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64,
+                                                  ctypes.POINTER(SeqikOptions)]
+        L.seqik_head_align_stats_select.restype = ctypes.c_int
+        L.seqik_head_align_stats_select.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_double, _i64p, _i64p]
+        L.seqik_head_align_stats_pick.restype = ctypes.c_int
+        L.seqik_head_align_stats_pick.argtypes = [_vp, _i64p, _i64p, ctypes.c_int32, _dp]
+        L.seqik_head_align_stats_close.restype = ctypes.c_int
+        L.seqik_head_align_stats_close.argtypes = [_vp]
+        L.seqik_head_angles_raw.restype = ctypes.c_int
+        L.seqik_head_angles_raw.argtypes = [_dp, _dp, ctypes.c_int64, ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(SeqikHeadAffine), _dp,
+                                            _dp, _dp, ctypes.POINTER(SeqikOptions)]
+        L.seqik_head_angles_raw_device.restype = ctypes.c_int
+        L.seqik_head_angles_raw_device.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                   ctypes.c_double, ctypes.c_double, ctypes.c_int32, _vp,
+                                                   ctypes.POINTER(SeqikHeadAffine), _vp, _vp, _vp, _vp]
         _lib = L
         return _lib
 
@@ -713,6 +748,136 @@ def resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d
     if rc != SEQIK_OK:
         _raise(rc)
     return n_out
+
+
+#: entry points of include/seqik_head_align.h (antenna alignment on the GPU), kept apart from the ABI-7 set of seqik.h
+HEAD_ALIGN_EXPORTED_SYMBOLS = ["seqik_head_align_stats_open", "seqik_head_align_stats_select",
+                               "seqik_head_align_stats_pick", "seqik_head_align_stats_close", "seqik_head_angles_raw",
+                               "seqik_head_angles_raw_device"]
+#: what the antenna-alignment kernels are compiled from (``csrc_sha256(HEAD_ALIGN_SOURCES)`` ties
+#: profiles/head_align.json to a build; ``KERNEL_SOURCES`` stays the solver's own set)
+HEAD_ALIGN_SOURCES = ["seqik_head.hpp", "seqik_head_align.hpp", "seqik_head_align.hip"]
+HEAD_STAT_THRESHOLD = 5e-5
+
+
+def _head_arrays(r_head, l_head, min_points=1):
+    r_head = np.ascontiguousarray(r_head, dtype=np.float64)
+    l_head = np.ascontiguousarray(l_head, dtype=np.float64)
+    if r_head.ndim != 3 or r_head.shape[2] != 3 or r_head.shape[1] < min_points or l_head.shape != r_head.shape:
+        raise ValueError(f"R_head / L_head must have the same shape (N, key points >= {min_points}, 3)")
+    return r_head, l_head
+
+
+def head_align_stats(r_head, l_head, thorax, ranks_for, threshold=HEAD_STAT_THRESHOLD, device=-1):
+    """``seqik_head_align_stats_*`` on host arrays: the order statistics AlignPose.align_head reduces, from RAW key
+    points.  ``r_head`` / ``l_head`` (N, K >= 2, 3), ``thorax`` (N, P, 3) (points 0 and last are read), N >= 3.
+
+    ``ranks_for(n) -> sequence of ranks`` is called once per side with that side's number of stationary frames and once
+    with N (the ranks depend on sizes that are only known after the selection).  Returns dict(n_stat (2,) int64 for R, L;
+    n_nonfinite; order): ``order`` (2, 5, n_ranks) holds per side the order statistics of base x, y, z and the
+    base-to-thorax distance over the stationary frames and of the antenna length over all frames -- or None when the
+    input held non-finite values or a side selected no frame (nothing is sorted then)."""
+    r_head, l_head = _head_arrays(r_head, l_head, 2)
+    n = r_head.shape[0]
+    thorax = np.ascontiguousarray(thorax, dtype=np.float64)
+    if thorax.ndim != 3 or thorax.shape[0] != n or thorax.shape[1] < 1 or thorax.shape[2] != 3:
+        raise ValueError(f"Thorax must have shape ({n}, key points, 3), got {thorax.shape}")
+    if n < 3:
+        raise ValueError(f"the stationary-frame test needs at least 3 frames, got {n}")
+    lib = load()
+    h = ctypes.c_void_p()
+    opt = SeqikOptions()
+    opt.device = device
+    rc = lib.seqik_head_align_stats_open(ctypes.byref(h), n, ctypes.byref(opt))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    try:
+        n_stat = np.zeros(2, dtype=np.int64)
+        bad = ctypes.c_int64(0)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        rc = lib.seqik_head_align_stats_select(h, r_head.ctypes.data, l_head.ctypes.data, thorax.ctypes.data, 0, n,
+                                               r_head.shape[1], thorax.shape[1], float(threshold),
+                                               n_stat.ctypes.data_as(i64p), ctypes.byref(bad))
+        if rc != SEQIK_OK:
+            _raise(rc)
+        out = dict(n_stat=n_stat, n_nonfinite=int(bad.value), order=None)
+        if bad.value or not n_stat.all():
+            return out
+        ranks_stat = np.ascontiguousarray([list(ranks_for(int(k))) for k in n_stat], dtype=np.int64)
+        ranks_all = np.ascontiguousarray(list(ranks_for(n)), dtype=np.int64)
+        if ranks_stat.ndim != 2 or ranks_stat.shape[1] != ranks_all.shape[0]:
+            raise ValueError("ranks_for must return the same number of ranks for every size")
+        order = np.zeros((2, 5, ranks_all.shape[0]))
+        rc = lib.seqik_head_align_stats_pick(h, ranks_stat.ctypes.data_as(i64p), ranks_all.ctypes.data_as(i64p),
+                                             ranks_all.shape[0], order.ctypes.data_as(_dp))
+        if rc != SEQIK_OK:
+            _raise(rc)
+        out["order"] = order
+        return out
+    finally:
+        lib.seqik_head_align_stats_close(h)
+
+
+def _head_affine_pair(affine):
+    """(R, L) -> ``SeqikHeadAffine[2]``; each a ``SeqikHeadAffine`` or the tuple ``AlignPose.head_affine`` returns."""
+    if isinstance(affine, dict):
+        affine = (affine["R"], affine["L"])
+    if len(affine) != 2:
+        raise ValueError("two head affines expected: R, then L")
+    return (SeqikHeadAffine * 2)(*[a if isinstance(a, SeqikHeadAffine) else make_head_affine(*a) for a in affine])
+
+
+def head_angles_raw(r_head, l_head, neck, rest_head_pitch, rest_antenna_pitch, affine, compute_ant=True, device=-1,
+                    head_roll=None, want_aligned=False):
+    """``seqik_head_angles_raw`` on host arrays: ``head_angles`` on RAW key points, with the map of
+    ``AlignPose.align_head`` (``affine``: ``{"R": ..., "L": ...}`` or an (R, L) pair of ``AlignPose.head_affine`` tuples /
+    ``SeqikHeadAffine``) applied in the kernel's prologue.  Returns the (7 or 3, N) angles -- the bits ``head_angles``
+    gives on the host-aligned points -- or, with ``want_aligned``, ``(angles, r_aligned, l_aligned)`` with the aligned
+    key points (N, min(K, 2), 3)."""
+    r_head, l_head = _head_arrays(r_head, l_head)
+    n, k = r_head.shape[:2]
+    if compute_ant and k < 2:
+        raise IndexError(f"index 1 is out of bounds for axis 1 with size {k}: the antenna angles need the antenna base "
+                         "and tip; call compute_head_angles(compute_ant_angles=False)")
+    neck = np.ascontiguousarray(neck, dtype=np.float64).reshape(-1, 3)
+    if neck.shape[0] not in (1, n):
+        raise ValueError("Neck must hold one point or one point per frame")
+    stride = 3 if (neck.shape[0] == n and n > 1) else 0
+    roll_p = None
+    if head_roll is not None and compute_ant:
+        head_roll = np.ascontiguousarray(np.broadcast_to(np.asarray(head_roll, dtype=np.float64).reshape(-1), (n,)))
+        roll_p = head_roll.ctypes.data_as(_dp)
+    out = np.zeros((7 if compute_ant else 3, n))
+    r_al = np.zeros((n, min(k, 2), 3)) if want_aligned else None
+    l_al = np.zeros((n, min(k, 2), 3)) if want_aligned else None
+    opt = SeqikOptions()
+    opt.device = device
+    rc = load().seqik_head_angles_raw(r_head.ctypes.data_as(_dp), l_head.ctypes.data_as(_dp), n, k,
+                                      neck.ctypes.data_as(_dp), stride, float(rest_head_pitch), float(rest_antenna_pitch),
+                                      1 if compute_ant else 0, roll_p, _head_affine_pair(affine), out.ctypes.data_as(_dp),
+                                      r_al.ctypes.data_as(_dp) if want_aligned else None,
+                                      l_al.ctypes.data_as(_dp) if want_aligned else None, ctypes.byref(opt))
+    if rc != SEQIK_OK:
+        _raise(rc)
+    return (out, r_al, l_al) if want_aligned else out
+
+
+def head_angles_raw_device(d_r_head, d_l_head, n_frames, n_points, d_neck, neck_stride, rest_head_pitch,
+                           rest_antenna_pitch, affine, d_angles, compute_ant=True, d_head_roll=0, d_r_aligned=0,
+                           d_l_aligned=0, stream=0):
+    """``seqik_head_angles_raw_device``: raw device pointers (ints) or torch tensors -- RAW records (N, K, 3), neck (3,) or
+    (N, 3) by ``neck_stride`` 0 / 3, angles (7, N), optional aligned records (N, min(K, 2), 3) -- asynchronous on ``stream``
+    (a hipStream_t as int, or a torch stream) of the current device."""
+    n, k = int(n_frames), int(n_points)
+    al = (n, min(k, 2), 3)
+    rc = load().seqik_head_angles_raw_device(_ptr(d_r_head, "r_head", (n, k, 3)), _ptr(d_l_head, "l_head", (n, k, 3)), n, k,
+                                             _ptr(d_neck, "neck", (n if neck_stride else 1, 3)), int(neck_stride),
+                                             float(rest_head_pitch), float(rest_antenna_pitch), 1 if compute_ant else 0,
+                                             _ptr(d_head_roll, "head_roll", (n,)), _head_affine_pair(affine),
+                                             _ptr(d_angles, "angles", (7, n)), _ptr(d_r_aligned, "r_aligned", al),
+                                             _ptr(d_l_aligned, "l_aligned", al), _stream_ptr(stream))
+    if rc != SEQIK_OK:
+        _raise(rc)
 
 
 class AlignStats:

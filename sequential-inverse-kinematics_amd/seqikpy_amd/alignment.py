@@ -9,9 +9,9 @@ the host by ``align_pose()`` -- bit-identical to the reference -- or handed to t
 ``leg_affine()`` / ``LegInvKinSeq(..., leg_affine=...)`` so that RAW key points go straight to the
 GPU and the map is fused into the solve prologue (``include/seqik.h``: ``SeqikAffine``).
 
-Also here: the antenna alignment (``align_head``, host only -- it feeds the closed-form head kernel)
-and the three input converters (anipose, DeepFly3D, DeepFly3DPostProcessing -> the segment dictionary
-every class of this package consumes), reference ``seqikpy/alignment.py:103-226``.
+Also here: the antenna alignment (``align_head``; its constants ``head_affine`` / ``head_affines``, on the host or with
+the statistics taken on the GPU, feed the head kernel's fused map, ``include/seqik_head_align.h``) and the three
+input converters (anipose, DeepFly3D, DeepFly3DPostProcessing -> the segment dictionary every class of this package consumes), reference ``seqikpy/alignment.py:103-226``.
 """
 import logging
 from pathlib import Path
@@ -82,6 +82,31 @@ def linear_quantile_index(n: int, q: float) -> Tuple[int, int, float]:
     if vi < 0:
         lo = hi = 0
     return lo, hi, float(vi - np.floor(vi))
+
+
+def _order_mean_quantile(v4, gammas) -> float:
+    """Mean of two "linear" quantiles from their order statistics: ``v4`` = (previous, next) of the first quantile, then
+    of the second; ``gammas`` their interpolation weights (``linear_quantile_index``).  The interpolation restates
+    ``numpy.lib._function_base_impl._lerp``, so the value is ``_mean_quantile``'s bit for bit."""
+    vals = []
+    for j, g in enumerate(gammas):
+        a, b = v4[2 * j], v4[2 * j + 1]
+        diff = b - a
+        r = a + diff * g
+        if g >= 0.5:
+            r = b - diff * (1 - g)
+        vals.append(r)
+    return 0.5 * (vals[0] + vals[1])
+
+
+def _quantile_ranks(n: int):
+    """``(ranks, gammas)`` of the 0.45 and 0.55 quantiles of ``n`` values: previous and next index of each."""
+    ranks, gammas = [], []
+    for q in (0.5 - 0.05, 0.5 + 0.05):
+        lo, hi, gamma = linear_quantile_index(n, q)
+        ranks += [lo, hi]
+        gammas.append(gamma)
+    return ranks, gammas
 
 
 class AlignPose:
@@ -168,26 +193,13 @@ class AlignPose:
         if not np.isfinite(pose).all():
             # numpy's quantile of a series that holds a NaN is NaN; a radix sort would just push the NaN to the end
             return {seg[:2]: self.leg_affine(arr, seg[:2]) for seg, arr in segs}
-        qs = (0.5 - 0.05, 0.5 + 0.05)
-        ranks, gammas = [], []
-        for q in qs:
-            lo, hi, gamma = linear_quantile_index(n, q)
-            ranks += [lo, hi]
-            gammas.append(gamma)
+        ranks, gammas = _quantile_ranks(n)
         with _lib.AlignStats(len(segs), n, device=device) as st:
             st.add(pose)
             order = st.finish(ranks)                                                                  # (L, 7, 4)
 
         def mean_quantile(v4):
-            vals = []
-            for j, g in enumerate(gammas):  # numpy.lib._function_base_impl._lerp
-                a, b = v4[2 * j], v4[2 * j + 1]
-                diff = b - a
-                r = a + diff * g
-                if g >= 0.5:
-                    r = b - diff * (1 - g)
-                vals.append(r)
-            return 0.5 * (vals[0] + vals[1])
+            return _order_mean_quantile(v4, gammas)
 
         out = {}
         for li, (seg, _) in enumerate(segs):
@@ -219,24 +231,99 @@ class AlignPose:
         """Frames where the second difference of ``array`` is below ``threshold``."""
         return np.where(np.diff(np.diff(array)) < threshold)[0]
 
+    def _head_scales(self) -> Tuple[float, float]:
+        if not (self.body_size.get("Antenna_mid_thorax") and self.body_size.get("Antenna")):
+            raise KeyError("body_size must hold <Antenna_mid_thorax> and <Antenna>")
+        return self.body_size["Antenna_mid_thorax"], self.body_size["Antenna"]
+
+    def _check_head_input(self, n_frames: int) -> None:
+        if "Thorax" not in self.pose_data_dict:
+            raise ValueError("To align the head, you need to have a `Thorax` key point")
+        if n_frames < 3:
+            raise ValueError(f"To align the head, you need at least 3 frames (second difference), got {n_frames}")
+
+    def head_affine(self, head_array: np.ndarray, side: str,
+                    threshold: float = 5e-5) -> Tuple[np.ndarray, float, float, np.ndarray]:
+        """``(origin, scale_base, scale_tip, template_base)`` of one side -- the constants of ``align_head`` -- on the
+        host.  ``ValueError`` when ``Thorax`` is missing, for fewer than 3 frames, and when ``threshold`` selects no
+        stationary frame (the reference's quantile of an empty array fails obscurely there)."""
+        self._check_head_input(np.asarray(head_array).shape[0])
+        model_base, model_tip = self._head_scales()
+        base_to_thorax = np.linalg.norm(head_array[:, 0, :] - self.thorax_mid_pts, axis=1)
+        ant_len = np.linalg.norm(np.diff(head_array, axis=1), axis=2)[:, 0]
+        stat = self.find_stationary_indices(base_to_thorax, threshold)
+        if stat.size == 0:
+            raise ValueError(f"{side}_head: no stationary frame: the second difference of the antenna-base-to-thorax "
+                             f"distance is nowhere below the threshold {threshold!r}")
+        origin = AlignPose.get_fixed_pos(head_array[stat, 0, :])
+        scale_base = model_base / _mean_quantile(base_to_thorax[stat])
+        scale_tip = model_tip / _mean_quantile(ant_len)
+        self.logger.info("Scale factor antenna base %s: %s, ant itself: %s", side, scale_base, scale_tip)
+        return origin, float(scale_base), float(scale_tip), np.asarray(self.body_template[f"{side}_Antenna_base"],
+                                                                       dtype=np.float64)
+
+    def head_affines(self, on_gpu: bool = False, device: int = -1, threshold: float = 5e-5) -> Dict[str, tuple]:
+        """Constants of every ``*_head`` entry, keyed by side (``"R"``, ``"L"``), for the fused GPU path
+        (``HeadInverseKinematics.from_raw``, ``pipeline.run_body_ik(head_affine=...)``).
+
+        ``on_gpu=True`` (needs both sides) takes the whole-recording statistics on the MI355X
+        (``seqik_head_align_stats_*``): the stationary frames are selected and the ten series sorted there, the exact
+        order statistics come back and numpy's own interpolation is applied here, so the constants equal the host
+        path's bit for bit.  Non-finite input takes the host path (numpy's quantile of a series with a NaN is NaN, a
+        sort would just push it to the end), as ``leg_affines`` does."""
+        segs = [(seg, arr) for seg, arr in self.pose_data_dict.items() if "head" in seg]
+
+        def host():
+            return {seg[0]: self.head_affine(arr, seg[0], threshold) for seg, arr in segs}
+        if not on_gpu:
+            return host()
+        heads = {seg[0]: np.asarray(arr, dtype=np.float64) for seg, arr in segs}
+        if sorted(heads) != ["L", "R"]:
+            raise ValueError("on_gpu=True needs both R_head and L_head")
+        self._check_head_input(heads["R"].shape[0])
+        model_base, model_tip = self._head_scales()
+        from . import _lib
+        gam = {}
+
+        def ranks_for(n):
+            ranks, gam[n] = _quantile_ranks(n)
+            return ranks
+        res = _lib.head_align_stats(heads["R"], heads["L"], self.pose_data_dict["Thorax"], ranks_for,
+                                    threshold=threshold, device=device)
+        if res["n_nonfinite"]:
+            return host()
+        for i, side in enumerate("RL"):
+            if res["n_stat"][i] == 0:
+                raise ValueError(f"{side}_head: no stationary frame: the second difference of the antenna-base-to-thorax "
+                                 f"distance is nowhere below the threshold {threshold!r}")
+        out = {}
+        for seg, _ in segs:   # the dictionary's own order
+            side = seg[0]
+            order = res["order"]["RL".index(side)]
+            g_stat, g_all = gam[int(res["n_stat"]["RL".index(side)])], gam[heads[side].shape[0]]
+            origin = np.array([_order_mean_quantile(order[a], g_stat) for a in range(3)])
+            scale_base = model_base / _order_mean_quantile(order[3], g_stat)
+            scale_tip = model_tip / _order_mean_quantile(order[4], g_all)
+            self.logger.info("Scale factor antenna base %s: %s, ant itself: %s", side, scale_base, scale_tip)
+            out[side] = (origin, float(scale_base), float(scale_tip),
+                         np.asarray(self.body_template[f"{side}_Antenna_base"], dtype=np.float64))
+        return out
+
+    @staticmethod
+    def apply_head_affine(head_array: np.ndarray, affine: tuple) -> np.ndarray:
+        """The per-frame map of ``align_head`` with given constants: subtract, multiply, add (what the fused kernel does)."""
+        origin, scale_base, scale_tip, tmpl = affine
+        aligned = np.empty_like(head_array)
+        aligned[:, 0, :] = (head_array[:, 0, :] - origin) * scale_base + tmpl
+        if head_array.shape[1] > 1:
+            aligned[:, 1, :] = (head_array[:, 1, :] - origin) * scale_tip + tmpl
+        return aligned
+
     def align_head(self, head_array: np.ndarray, side: str) -> np.ndarray:
         """Scales / translates antenna base and tip to the template (reference :489-555): the base by the
         antenna-base-to-thorax distance, the tip by the antenna length, both about a fixed antenna origin
         estimated on the frames where that distance is stationary."""
-        base_to_thorax = np.linalg.norm(head_array[:, 0, :] - self.thorax_mid_pts, axis=1)
-        ant_len = np.linalg.norm(np.diff(head_array, axis=1), axis=2)[:, 0]
-        if not (self.body_size.get("Antenna_mid_thorax") and self.body_size.get("Antenna")):
-            raise KeyError("body_size must hold <Antenna_mid_thorax> and <Antenna>")
-        stat = self.find_stationary_indices(base_to_thorax)
-        origin = AlignPose.get_fixed_pos(head_array[stat, 0, :])
-        scale_base = self.body_size["Antenna_mid_thorax"] / _mean_quantile(base_to_thorax[stat])
-        scale_tip = self.body_size["Antenna"] / _mean_quantile(ant_len)
-        self.logger.info("Scale factor antenna base %s: %s, ant itself: %s", side, scale_base, scale_tip)
-        aligned = np.empty_like(head_array)
-        tmpl = self.body_template[f"{side}_Antenna_base"]
-        aligned[:, 0, :] = (head_array[:, 0, :] - origin) * scale_base + tmpl
-        aligned[:, 1, :] = (head_array[:, 1, :] - origin) * scale_tip + tmpl
-        return aligned
+        return AlignPose.apply_head_affine(head_array, self.head_affine(head_array, side))
 
     def align_pose(self, export_path: Optional[Union[str, Path]] = None) -> Dict[str, np.ndarray]:
         aligned_pose = {}

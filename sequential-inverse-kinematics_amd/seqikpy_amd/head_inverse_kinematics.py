@@ -66,6 +66,51 @@ class HeadInverseKinematics:
         self.logger.setLevel(getattr(logging, log_level.upper(), None))
         self.device = -1  # HIP device ordinal; -1 = the calling thread's current device
 
+    #: ``from_raw``: ``{"R": ..., "L": ...}`` constants of ``AlignPose.align_head``; None = ``aligned_pos`` is aligned
+    head_affine = None
+
+    @classmethod
+    def from_raw(cls, pose_data_dict: Dict[str, np.ndarray], body_template: Dict[str, np.ndarray],
+                 head_affine: Dict[str, tuple],
+                 log_level: Literal["DEBUG", "INFO", "WARNING", "ERROR"] = "INFO") -> "HeadInverseKinematics":
+        """From RAW key points (``R_head``, ``L_head`` of the un-aligned dictionary) and the constants of their alignment
+        (``AlignPose.head_affines()``): ``compute_head_angles`` and the per-quantity methods launch the kernel that applies
+        the map of ``AlignPose.align_head`` in its prologue, so no aligned copy is made or uploaded; the results are the
+        bits of the usual constructor on ``AlignPose.align_pose()``'s output.  ``aligned_pos`` (``R_head``, ``L_head`` and
+        the template's ``Neck``), and the array helpers that read it, are mapped on the host when first asked for, or
+        taken from the kernel by ``compute_head_angles``."""
+        if not all(key in pose_data_dict for key in ["R_head", "L_head"]):
+            raise ValueError("pose_data_dict must have R_head and L_head as keys")
+        if not all(side in head_affine for side in "RL"):
+            raise ValueError("head_affine must hold the constants of both sides, 'R' and 'L'")
+        self = cls.__new__(cls)
+        self.raw_pos = {k: np.ascontiguousarray(pose_data_dict[k], dtype=np.float64) for k in ("R_head", "L_head")}
+        self.head_affine = {side: head_affine[side] for side in "RL"}
+        self.body_template = body_template
+        self.rest_head_pitch = self.get_rest_head_pitch()
+        self.rest_antenna_pitch = self.get_rest_antenna_pitch()
+        self.logger = logging.getLogger(cls.__name__)
+        self.logger.setLevel(getattr(logging, log_level.upper(), None))
+        self.device = -1
+        return self
+
+    def _template_neck(self) -> np.ndarray:
+        return np.asarray(self.body_template["Neck"], dtype=np.float64).reshape((-1, 1, 3))
+
+    def __getattr__(self, name):
+        # (only reached for attributes that are not set) ``from_raw``: what depends on the aligned points is made on demand
+        if self.__dict__.get("head_affine") is not None:
+            if name == "aligned_pos":
+                from .alignment import AlignPose
+                self.aligned_pos = {k: AlignPose.apply_head_affine(self.raw_pos[k][:, :2], self.head_affine[k[0]])
+                                    for k in ("R_head", "L_head")}
+                self.aligned_pos["Neck"] = self._template_neck()
+                return self.aligned_pos
+            if name in ("head_vector_mid", "head_vector_horizontal"):
+                setattr(self, name, getattr(self, f"get_{name}")())
+                return self.__dict__[name]
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
     def get_rest_antenna_pitch(self) -> float:
         """Antenna pitch at the zero pose of the biomechanical model."""
         head = np.array(self.body_template["Neck"] - self.body_template["R_Antenna_base"], dtype=np.float64)
@@ -128,9 +173,23 @@ class HeadInverseKinematics:
         return _lib.signed_angles(v1, v2, rot_axis)
 
     def _rows(self, compute_ant: bool, head_roll=None) -> np.ndarray:
+        if self.head_affine is not None:
+            return self._rows_raw(compute_ant, head_roll)
         neck = np.asarray(self.aligned_pos["Neck"], dtype=np.float64)[:, 0, :]
         return _lib.head_angles(self.aligned_pos["R_head"], self.aligned_pos["L_head"], neck, self.rest_head_pitch,
                                 self.rest_antenna_pitch, compute_ant=compute_ant, device=self.device, head_roll=head_roll)
+
+    def _rows_raw(self, compute_ant: bool, head_roll=None) -> np.ndarray:
+        """``from_raw``: the fused kernel on the raw points; the aligned points it maps are kept as ``aligned_pos``
+        unless the host has made them already (same bits either way)."""
+        want = "aligned_pos" not in self.__dict__
+        res = _lib.head_angles_raw(self.raw_pos["R_head"], self.raw_pos["L_head"], self._template_neck()[:, 0, :],
+                                   self.rest_head_pitch, self.rest_antenna_pitch, self.head_affine,
+                                   compute_ant=compute_ant, device=self.device, head_roll=head_roll, want_aligned=want)
+        if not want:
+            return res
+        self.aligned_pos = {"R_head": res[1], "L_head": res[2], "Neck": self._template_neck()}
+        return res[0]
 
     def compute_head_pitch(self) -> np.ndarray:
         """Head pitch (rad): antero-posterior axis to the mid head vector on the sagittal plane, plus the rest pitch.
@@ -167,10 +226,13 @@ class HeadInverseKinematics:
     def compute_head_angles(self, export_path: Union[str, Path] = None,
                             compute_ant_angles: Optional[bool] = True) -> Dict[str, np.ndarray]:
         """Head roll, pitch, yaw and (optionally) antenna yaw / pitch per side, one value per frame."""
-        neck = np.asarray(self.aligned_pos["Neck"], dtype=np.float64)[:, 0, :]
-        out = _lib.head_angles(self.aligned_pos["R_head"], self.aligned_pos["L_head"], neck,
-                               self.rest_head_pitch, self.rest_antenna_pitch, compute_ant=bool(compute_ant_angles),
-                               device=self.device)
+        if self.head_affine is not None:
+            out = self._rows_raw(bool(compute_ant_angles))
+        else:
+            neck = np.asarray(self.aligned_pos["Neck"], dtype=np.float64)[:, 0, :]
+            out = _lib.head_angles(self.aligned_pos["R_head"], self.aligned_pos["L_head"], neck,
+                                   self.rest_head_pitch, self.rest_antenna_pitch, compute_ant=bool(compute_ant_angles),
+                                   device=self.device)
         head_angles = {name: out[i].copy() for i, name in enumerate(ANGLE_NAMES[: out.shape[0]])}
         if export_path is not None:
             save_file(Path(export_path) / "head_joint_angles.pkl", head_angles)

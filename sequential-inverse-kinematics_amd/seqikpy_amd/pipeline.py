@@ -21,7 +21,9 @@ from .kinematic_chain import KinematicChainSeq
 def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: KinematicChainSeq,
                 body_template: Dict[str, np.ndarray], initial_angles: Optional[Dict] = None, device: int = -1,
                 frame_parallel=None, stats: Optional[dict] = None,
-                missing_key_points: str = "raise") -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+                missing_key_points: str = "raise", leg_affine: Optional[Dict[str, tuple]] = None,
+                head_affine: Optional[Dict[str, tuple]] = None,
+                aligned_head: Optional[dict] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
     """Returns ``(body_joint_angles, forward_kinematics)``: the 7 head / antenna angles (when ``R_head``, ``L_head``
     and ``Neck`` are present) + 7 angles per leg, and the ``"<leg>_leg" -> (N, 9, 3)`` joint positions.
     ``frame_parallel``: as ``LegInvKinSeq.run_ik_and_fk`` -- None / ``"auto"`` (default: verified frame chunks; the same
@@ -32,7 +34,13 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
     -- frames with a non-finite key point are left out of the warm-start chain and come back as NaN angles and NaN FK
     rows (compact -> solve -> expand on the leg stream, ``_lib.solve_seq_gaps_device``).  It applies to the legs only:
     the head and antenna angles keep their behaviour in either mode (they are computed per frame, and a non-finite head
-    key point gives non-finite angles for that frame)."""
+    key point gives non-finite angles for that frame).
+    ``leg_affine`` (``AlignPose.leg_affines()``) and ``head_affine`` (``AlignPose.head_affines()``): with one given, that
+    part of ``aligned_pos`` holds RAW key points and its alignment runs inside the kernels -- the legs through the
+    solver's ``SeqikAffine`` prologue, the head through ``seqik_head_angles_raw_device`` (the neck is then the template's)
+    -- still two streams, one synchronisation, one download; the results are the bits of the call on the host-aligned
+    dictionary.  ``aligned_head``: a dict that receives the aligned ``R_head``, ``L_head`` and ``Neck`` the head kernel
+    mapped (``head_affine`` only; what ``AlignPose.align_pose()`` returns for them)."""
     import torch
     from .leg_inverse_kinematics import default_frame_parallel
     if frame_parallel is None:
@@ -50,7 +58,8 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
     if not skip:
         _lib._check_finite(pose)
     n = pose.shape[2]
-    with_head = all(k in aligned_pos for k in ("R_head", "L_head", "Neck"))
+    affine = None if leg_affine is None else [_lib.make_affine(*leg_affine[leg]) for _, leg in segs]
+    with_head = all(k in aligned_pos for k in (("R_head", "L_head", "Neck") if head_affine is None else ("R_head", "L_head")))
     lib = _lib.load()
     with torch.cuda.device(device):
         leg_stream, head_stream = torch.cuda.Stream(), torch.cuda.Stream()
@@ -70,12 +79,29 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
                         d_cangles=torch.empty((1, L, n, 7), **f64), d_cfk=torch.empty((1, L, n, 9, 3), **f64))
             _lib.solve_seq_gaps_device(d_pose, 1, L, n, legs, d_ang, d_fk=d_fk, stream=leg_stream,
                                        frame_chunk=-1 if frame_parallel else 0, d_chunk_stats=d_stats.data_ptr(),
-                                       **gaps)
+                                       affine=affine, **gaps)
         else:
             _lib.solve_seq_device(d_pose.data_ptr(), 1, len(segs), n, legs, d_ang.data_ptr(), d_fk.data_ptr(),
                                   stream=leg_stream.cuda_stream, frame_chunk=-1 if frame_parallel else 0,
-                                  d_chunk_stats=d_stats.data_ptr())
-        if with_head:
+                                  d_chunk_stats=d_stats.data_ptr(), affine=affine)
+        d_al = None
+        if with_head and head_affine is not None:
+            hk = HeadInverseKinematics.from_raw(aligned_pos, body_template, head_affine, log_level="ERROR")
+            r, l_ = hk.raw_pos["R_head"], hk.raw_pos["L_head"]
+            neck = np.ascontiguousarray(hk._template_neck()[:, 0, :])
+            nh, kp = r.shape[:2]
+            if kp < 2:
+                raise ValueError("R_head / L_head must hold the antenna base and tip")
+            d_r, d_l, d_n = (torch.from_numpy(a).cuda(non_blocking=True) for a in (r, l_, neck))
+            d_head = torch.zeros((7, nh), dtype=torch.float64, device="cuda")
+            if aligned_head is not None:
+                d_al = [torch.zeros((nh, 2, 3), dtype=torch.float64, device="cuda") for _ in range(2)]
+            head_stream.wait_stream(cur)
+            _lib.head_angles_raw_device(d_r, d_l, nh, kp, d_n, 3 if (neck.shape[0] == nh and nh > 1) else 0,
+                                        hk.rest_head_pitch, hk.rest_antenna_pitch, head_affine, d_head,
+                                        d_r_aligned=d_al[0] if d_al else 0, d_l_aligned=d_al[1] if d_al else 0,
+                                        stream=head_stream)
+        elif with_head:
             hk = HeadInverseKinematics(aligned_pos, body_template, log_level="ERROR")
             r = np.ascontiguousarray(aligned_pos["R_head"], dtype=np.float64)
             l_ = np.ascontiguousarray(aligned_pos["L_head"], dtype=np.float64)
@@ -94,6 +120,9 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
         _lib.check_faults()   # the device entry points do not synchronise: a kernel fault is reported here
         ang, fk = d_ang.cpu().numpy(), d_fk.cpu().numpy()
         head = d_head.cpu().numpy() if with_head else None
+        if d_al:
+            aligned_head.update({"R_head": d_al[0].cpu().numpy(), "L_head": d_al[1].cpu().numpy(),
+                                 "Neck": hk._template_neck()})
         if stats is not None:
             stats.update(_lib.chunk_stats_dict(d_stats.cpu().numpy()))
     body = {}
