@@ -317,6 +317,13 @@ int seqik_solve_generic_device(const double *d_pose, int64_t n_seq, int32_t n_le
  *   angles          [7][n_frames] (or [3][n_frames]): rows in the reference's dict order -- head roll,
  *                   head pitch, head yaw, antenna yaw L, antenna pitch L, antenna yaw R, antenna pitch R
  * The _device variant takes device pointers, enqueues on `hip_stream` and does not synchronise.
+ * Magnitudes: the rule forms |v1|^2 |v2|^2 before its one square root, so key points (and differences of key points) are
+ * supported between 2^-100 and 2^100 in magnitude, whatever the unit; inside that range scaling every key point and the
+ * neck by a power of two leaves every angle's bits unchanged (tests/test_head_accuracy.py, family c).  Outside it the
+ * products under- or overflow and the angles are wrong without notice.
+ * Non-finite and degenerate frames: an angle is NaN where the reference's is -- a NaN or infinite coordinate in a vector
+ * the angle is taken from, or a zero-length projected vector (L base = R base, tip = base, neck on a base) -- and the
+ * frame's other angles and every other frame are untouched.  Nothing is reported; the caller looks for NaN.
  */
 int seqik_head_angles(const double *r_head, const double *l_head, int64_t n_frames, const double *neck,
                       int64_t neck_stride, double rest_head_pitch, double rest_antenna_pitch, int32_t compute_ant,

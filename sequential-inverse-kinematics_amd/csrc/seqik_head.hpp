@@ -15,8 +15,11 @@
 namespace seqik {
 
 // This file is built with -ffp-contract=off like the solver (one flag set for the library), but nothing here is pinned
-// bit for bit to an oracle (the angles are compared with the reference at a tolerance), so products feeding sums are
-// written as explicit fused multiply-adds: a third fewer vector instructions than the separate multiply + add.
+// bit for bit to an oracle, so products feeding sums are written as explicit fused multiply-adds: a third fewer vector
+// instructions than the separate multiply + add.  What the angles ARE held to (tests/test_head_accuracy.py): atan2 in
+// long double, within K u (1 + 1 / max(|sin theta|, sqrt(K u))), u = 2^-53, K = 32 -- four times what the float64
+// restatement of the reference needs -- i.e. ~7e-15 rad mid-range, 6e-8 rad at an angle of 0 or pi, where a cosine one
+// ulp short of 1 is an angle of 2.6e-8; NaN exactly where the reference gives NaN; bit-equal under scaling by 2^+-100.
 SEQIK_HD double hfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // 1 / sqrt(v) and 1 / q without the IEEE corner-case handling of the compiler's division / square-root expansions (34
@@ -24,6 +27,9 @@ SEQIK_HD double hfma(double a, double b, double c) { return __builtin_fma(a, b, 
 // formulas on 6000 frames, scripts/microbench/head_split.hip: 2 + 3 steps 4e-12 rad, 2 + 2 steps 1.5e-11; the seeds are
 // good to ~2^-23 and the reciprocal's argument is in [0.6, 1], the square root's feeds an acos).  Host builds
 // (tests/harness) use the plain expressions.
+// inv_sqrt(0), inv_sqrt(inf) and inv_sqrt(NaN) are NaN: a zero-length or infinite vector has no direction, and its
+// angles are NaN as the reference's are.  On the device that is the first Newton step (seed inf times h = 0, seed 0
+// times h = inf); the host expression would give inf and 0 and says so explicitly.
 #ifndef SEQIK_HEAD_NEWTON
 #define SEQIK_HEAD_NEWTON 2
 #endif
@@ -36,7 +42,8 @@ SEQIK_HD double inv_sqrt(double v)
     for (int i = 0; i < SEQIK_HEAD_NEWTON + 1; ++i) y = hfma(y, hfma(-(h * y), y, 0.5), y);
     return y;
 #else
-    return 1.0 / sqrt(v);
+    const double y = 1.0 / sqrt(v);
+    return (y > 0.0 && y < HUGE_VAL) ? y : NAN;
 #endif
 }
 
@@ -52,10 +59,15 @@ SEQIK_HD double inv(double q)
 #endif
 }
 
+// A cosine into [-1, 1], NaN kept.  Compare-and-select, not fmin / fmax: those (and v_min_f64 / v_max_f64) return the
+// operand that is not NaN, which turned the NaN cosine of a frame with a missing or degenerate key point into -1 and the
+// frame into a plausible angle of -pi.  The comparisons are false for NaN, so it falls through; no finite value changes.
+SEQIK_HD double clamp_unit(double d) { return d > 1.0 ? 1.0 : (d < -1.0 ? -1.0 : d); }
+
 // acos for |x| <= 1 (the callers clamp).  The classic fdlibm scheme -- acos(x) = pi/2 - (x + x z R(z)) with z = x^2 for
 // |x| <= 1/2, 2 (s + s z R(z)) with z = (1 - |x|) / 2, s = sqrt(z) otherwise, R = P / Q a (6, 4) rational -- evaluated
 // branch-free: ONE rational for both ranges, selects at the end, without fdlibm's last-bit correction of the square
-// root (<= 2 ulp instead of < 1 ulp; the angles are compared at 1e-9 rad).  57 vector instructions instead of the 93 of
+// root (<= 2 ulp instead of < 1 ulp: one of the two factors of 2 in the bound above).  57 vector instructions instead of the 93 of
 // the device library's acos, seven times per frame: this kernel is meant to be bound by HBM, not by its arithmetic.
 SEQIK_HD double acos_unit(double x)
 {
@@ -91,7 +103,7 @@ SEQIK_HD double planar_angle(double a0, double a1, double b0, double b1)
     const double n2 = hfma(b0, b0, b1 * b1);
     double d = hfma(a0, b0, a1 * b1) * inv_sqrt(n1 * n2);
     const double det = hfma(a0, b1, -(a1 * b0));
-    d = fmin(1.0, fmax(-1.0, d));  // guard the last-ulp overshoot of the fused normalisation
+    d = clamp_unit(d);  // guard the last-ulp overshoot of the fused normalisation
     const double ang = acos_unit(d);
     return (det > 0) ? ang : -ang;
 }
@@ -103,7 +115,7 @@ SEQIK_HD double axis_angle(double b_along, double b_across, double *cos_out = nu
 {
     const double n2 = hfma(b_along, b_along, b_across * b_across);
     const double rn = inv_sqrt(n2);
-    const double d = fmin(1.0, fmax(-1.0, b_along * rn));
+    const double d = clamp_unit(b_along * rn);
     if (cos_out) { *cos_out = d; *sin_out = b_across * rn; }
     const double ang = acos_unit(d);
     return (b_across > 0) ? ang : -ang;
@@ -127,7 +139,7 @@ SEQIK_HD double signed_angle3(const double *v1, const double *v2, const double *
     const double n1 = hfma(v1[0], v1[0], hfma(v1[1], v1[1], v1[2] * v1[2]));
     const double n2 = hfma(v2[0], v2[0], hfma(v2[1], v2[1], v2[2] * v2[2]));
     double d = hfma(v1[0], v2[0], hfma(v1[1], v2[1], v1[2] * v2[2])) * inv_sqrt(n1 * n2);
-    d = fmin(1.0, fmax(-1.0, d));
+    d = clamp_unit(d);
     const double cx = hfma(v1[1], v2[2], -(v1[2] * v2[1])), cy = hfma(v1[2], v2[0], -(v1[0] * v2[2])),
                  cz = hfma(v1[0], v2[1], -(v1[1] * v2[0]));
     const double det = hfma(axis[0], cx, hfma(axis[1], cy, axis[2] * cz));

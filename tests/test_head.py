@@ -11,7 +11,8 @@ from conftest import ROOT, load_golden
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import head_oracle  # noqa: E402
 
-# acos is ill-conditioned near 0 / pi; libm, numpy and ocml differ in the last ulp of their inputs
+# acos is ill-conditioned near 0 / pi; libm, numpy and ocml differ in the last ulp of their inputs.  This flat bound is
+# the worst case at the ends; tests/test_head_accuracy.py holds the rule to a bound conditioned on the angle.
 TOL = 1e-6
 
 
