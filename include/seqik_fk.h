@@ -18,7 +18,12 @@
  * chain (KinematicChainGeneric: roll(Z), yaw(X), pitch(Y)).  The same angles give different positions under the two
  * kinds: pass the kind that produced them.  Only legs[i].seg is read.
  *
- * A non-finite angle makes that leg-frame's 27 FK values (and its 4 distances) NaN; it is not an error.
+ * Angle domain: finite and |angle| <= SEQIK_ANGLE_MAX = 2^30 rad.  Inside it sin and cos of every angle are within
+ * 2^-53 of the true values (within 1 ulp up to 1e7 rad), so unwrapped angles of any real recording are served as they
+ * are.  A non-finite angle, or one beyond SEQIK_ANGLE_MAX, makes that leg-frame's 27 FK values (and its 4 distances)
+ * NaN; it is not an error, and no other leg-frame is affected.  (Beyond 2^31 * pi / 2 the quadrant of the argument
+ * reduction no longer fits its integer; the domain ends well before, at a power of two.)  sin(-0.0) is returned as
+ * +0.0, so a zero entry of a result may differ in sign from numpy's; values never do.
  * Return codes and seqik_last_error() as in seqik.h.  SEQIK_ERR_BAD_ARG: n_legs outside 1..8, a negative size, null
  * angles / fk / legs, kind not 0 / 1, both pose and origin, dist without pose, a non-finite segment length.  A call
  * with no leg-frames returns SEQIK_OK without a launch.
@@ -35,6 +40,7 @@ extern "C" {
 #define SEQIK_FK_KIND_SEQ 0
 #define SEQIK_FK_KIND_GENERIC 1
 #define SEQIK_FK_MAX_LEGS 8
+#define SEQIK_ANGLE_MAX 1073741824.0 /* 2^30 rad: the largest |angle| these entry points and seqik_frames.h evaluate */
 
 /* Host buffers: copies in, launches on a pooled stream of `device` (-1 = the calling thread's current device),
  * copies out and synchronises. */

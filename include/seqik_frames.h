@@ -14,12 +14,16 @@
  *   0  sequential chain: base, ThC_yaw (X), ThC_pitch (Y), ThC_roll (Z), CTr_pitch (Y), CTr_roll (Z), FTi_pitch (Y),
  *                        TiTa_pitch (Y), Claw
  *   1  generic chain:    base, ThC_roll (Z), ThC_yaw (X), ThC_pitch (Y), then the same
- * The base and claw variables are 0.  Only legs[i].seg is read.
+ * Frame i is the product of the link matrices 0 .. i, each T(0, 0, tz) . R(axis, angle): tz = -seg[0] (coxa) for
+ * CTr_pitch, -seg[1] (femur) for FTi_pitch, -seg[2] (tibia) for TiTa_pitch, -seg[3] (tarsus) for the claw, 0 for the
+ * other links.  The base and claw variables are 0.  Only legs[i].seg is read.
  *
  * The translation column frames[..][i][a][3] equals row i, component a of seqik_forward_kinematics for the same angles,
  * kind and origin, bit for bit (the origin is added to the column; the rotation blocks do not depend on it).
  *
- * A non-finite angle makes that leg-frame's 108 values NaN; it is not an error.
+ * Angle domain as in seqik_fk.h: a non-finite angle, or one with |angle| > SEQIK_ANGLE_MAX (2^30 rad), makes that
+ * leg-frame's 108 values NaN; it is not an error, and no other leg-frame is affected.  sin(-0.0) is returned as +0.0,
+ * so a zero entry may differ in sign from IKPy's; values never do.
  * Return codes and seqik_last_error() as in seqik.h.  SEQIK_ERR_BAD_ARG: n_legs outside 1..8, a negative size, null
  * angles / frames / legs, kind not 0 / 1, a non-finite segment length, more leg-frames than 864 bytes each can be
  * addressed for.  A call with no leg-frames returns SEQIK_OK without a launch.

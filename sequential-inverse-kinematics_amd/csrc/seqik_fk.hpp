@@ -15,11 +15,18 @@
 #include "seqik_core.hpp"
 #include "seqik_generic.hpp"
 #include "../../include/seqik.h"
+#include "../../include/seqik_fk.h"
 
 namespace seqik {
 
 enum : int { FK_KIND_SEQ = 0, FK_KIND_GENERIC = 1 };
 constexpr int kFkMaxLegs = 8;  // the solver's kMaxLegs
+
+// The angle domain of the entry points that take angles from outside (fk_leg_frame, link_frames_walk): finite and
+// |x| <= SEQIK_ANGLE_MAX (include/seqik_fk.h).  sincos_cw turns rint(x * 2 / pi) into an int, which holds it only for
+// |x| < 2^31 * pi / 2; inside the domain that number stays below 6.84e8.  The comparison is false for NaN and for
+// +-inf, so it is the whole test.  The solvers do not need it: their angles lie inside validated bounds.
+SEQIK_HD bool angle_in_domain(double x) { return fabs(x) <= SEQIK_ANGLE_MAX; }
 
 // What the chains take from SeqikLegParams: the link translations, -seg[0..3] (negations, hence exactly the values
 // make_leg_consts / make_generic_consts store).
@@ -33,7 +40,8 @@ inline void make_fk_leg(const SeqikLegParams &lp, FkLeg &fl)
 }
 
 // One leg-frame.  ang [7] in DOFS order, origin [3] (nullable: leg-local positions, origin 0), out [27].
-// A non-finite angle makes all 27 values NaN (the chain itself is evaluated at 0 there).
+// An angle outside the domain (non-finite, or |x| > SEQIK_ANGLE_MAX) makes all 27 values NaN (the chain itself is
+// evaluated at 0 there).
 template <int KIND>
 SEQIK_HD void fk_leg_frame(const FkLeg &fl, const double *ang, const double *origin, double *out)
 {
@@ -42,7 +50,7 @@ SEQIK_HD void fk_leg_frame(const FkLeg &fl, const double *ang, const double *ori
 #pragma unroll
     for (int d = 0; d < 7; ++d) {
         x[d] = ang[d];
-        finite = finite && is_finite(x[d]);
+        finite = finite && angle_in_domain(x[d]);
     }
     if (!finite) {
 #pragma unroll

@@ -53,7 +53,7 @@ SEQIK_HD void link_frames_walk(const FkLeg &fl, const double *ang, const double 
 #pragma unroll
     for (int d = 0; d < 7; ++d) {
         x[d] = ang[d];
-        finite = finite && is_finite(x[d]);
+        finite = finite && angle_in_domain(x[d]);
     }
     if (!finite) {
 #pragma unroll
@@ -126,7 +126,7 @@ struct FramesQuadSink {
 };
 
 // One leg-frame.  ang [7] in DOFS order, origin [3] (nullable: leg-local positions), out [9][3][4].
-// A non-finite angle makes all 108 values NaN.
+// An angle outside the domain (non-finite, or |x| > SEQIK_ANGLE_MAX) makes all 108 values NaN.
 template <int KIND>
 SEQIK_HD void link_frames_leg_frame(const FkLeg &fl, const double *ang, const double *origin, double *out)
 {

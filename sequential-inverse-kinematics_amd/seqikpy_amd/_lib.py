@@ -458,8 +458,8 @@ def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_di
     ``kind``: ``"seq"`` (KinematicChainSeq) or ``"generic"`` (KinematicChainGeneric) -- the chain that produced the angles.
     The origin of each leg-frame is key point 0 of ``pose`` (S, L, N, 5, 3), or ``origin`` (anything that broadcasts to
     (S, L, N, 3); the fused alignment's origin is ``template_coxa``), or 0 when neither is given (leg-local positions).
-    ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  A non-finite angle makes that
-    leg-frame's rows NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
+    ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  An angle that is not finite or lies beyond
+    ``SEQIK_ANGLE_MAX`` (2^30 rad, include/seqik_fk.h) makes that leg-frame's rows (and distances) NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
     angles = np.ascontiguousarray(angles, dtype=np.float64)
     if angles.ndim != 4 or angles.shape[3] != 7:
         raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
@@ -515,8 +515,8 @@ def link_frames(angles, legs, kind="seq", origin=None, device=-1, rows3=False):
     ``"generic"`` (base, ThC_roll, ThC_yaw, ThC_pitch, ...).  ``origin``: anything that broadcasts to (S, L, N, 3), added to
     the translation column only; absent = leg-local frames.  The translation columns equal ``forward_kinematics``' rows
     for the same angles, kind and origin bit for bit.  ``rows3=True`` returns the (S, L, N, 9, 3, 4) array as the library
-    wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  A non-finite angle makes that leg-frame's
-    frames NaN (with ``rows3=False`` the fourth row too)."""
+    wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  An angle that is not finite or lies beyond
+    ``SEQIK_ANGLE_MAX`` (2^30 rad) makes that leg-frame's frames NaN (with ``rows3=False`` the fourth row too)."""
     angles = np.ascontiguousarray(angles, dtype=np.float64)
     if angles.ndim != 4 or angles.shape[3] != 7:
         raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
