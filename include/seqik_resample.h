@@ -14,7 +14,8 @@
  *               last knot are evaluated with the last interval's cubic (scipy: extrapolate=True)
  *   derivatives scipy's PchipInterpolator._find_derivatives: 0 where the two secant slopes differ in sign or one is 0,
  *               else their weighted harmonic mean; the three-point rule at both ends; two knots give a straight line
- *   value       the cubic Hermite polynomial of the interval
+ *   value       the cubic Hermite polynomial of the interval; a sample that sits on a knot is that knot's value, bit for
+ *               bit (the last knot closes its interval instead of opening one: its value is returned, not evaluated)
  *
  * DEFAULT MODE checks nothing per frame: a sample whose stencil (knots j-1 .. j+2, as far as they exist) holds a
  * non-finite value in its column is NaN, and no other sample is affected.

@@ -190,11 +190,19 @@ __global__ void __launch_bounds__(kBlock) seqik_resample_kernel(ResampleArgs a)
                 } else {
                     const int la = (A - lo) * W + col, lj = (j - lo) * W + col;
                     v = seqik::pchip_horner(sc0[lj], sc1[lj], sd[la], sy[la], u - seqik::resample_x(A, p.ots));
+                    if (tail && u == seqik::resample_x(B, p.ots)) v = sy[(B - lo) * W + col];  // pchip_eval: on knot B
                 }
             } else {
                 const int32_t A = j < n - 2 ? j : n - 2;
                 const int la = (A - lo) * W + col;
                 v = seqik::pchip_horner(sc0[la], sc1[la], sd[la], sy[la], u - seqik::resample_x(A, p.ots));
+                // pchip_eval: a sample on knot B (the last knot's alone) takes its value -- NaN when the stencil n - 3 .. n - 1
+                // holds a non-finite value, as resample_sample decides it (an overflowed c0 must not count as one)
+                if (j == n - 1 && u == seqik::resample_x(A + 1, p.ots)) {
+                    bool fin = seqik::is_finite(sy[la]) && seqik::is_finite(sy[la + W]);
+                    if (A > 0) fin = fin && seqik::is_finite(sy[la - W]);
+                    v = fin ? sy[la + W] : seqik::resample_nan();
+                }
             }
             __builtin_nontemporal_store(v, och + e);
         }

@@ -106,9 +106,12 @@ SEQIK_HD double pchip_horner(double c0, double c1, double c2, double c3, double 
     return r == r ? r : resample_nan();
 }
 
-// the stencil P, A, B, Q of interval (A, B) as knots
+// the stencil P, A, B, Q of interval (A, B) as knots.  A sample ON knot B takes that knot's value: the power form at
+// s = h equals it only up to rounding.  Every knot but the last (valid) one starts an interval of its own, where s = 0
+// returns y_A exactly, so this is the last knot's sample alone.
 SEQIK_HD double pchip_eval(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u)
 {
+    if (u == B.x) return B.y;
     const PchipKnot none = {0.0, 0.0, false};
     const double da = pchip_deriv(none, P, A, B, Q), db = pchip_deriv(P, A, B, Q, none);
     double c0, c1;
