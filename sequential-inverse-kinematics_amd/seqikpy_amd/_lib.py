@@ -22,13 +22,13 @@ _NATIVE = os.path.join(_PKG, "_native")
 _IN_TREE = not os.path.isfile(os.path.join(_NATIVE, "libseqik_hip.so")) and os.path.isfile(os.path.join(CSRC, "seqik_hip.hip"))
 _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
-SOURCES = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip", "seqik_peer.hip",
-           "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp",
-           "seqik_generic.hpp", "seqik_device_scope.hpp", "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp",
-           "seqik_resample.hpp", "seqik_frames.hip", "seqik_frames.hpp", "seqik_head_align.hip", "seqik_head_align.hpp"]
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
                  "seqik_head_align.hip"]
+CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
+                "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
+                "seqik_head_align.hpp"]
+SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
 SEQIK_OK = 0
@@ -36,6 +36,7 @@ ERR_HIP, ERR_X0, ERR_BOUNDS, ERR_ARG, ERR_STAGE = -1, -2, -3, -4, -5
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 
 
 class SeqikLegParams(ctypes.Structure):
@@ -79,10 +80,7 @@ def selftest_div_sqrt(a, b):
     if a.shape != b.shape:
         raise ValueError("a and b must have the same number of elements")
     q, r = np.empty_like(a), np.empty_like(a)
-    rc = load().seqik_selftest_div_sqrt(a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), q.ctypes.data_as(_dp),
-                                        r.ctypes.data_as(_dp), a.size)
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_selftest_div_sqrt", _data(a), _data(b), _data(q), _data(r), a.size)
     return q, r
 
 
@@ -90,9 +88,7 @@ def selftest_sqrt_pos(a):
     """sqrt(a) as the kernels compute it for the Coleman-Li distances (``sqrt_pos_``: no zero / infinity selects)."""
     a = np.ascontiguousarray(a, dtype=np.float64).ravel()
     r = np.empty_like(a)
-    rc = load().seqik_selftest_sqrt_pos(a.ctypes.data_as(_dp), r.ctypes.data_as(_dp), a.size)
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_selftest_sqrt_pos", _data(a), _data(r), a.size)
     return r
 
 
@@ -102,20 +98,18 @@ def check_faults(stream=None):
     after synchronising.  ``stream=None``: every stream of the process (single-threaded callers); ``stream=<hipStream_t as
     int>`` (0 = the default stream): the launches made on that stream of the current device only -- what a host thread
     that shares the process with other threads' GPUs / streams uses (ABI 6)."""
-    rc = load().seqik_check_faults() if stream is None else load().seqik_check_faults_stream(ctypes.c_void_p(int(stream)))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    if stream is None:
+        _call("seqik_check_faults")
+    else:
+        _call("seqik_check_faults_stream", _stream_ptr(stream))
 
 
 def frame_chunk_plan(n_frames, frame_chunk=-1, frame_halo=0, frame_lead=0):
     """``seqik_frame_chunk_plan``: (frames per chunk, run-in frames, chunks per chain) a call over recordings of
     ``n_frames`` frames would use -- (0, 0, 0) when it would be walked serially.  No GPU needed."""
-    opt = SeqikOptions()
-    opt.frame_chunk, opt.frame_halo, opt.frame_lead = int(frame_chunk), int(frame_halo), int(frame_lead)
+    opt = SeqikOptions(frame_chunk=int(frame_chunk), frame_halo=int(frame_halo), frame_lead=int(frame_lead))
     c, h, k = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
-    rc = load().seqik_frame_chunk_plan(int(n_frames), ctypes.byref(opt), ctypes.byref(c), ctypes.byref(h), ctypes.byref(k))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_frame_chunk_plan", int(n_frames), ctypes.byref(opt), ctypes.byref(c), ctypes.byref(h), ctypes.byref(k))
     return int(c.value), int(h.value), int(k.value)
 
 
@@ -158,6 +152,83 @@ def make_head_affine(origin, scale_base, scale_tip, template_base) -> SeqikHeadA
         a.template_base[i] = float(template_base[i])
     a.scale_base, a.scale_tip = float(scale_base), float(scale_tip)
     return a
+
+
+# The C ABI as ctypes sees it, one line per entry point of each header under include/: (name, return type, parameter
+# types...).  ``load()`` applies it; tests/test_capi_symbols.py holds it against the prototypes.  Device pointers, streams
+# and handles are ``void *`` here whatever the header's pointee type, so that wrappers and tests can pass plain ints.
+_int, _i32, _i64, _f64, _size = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_double, ctypes.c_size_t
+_vp, _vpp, _cp, _i64p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)
+_legs, _opt, _lay = ctypes.POINTER(SeqikLegParams), ctypes.POINTER(SeqikOptions), ctypes.POINTER(SeqikLayout)
+_aff, _haff = ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikHeadAffine)
+SIGNATURES = {
+    "seqik.h": (
+        ("seqik_abi_version", _int),
+        ("seqik_device_count", _int),
+        ("seqik_last_error", _cp),
+        ("seqik_device_attributes", _int, _i32, _ip, _ip, _i64p),
+        ("seqik_release_workspaces", _int),
+        ("seqik_validate_legs", _int, _legs, _i32, _i32, _i32),
+        ("seqik_solve_seq", _int, _dp, _i64, _i32, _i64, _legs, _i32, _i32, _dp, _dp, _ip, _ip, _dp, _aff, _opt),
+        ("seqik_selftest_div_sqrt", _int, _dp, _dp, _dp, _dp, _i64),
+        ("seqik_selftest_sqrt_pos", _int, _dp, _dp, _i64),
+        ("seqik_check_faults", _int),
+        ("seqik_check_faults_stream", _int, _vp),
+        ("seqik_frame_chunk_plan", _int, _i64, _opt, _ip, _ip, _i64p),
+        ("seqik_solve_seq_device", _int, _vp, _i64, _i32, _i64, _legs, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _lay, _aff, _opt, _vp),
+        ("seqik_validate_legs_generic", _int, _legs, _i32),
+        ("seqik_solve_generic", _int, _dp, _i64, _i32, _i64, _legs, _dp, _dp, _ip, _ip, _dp, _aff, _opt),
+        ("seqik_solve_generic_device", _int, _vp, _i64, _i32, _i64, _legs, _vp, _vp, _vp, _vp, _vp, _lay, _aff, _opt, _vp),
+        ("seqik_head_angles", _int, _dp, _dp, _i64, _dp, _i64, _f64, _f64, _i32, _dp, _opt),
+        ("seqik_head_angles_device", _int, _vp, _vp, _i64, _vp, _i64, _f64, _f64, _i32, _vp, _vp),
+        ("seqik_head_angles_ex", _int, _dp, _dp, _i64, _i32, _dp, _i64, _f64, _f64, _i32, _dp, _dp, _opt),
+        ("seqik_head_angles_ex_device", _int, _vp, _vp, _i64, _i32, _vp, _i64, _f64, _f64, _i32, _vp, _vp, _vp),
+        ("seqik_signed_angles", _int, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _opt),
+        ("seqik_peer_alloc", _int, _vpp, _size),
+        ("seqik_peer_free", _int, _vp),
+        ("seqik_peer_export", _int, _vp, _cp),
+        ("seqik_peer_open", _int, _cp, _vpp),
+        ("seqik_peer_close", _int, _vp),
+        ("seqik_peer_copy", _int, _vp, _vp, _size, _vp),
+        ("seqik_host_alloc", _vp, _size),
+        ("seqik_host_free", None, _vp),
+        ("seqik_host_register", _int, _vp, _size),
+        ("seqik_host_unregister", _int, _vp),
+        ("seqik_stream_open", _int, _vpp, _i32, _legs, _aff, _i64, _i64, _lay, _i32, _i32, _i32, _i32, _opt),
+        ("seqik_stream_submit", _int, _vp, _vp, _i64, _vp, _vp),
+        ("seqik_stream_wait", _int, _vp),
+        ("seqik_stream_reset_carry", _int, _vp),
+        ("seqik_stream_set_carry", _int, _vp, _vp, _i64, _i32),
+        ("seqik_stream_close", _int, _vp),
+        ("seqik_align_stats_open", _int, _vpp, _i32, _i64, _opt),
+        ("seqik_align_stats_add", _int, _vp, _vp, _i32, _i64, _i64, _lay, _vp),
+        ("seqik_align_stats_finish", _int, _vp, _i64p, _i32, _dp, _vp),
+        ("seqik_align_stats_reset", _int, _vp),
+        ("seqik_align_stats_close", _int, _vp)),
+    "seqik_fk.h": (
+        ("seqik_forward_kinematics", _int, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _dp, _dp, _dp, _i32),
+        ("seqik_forward_kinematics_device", _int, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _vp, _vp, _vp)),
+    "seqik_frames.h": (
+        ("seqik_link_frames", _int, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _dp, _i32),
+        ("seqik_link_frames_device", _int, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _vp)),
+    "seqik_gaps.h": (
+        ("seqik_gaps_compact_device", _int, _vp, _i64, _i32, _i64, _i32, _legs, _vp, _vp, _vp, _vp),
+        ("seqik_gaps_expand_device", _int, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+        ("seqik_solve_seq_gaps", _int, _dp, _i64, _i32, _i64, _legs, _i32, _i32, _dp, _dp, _ip, _ip, _dp, _aff, _opt, _ip),
+        ("seqik_solve_generic_gaps", _int, _dp, _i64, _i32, _i64, _legs, _dp, _dp, _ip, _ip, _dp, _aff, _opt, _ip)),
+    "seqik_resample.h": (
+        ("seqik_resample_count", _i64, _i64, _f64, _f64),
+        ("seqik_resample_workspace_bytes", _size, _i64, _i64, _i32),
+        ("seqik_resample_pchip", _int, _dp, _i64, _i64, _i32, _f64, _f64, _i32, _i32, _dp, _i64, _i32),
+        ("seqik_resample_pchip_device", _int, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _i32, _vp, _i64, _vp, _vp)),
+    "seqik_head_align.h": (
+        ("seqik_head_align_stats_open", _int, _vpp, _i64, _opt),
+        ("seqik_head_align_stats_select", _int, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f64, _i64p, _i64p),
+        ("seqik_head_align_stats_pick", _int, _vp, _i64p, _i64p, _i32, _dp),
+        ("seqik_head_align_stats_close", _int, _vp),
+        ("seqik_head_angles_raw", _int, _dp, _dp, _i64, _i32, _dp, _i64, _f64, _f64, _i32, _dp, _haff, _dp, _dp, _dp, _opt),
+        ("seqik_head_angles_raw_device", _int, _vp, _vp, _i64, _i32, _vp, _i64, _f64, _f64, _i32, _vp, _haff, _vp, _vp, _vp, _vp)),
+}
 
 
 class SeqikLibraryError(RuntimeError):
@@ -203,21 +274,27 @@ def csrc_sha256(files=None, read=None) -> str:
     return h.hexdigest()
 
 
+def _older_than_sources(path) -> bool:
+    return (not os.path.exists(path) or
+            any(os.path.getmtime(os.path.join(CSRC, s)) > os.path.getmtime(path) for s in SOURCES))
+
+
 def is_stale() -> bool:
-    if not _IN_TREE:
-        return False          # installed package: the library was compiled when the distribution was built
-    if not os.path.exists(LIB_PATH):
-        return True
-    t = os.path.getmtime(LIB_PATH)
-    return any(os.path.getmtime(os.path.join(CSRC, s)) > t for s in SOURCES)
+    # installed package: the library was compiled when the distribution was built
+    return _IN_TREE and _older_than_sources(LIB_PATH)
+
+
+def _compile(out_path, extra_flags, needed) -> str:
+    """``COMPILE_UNITS`` -> ``out_path`` with ``HIPCC_FLAGS`` + ``extra_flags`` (gfx950), when ``needed``."""
+    if needed:
+        cmd = [_hipcc()] + HIPCC_FLAGS + extra_flags + ["-o", out_path] + [os.path.join(CSRC, u) for u in COMPILE_UNITS]
+        subprocess.check_call(cmd, cwd=CSRC)
+    return out_path
 
 
 def build(force: bool = False) -> str:
     """Compiles ``csrc/seqik_hip.hip`` -> ``csrc/libseqik_hip.so`` (gfx950)."""
-    if force or is_stale():
-        cmd = [_hipcc()] + HIPCC_FLAGS + ["-o", LIB_PATH] + [os.path.join(CSRC, u) for u in COMPILE_UNITS]
-        subprocess.check_call(cmd, cwd=CSRC)
-    return LIB_PATH
+    return _compile(LIB_PATH, [], force or is_stale())
 
 
 WATCHDOG_LIB_PATH = os.path.join(CSRC, "libseqik_hip_watchdog.so")
@@ -228,13 +305,7 @@ def build_watchdog_variant(force: bool = False) -> str:
     pipeline's watchdog limit set to ONE pass (``-DSEQIK_PIPE_SPIN_LIMIT=1``), so that the fault path -- NaN in the
     chain, fault word, ``SEQIK_ERR_HIP`` from the entry points -- can be exercised.  Never loaded by the package itself
     (only through ``SEQIK_LIB`` in a child process of that test)."""
-    stale = (not os.path.exists(WATCHDOG_LIB_PATH) or
-             any(os.path.getmtime(os.path.join(CSRC, s)) > os.path.getmtime(WATCHDOG_LIB_PATH) for s in SOURCES))
-    if force or stale:
-        cmd = ([_hipcc()] + HIPCC_FLAGS + ["-DSEQIK_PIPE_SPIN_LIMIT=1", "-o", WATCHDOG_LIB_PATH] +
-               [os.path.join(CSRC, u) for u in COMPILE_UNITS])
-        subprocess.check_call(cmd, cwd=CSRC)
-    return WATCHDOG_LIB_PATH
+    return _compile(WATCHDOG_LIB_PATH, ["-DSEQIK_PIPE_SPIN_LIMIT=1"], force or _older_than_sources(WATCHDOG_LIB_PATH))
 
 
 def load():
@@ -258,320 +329,42 @@ def load():
             except ImportError:
                 pass
         L = ctypes.CDLL(LIB_PATH)
-        L.seqik_abi_version.restype = ctypes.c_int
         if L.seqik_abi_version() != ABI_VERSION:
             raise SeqikLibraryError(f"{LIB_PATH} has ABI {L.seqik_abi_version()}, this package needs {ABI_VERSION}: "
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        L.seqik_device_count.restype = ctypes.c_int
-        L.seqik_last_error.restype = ctypes.c_char_p
-        L.seqik_release_workspaces.restype = ctypes.c_int
-        L.seqik_release_workspaces.argtypes = []
-        _vpp = ctypes.POINTER(ctypes.c_void_p)
-        for name, args in (("seqik_peer_alloc", [_vpp, ctypes.c_size_t]), ("seqik_peer_free", [ctypes.c_void_p]),
-                           ("seqik_peer_export", [ctypes.c_void_p, ctypes.c_char_p]),
-                           ("seqik_peer_open", [ctypes.c_char_p, _vpp]), ("seqik_peer_close", [ctypes.c_void_p]),
-                           ("seqik_peer_copy", [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p])):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = args
-        L.seqik_device_attributes.restype = ctypes.c_int
-        L.seqik_device_attributes.argtypes = [ctypes.c_int32, _ip, _ip, ctypes.POINTER(ctypes.c_int64)]
-        L.seqik_validate_legs.restype = ctypes.c_int
-        L.seqik_validate_legs.argtypes = [ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-        L.seqik_solve_seq.restype = ctypes.c_int
-        L.seqik_solve_seq.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                      ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_int32,
-                                      _dp, _dp, _ip, _ip, _dp, ctypes.POINTER(SeqikAffine),
-                                      ctypes.POINTER(SeqikOptions)]
-        L.seqik_solve_seq_device.restype = ctypes.c_int
-        L.seqik_solve_seq_device.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                             ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.POINTER(SeqikLayout), ctypes.POINTER(SeqikAffine),
-                                             ctypes.POINTER(SeqikOptions), ctypes.c_void_p]
-        L.seqik_selftest_div_sqrt.restype = ctypes.c_int
-        L.seqik_selftest_div_sqrt.argtypes = [_dp, _dp, _dp, _dp, ctypes.c_int64]
-        L.seqik_selftest_sqrt_pos.restype = ctypes.c_int
-        L.seqik_selftest_sqrt_pos.argtypes = [_dp, _dp, ctypes.c_int64]
-        L.seqik_check_faults.restype = ctypes.c_int
-        L.seqik_check_faults.argtypes = []
-        L.seqik_check_faults_stream.restype = ctypes.c_int
-        L.seqik_check_faults_stream.argtypes = [ctypes.c_void_p]
-        L.seqik_frame_chunk_plan.restype = ctypes.c_int
-        L.seqik_frame_chunk_plan.argtypes = [ctypes.c_int64, ctypes.POINTER(SeqikOptions), _ip, _ip,
-                                             ctypes.POINTER(ctypes.c_int64)]
-        L.seqik_validate_legs_generic.restype = ctypes.c_int
-        L.seqik_validate_legs_generic.argtypes = [ctypes.POINTER(SeqikLegParams), ctypes.c_int32]
-        L.seqik_solve_generic.restype = ctypes.c_int
-        L.seqik_solve_generic.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                          ctypes.POINTER(SeqikLegParams), _dp, _dp, _ip, _ip, _dp,
-                                          ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikOptions)]
-        L.seqik_solve_generic_device.restype = ctypes.c_int
-        L.seqik_solve_generic_device.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                 ctypes.POINTER(SeqikLegParams), ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.POINTER(SeqikLayout), ctypes.POINTER(SeqikAffine),
-                                                 ctypes.POINTER(SeqikOptions), ctypes.c_void_p]
-        L.seqik_head_angles.restype = ctypes.c_int
-        L.seqik_head_angles.argtypes = [_dp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_double,
-                                        ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(SeqikOptions)]
-        L.seqik_head_angles_device.restype = ctypes.c_int
-        L.seqik_head_angles_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                               ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
-                                               ctypes.c_void_p, ctypes.c_void_p]
-        L.seqik_head_angles_ex.restype = ctypes.c_int
-        L.seqik_head_angles_ex.argtypes = [_dp, _dp, ctypes.c_int64, ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_int32, _dp, _dp, ctypes.POINTER(SeqikOptions)]
-        L.seqik_head_angles_ex_device.restype = ctypes.c_int
-        L.seqik_head_angles_ex_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.seqik_signed_angles.restype = ctypes.c_int
-        L.seqik_signed_angles.argtypes = [_dp, ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_int64, _dp,
-                                          ctypes.POINTER(SeqikOptions)]
-        L.seqik_host_alloc.restype = ctypes.c_void_p
-        L.seqik_host_alloc.argtypes = [ctypes.c_size_t]
-        L.seqik_host_free.restype = None
-        L.seqik_host_free.argtypes = [ctypes.c_void_p]
-        L.seqik_host_register.restype = ctypes.c_int
-        L.seqik_host_register.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-        L.seqik_host_unregister.restype = ctypes.c_int
-        L.seqik_host_unregister.argtypes = [ctypes.c_void_p]
-        L.seqik_stream_open.restype = ctypes.c_int
-        L.seqik_stream_open.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.POINTER(SeqikLegParams),
-                                        ctypes.POINTER(SeqikAffine), ctypes.c_int64, ctypes.c_int64,
-                                        ctypes.POINTER(SeqikLayout), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_int32, ctypes.POINTER(SeqikOptions)]
-        L.seqik_stream_submit.restype = ctypes.c_int
-        L.seqik_stream_submit.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                          ctypes.c_void_p]
-        L.seqik_stream_set_carry.restype = ctypes.c_int
-        L.seqik_stream_set_carry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32]
-        for name in ("seqik_stream_wait", "seqik_stream_reset_carry", "seqik_stream_close"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [ctypes.c_void_p]
-        L.seqik_align_stats_open.restype = ctypes.c_int
-        L.seqik_align_stats_open.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int64,
-                                             ctypes.POINTER(SeqikOptions)]
-        L.seqik_align_stats_add.restype = ctypes.c_int
-        L.seqik_align_stats_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
-                                            ctypes.c_int64, ctypes.POINTER(SeqikLayout), ctypes.c_void_p]
-        L.seqik_align_stats_finish.restype = ctypes.c_int
-        L.seqik_align_stats_finish.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, _dp,
-                                               ctypes.c_void_p]
-        for name in ("seqik_align_stats_reset", "seqik_align_stats_close"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [ctypes.c_void_p]
-        L.seqik_forward_kinematics.restype = ctypes.c_int
-        L.seqik_forward_kinematics.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                               ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _dp, _dp, _dp, _dp,
-                                               ctypes.c_int32]
-        L.seqik_forward_kinematics_device.restype = ctypes.c_int
-        L.seqik_forward_kinematics_device.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                                      ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_void_p,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        _vp = ctypes.c_void_p
-        L.seqik_link_frames.restype = ctypes.c_int
-        L.seqik_link_frames.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                        ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _dp, _dp, ctypes.c_int32]
-        L.seqik_link_frames_device.restype = ctypes.c_int
-        L.seqik_link_frames_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                               ctypes.POINTER(SeqikLegParams), ctypes.c_int32, _vp, _vp, _vp]
-        L.seqik_gaps_compact_device.restype = ctypes.c_int
-        L.seqik_gaps_compact_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                                ctypes.POINTER(SeqikLegParams), _vp, _vp, _vp, _vp]
-        L.seqik_gaps_expand_device.restype = ctypes.c_int
-        L.seqik_gaps_expand_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.seqik_solve_seq_gaps.restype = ctypes.c_int
-        L.seqik_solve_seq_gaps.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                           ctypes.POINTER(SeqikLegParams), ctypes.c_int32, ctypes.c_int32,
-                                           _dp, _dp, _ip, _ip, _dp, ctypes.POINTER(SeqikAffine),
-                                           ctypes.POINTER(SeqikOptions), _ip]
-        L.seqik_solve_generic_gaps.restype = ctypes.c_int
-        L.seqik_solve_generic_gaps.argtypes = [_dp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-                                               ctypes.POINTER(SeqikLegParams), _dp, _dp, _ip, _ip, _dp,
-                                               ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikOptions), _ip]
-        L.seqik_resample_count.restype = ctypes.c_int64
-        L.seqik_resample_count.argtypes = [ctypes.c_int64, ctypes.c_double, ctypes.c_double]
-        L.seqik_resample_workspace_bytes.restype = ctypes.c_size_t
-        L.seqik_resample_workspace_bytes.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32]
-        L.seqik_resample_pchip.restype = ctypes.c_int
-        L.seqik_resample_pchip.argtypes = [_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int64,
-                                           ctypes.c_int32]
-        L.seqik_resample_pchip_device.restype = ctypes.c_int
-        L.seqik_resample_pchip_device.argtypes = [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
-                                                  ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int64,
-                                                  _vp, _vp]
-        _i64p = ctypes.POINTER(ctypes.c_int64)
-        L.seqik_head_align_stats_open.restype = ctypes.c_int
-        L.seqik_head_align_stats_open.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int64,
-                                                  ctypes.POINTER(SeqikOptions)]
-        L.seqik_head_align_stats_select.restype = ctypes.c_int
-        L.seqik_head_align_stats_select.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_double, _i64p, _i64p]
-        L.seqik_head_align_stats_pick.restype = ctypes.c_int
-        L.seqik_head_align_stats_pick.argtypes = [_vp, _i64p, _i64p, ctypes.c_int32, _dp]
-        L.seqik_head_align_stats_close.restype = ctypes.c_int
-        L.seqik_head_align_stats_close.argtypes = [_vp]
-        L.seqik_head_angles_raw.restype = ctypes.c_int
-        L.seqik_head_angles_raw.argtypes = [_dp, _dp, ctypes.c_int64, ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_double,
-                                            ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(SeqikHeadAffine), _dp,
-                                            _dp, _dp, ctypes.POINTER(SeqikOptions)]
-        L.seqik_head_angles_raw_device.restype = ctypes.c_int
-        L.seqik_head_angles_raw_device.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp, ctypes.c_int64,
-                                                   ctypes.c_double, ctypes.c_double, ctypes.c_int32, _vp,
-                                                   ctypes.POINTER(SeqikHeadAffine), _vp, _vp, _vp, _vp]
+        for signatures in SIGNATURES.values():
+            for name, restype, *argtypes in signatures:
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = L
         return _lib
 
 
-EXPORTED_SYMBOLS = ["seqik_abi_version", "seqik_device_count", "seqik_last_error", "seqik_device_attributes", "seqik_release_workspaces",
-                    "seqik_validate_legs", "seqik_frame_chunk_plan", "seqik_selftest_div_sqrt", "seqik_selftest_sqrt_pos", "seqik_check_faults", "seqik_check_faults_stream",
-                    "seqik_peer_alloc", "seqik_peer_free", "seqik_peer_export", "seqik_peer_open", "seqik_peer_close",
-                    "seqik_peer_copy",
-                    "seqik_solve_seq", "seqik_solve_seq_device", "seqik_head_angles", "seqik_head_angles_device",
-                    "seqik_head_angles_ex", "seqik_head_angles_ex_device", "seqik_signed_angles",
-                    "seqik_validate_legs_generic", "seqik_solve_generic", "seqik_solve_generic_device",
-                    "seqik_host_alloc", "seqik_host_free", "seqik_host_register", "seqik_host_unregister",
-                    "seqik_stream_open", "seqik_stream_submit", "seqik_stream_wait", "seqik_stream_reset_carry", "seqik_stream_set_carry",
-                    "seqik_stream_close", "seqik_align_stats_open", "seqik_align_stats_add",
-                    "seqik_align_stats_finish", "seqik_align_stats_reset", "seqik_align_stats_close"]
-
-#: entry points of include/seqik_fk.h (forward kinematics from joint angles), kept apart from the ABI-7 set of seqik.h
-FK_EXPORTED_SYMBOLS = ["seqik_forward_kinematics", "seqik_forward_kinematics_device"]
-FK_KINDS = {"seq": 0, "generic": 1}
+def _raise(rc: int):
+    msg = load().seqik_last_error().decode("utf-8", "replace")
+    if rc in (ERR_X0, ERR_BOUNDS, ERR_STAGE):
+        raise ValueError(msg)
+    if rc == ERR_ARG:
+        raise ValueError(f"seqik: bad argument: {msg}")
+    raise SeqikLibraryError(f"seqik: HIP error: {msg}")
 
 
-def _fk_kind(kind) -> int:
-    if isinstance(kind, str):
-        if kind not in FK_KINDS:
-            raise ValueError(f"kind must be one of {sorted(FK_KINDS)}, got {kind!r}")
-        return FK_KINDS[kind]
-    return int(kind)
-
-
-def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_dist=False, device=-1):
-    """``seqik_forward_kinematics`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(fk (S, L, N, 9, 3),
-    dist (S, L, N, 4) or None), the rows the solvers write (``solve_seq`` / ``solve_generic``).
-
-    ``kind``: ``"seq"`` (KinematicChainSeq) or ``"generic"`` (KinematicChainGeneric) -- the chain that produced the angles.
-    The origin of each leg-frame is key point 0 of ``pose`` (S, L, N, 5, 3), or ``origin`` (anything that broadcasts to
-    (S, L, N, 3); the fused alignment's origin is ``template_coxa``), or 0 when neither is given (leg-local positions).
-    ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  An angle that is not finite or lies beyond
-    ``SEQIK_ANGLE_MAX`` (2^30 rad, include/seqik_fk.h) makes that leg-frame's rows (and distances) NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
-    angles = np.ascontiguousarray(angles, dtype=np.float64)
-    if angles.ndim != 4 or angles.shape[3] != 7:
-        raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
-    S, L, N = angles.shape[:3]
-    if len(legs) != L:
-        raise ValueError("one SeqikLegParams per leg expected")
-    k = _fk_kind(kind)
-    if pose is not None and origin is not None:
-        raise ValueError("pass pose or origin, not both")
-    if want_dist and pose is None:
-        raise ValueError("want_dist needs pose (the key points to measure against)")
-    if pose is not None:
-        pose = np.ascontiguousarray(pose, dtype=np.float64)
-        if pose.shape != (S, L, N, 5, 3):
-            raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
-    if origin is not None:
-        origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64), (S, L, N, 3)))
-    fk = np.full((S, L, N, 9, 3), np.nan)
-    dist = np.full((S, L, N, 4), np.nan) if want_dist else None
-    rc = load().seqik_forward_kinematics(angles.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs), k,
-                                         pose.ctypes.data_as(_dp) if pose is not None else None,
-                                         origin.ctypes.data_as(_dp) if origin is not None else None,
-                                         fk.ctypes.data_as(_dp), dist.ctypes.data_as(_dp) if dist is not None else None,
-                                         int(device))
-    if rc != SEQIK_OK:
-        _raise(rc)
-    return dict(fk=fk, dist=dist)
-
-
-def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kind="seq", d_pose=0, d_origin=0, d_dist=0,
-                              stream=0):
-    """``seqik_forward_kinematics_device``: raw device pointers (ints) in the dense layouts of ``forward_kinematics``,
-    asynchronous on ``stream`` (a hipStream_t as int; 0 = the default stream) of the current device."""
-    arr = (SeqikLegParams * n_legs)(*legs)
-    rc = load().seqik_forward_kinematics_device(ctypes.c_void_p(int(d_angles) or None), int(n_seq), int(n_legs),
-                                                int(n_frames), arr, _fk_kind(kind), ctypes.c_void_p(int(d_pose) or None),
-                                                ctypes.c_void_p(int(d_origin) or None), ctypes.c_void_p(int(d_fk) or None),
-                                                ctypes.c_void_p(int(d_dist) or None), ctypes.c_void_p(int(stream) or None))
+def _call(name, *args):
+    """Calls the status-returning entry point ``name``; anything but ``SEQIK_OK`` raises (``_raise``)."""
+    rc = getattr(_lib or load(), name)(*args)
     if rc != SEQIK_OK:
         _raise(rc)
 
 
-#: entry points of include/seqik_frames.h (link frames from joint angles), kept apart from the ABI-7 set of seqik.h
-FRAMES_EXPORTED_SYMBOLS = ["seqik_link_frames", "seqik_link_frames_device"]
-
-
-def link_frames(angles, legs, kind="seq", origin=None, device=-1, rows3=False):
-    """``seqik_link_frames`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(frames (S, L, N, 9, 4, 4)),
-    the 4 x 4 frame of each of the nine links of the whole-leg chain in the chain's base frame -- what IKPy's
-    ``Chain.forward_kinematics(q, full_kinematics=True)`` returns, for every leg-frame of the batch.
-
-    ``kind``: ``"seq"`` (links base, ThC_yaw, ThC_pitch, ThC_roll, CTr_pitch, CTr_roll, FTi_pitch, TiTa_pitch, Claw) or
-    ``"generic"`` (base, ThC_roll, ThC_yaw, ThC_pitch, ...).  ``origin``: anything that broadcasts to (S, L, N, 3), added to
-    the translation column only; absent = leg-local frames.  The translation columns equal ``forward_kinematics``' rows
-    for the same angles, kind and origin bit for bit.  ``rows3=True`` returns the (S, L, N, 9, 3, 4) array as the library
-    wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  An angle that is not finite or lies beyond
-    ``SEQIK_ANGLE_MAX`` (2^30 rad) makes that leg-frame's frames NaN (with ``rows3=False`` the fourth row too)."""
-    angles = np.ascontiguousarray(angles, dtype=np.float64)
-    if angles.ndim != 4 or angles.shape[3] != 7:
-        raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
-    S, L, N = angles.shape[:3]
-    if len(legs) != L:
-        raise ValueError("one SeqikLegParams per leg expected")
-    k = _fk_kind(kind)
-    if origin is not None:
-        origin = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64), (S, L, N, 3)))
-    rows = np.full((S, L, N, 9, 3, 4), np.nan)
-    rc = load().seqik_link_frames(angles.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs), k,
-                                  origin.ctypes.data_as(_dp) if origin is not None else None,
-                                  rows.ctypes.data_as(_dp), int(device))
-    if rc != SEQIK_OK:
-        _raise(rc)
-    if rows3:
-        return dict(frames=rows)
-    frames = np.empty((S, L, N, 9, 4, 4))
-    frames[..., :3, :] = rows
-    frames[..., 3, :] = (0.0, 0.0, 0.0, 1.0)
-    frames[..., 3, :][np.isnan(rows[..., 0, 0])] = np.nan
-    return dict(frames=frames)
-
-
-def link_frames_device(d_angles, n_seq, n_legs, n_frames, legs, d_frames, kind="seq", d_origin=0, stream=None):
-    """``seqik_link_frames_device``: raw device pointers (ints) in the dense layouts of ``include/seqik_frames.h``
-    (``d_frames``: (S, L, N, 9, 3, 4) doubles), asynchronous on ``stream`` (a hipStream_t as int; None / 0 = the default
-    stream) of the current device."""
-    arr = (SeqikLegParams * n_legs)(*legs)
-    rc = load().seqik_link_frames_device(ctypes.c_void_p(int(d_angles) or None), int(n_seq), int(n_legs), int(n_frames),
-                                         arr, _fk_kind(kind), ctypes.c_void_p(int(d_origin) or None),
-                                         ctypes.c_void_p(int(d_frames) or None), ctypes.c_void_p(int(stream or 0) or None))
-    if rc != SEQIK_OK:
-        _raise(rc)
-
-
-#: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h
-GAPS_EXPORTED_SYMBOLS = ["seqik_gaps_compact_device", "seqik_gaps_expand_device", "seqik_solve_seq_gaps",
-                         "seqik_solve_generic_gaps"]
-#: status of a missing leg-frame in skip mode (``SEQIK_STATUS_MISSING``; scipy's statuses are -1..4)
-STATUS_MISSING = -100
-GAPS_SEQ, GAPS_GENERIC, GAPS_AFFINE = 0, 1, 2
-MISSING_MODES = ("raise", "skip")
-
-
-def check_missing_mode(missing) -> bool:
-    """True for ``"skip"``, False for ``"raise"``; anything else is a ``ValueError``."""
-    if missing not in MISSING_MODES:
-        raise ValueError(f"missing key points: expected one of {MISSING_MODES}, got {missing!r}")
-    return missing == "skip"
+def _data(a, pointer_type=_dp):
+    """``a.ctypes.data_as(pointer_type)`` of a numpy array; None = NULL."""
+    return a.ctypes.data_as(pointer_type) if a is not None else None
 
 
 def _ptr(x, name="buffer", shape=None, dtype="float64"):
     """A raw device pointer (int) or a tensor's ``data_ptr()``; 0 / None = NULL.  A tensor is checked against what the
-    kernel will read or write through the pointer: a contiguous GPU tensor of ``dtype`` with ``shape``'s element count."""
+    kernel will read or write through the pointer: a contiguous GPU tensor of ``dtype`` with ``shape``'s element count
+    (``shape=None``: the layout is not dense, the count is not checked)."""
     if x is None:
         return None
     if hasattr(x, "data_ptr"):
@@ -588,6 +381,138 @@ def _ptr(x, name="buffer", shape=None, dtype="float64"):
     return ctypes.c_void_p(int(x) or None)
 
 
+def _stream_ptr(stream):
+    """A hipStream_t as int or a torch stream; 0 / None = the default stream."""
+    if stream is None:
+        return None
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+    return ctypes.c_void_p(s or None)
+
+
+EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik.h"]]
+
+#: entry points of include/seqik_fk.h (forward kinematics from joint angles), kept apart from the ABI-7 set of seqik.h
+FK_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_fk.h"]]
+FK_KINDS = {"seq": 0, "generic": 1}
+
+
+def _fk_kind(kind) -> int:
+    if isinstance(kind, str):
+        if kind not in FK_KINDS:
+            raise ValueError(f"kind must be one of {sorted(FK_KINDS)}, got {kind!r}")
+        return FK_KINDS[kind]
+    return int(kind)
+
+
+def _angles_batch(angles, legs, kind):
+    """The checks ``forward_kinematics`` and ``link_frames`` share -> (angles, (S, L, N), kind as int)."""
+    angles = np.ascontiguousarray(angles, dtype=np.float64)
+    if angles.ndim != 4 or angles.shape[3] != 7:
+        raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
+    if len(legs) != angles.shape[1]:
+        raise ValueError("one SeqikLegParams per leg expected")
+    return angles, angles.shape[:3], _fk_kind(kind)
+
+
+def _origin_batch(origin, slf):
+    """``origin`` broadcast to a contiguous (S, L, N, 3) array; None stays None."""
+    if origin is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=np.float64), tuple(slf) + (3,)))
+
+
+def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_dist=False, device=-1):
+    """``seqik_forward_kinematics`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(fk (S, L, N, 9, 3),
+    dist (S, L, N, 4) or None), the rows the solvers write (``solve_seq`` / ``solve_generic``).
+
+    ``kind``: ``"seq"`` (KinematicChainSeq) or ``"generic"`` (KinematicChainGeneric) -- the chain that produced the angles.
+    The origin of each leg-frame is key point 0 of ``pose`` (S, L, N, 5, 3), or ``origin`` (anything that broadcasts to
+    (S, L, N, 3); the fused alignment's origin is ``template_coxa``), or 0 when neither is given (leg-local positions).
+    ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  An angle that is not finite or lies beyond
+    ``SEQIK_ANGLE_MAX`` (2^30 rad, include/seqik_fk.h) makes that leg-frame's rows (and distances) NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
+    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    if pose is not None and origin is not None:
+        raise ValueError("pass pose or origin, not both")
+    if want_dist and pose is None:
+        raise ValueError("want_dist needs pose (the key points to measure against)")
+    if pose is not None:
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        if pose.shape != (S, L, N, 5, 3):
+            raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    origin = _origin_batch(origin, (S, L, N))
+    fk = np.full((S, L, N, 9, 3), np.nan)
+    dist = np.full((S, L, N, 4), np.nan) if want_dist else None
+    _call("seqik_forward_kinematics", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(pose), _data(origin),
+          _data(fk), _data(dist), int(device))
+    return dict(fk=fk, dist=dist)
+
+
+def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kind="seq", d_pose=0, d_origin=0, d_dist=0,
+                              stream=0):
+    """``seqik_forward_kinematics_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``forward_kinematics``, asynchronous on ``stream`` (a hipStream_t as int, or a torch stream; 0 = the default stream)
+    of the current device."""
+    lf = (n_seq, n_legs, n_frames)
+    _call("seqik_forward_kinematics_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
+          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_pose, "pose", lf + (5, 3)),
+          _ptr(d_origin, "origin", lf + (3,)), _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_dist, "dist", lf + (4,)),
+          _stream_ptr(stream))
+
+
+#: entry points of include/seqik_frames.h (link frames from joint angles), kept apart from the ABI-7 set of seqik.h
+FRAMES_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_frames.h"]]
+
+
+def link_frames(angles, legs, kind="seq", origin=None, device=-1, rows3=False):
+    """``seqik_link_frames`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(frames (S, L, N, 9, 4, 4)),
+    the 4 x 4 frame of each of the nine links of the whole-leg chain in the chain's base frame -- what IKPy's
+    ``Chain.forward_kinematics(q, full_kinematics=True)`` returns, for every leg-frame of the batch.
+
+    ``kind``: ``"seq"`` (links base, ThC_yaw, ThC_pitch, ThC_roll, CTr_pitch, CTr_roll, FTi_pitch, TiTa_pitch, Claw) or
+    ``"generic"`` (base, ThC_roll, ThC_yaw, ThC_pitch, ...).  ``origin``: anything that broadcasts to (S, L, N, 3), added to
+    the translation column only; absent = leg-local frames.  The translation columns equal ``forward_kinematics``' rows
+    for the same angles, kind and origin bit for bit.  ``rows3=True`` returns the (S, L, N, 9, 3, 4) array as the library
+    wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  An angle that is not finite or lies beyond
+    ``SEQIK_ANGLE_MAX`` (2^30 rad) makes that leg-frame's frames NaN (with ``rows3=False`` the fourth row too)."""
+    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    origin = _origin_batch(origin, (S, L, N))
+    rows = np.full((S, L, N, 9, 3, 4), np.nan)
+    _call("seqik_link_frames", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(origin), _data(rows),
+          int(device))
+    if rows3:
+        return dict(frames=rows)
+    frames = np.empty((S, L, N, 9, 4, 4))
+    frames[..., :3, :] = rows
+    frames[..., 3, :] = (0.0, 0.0, 0.0, 1.0)
+    frames[..., 3, :][np.isnan(rows[..., 0, 0])] = np.nan
+    return dict(frames=frames)
+
+
+def link_frames_device(d_angles, n_seq, n_legs, n_frames, legs, d_frames, kind="seq", d_origin=0, stream=None):
+    """``seqik_link_frames_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_frames.h`` (``d_frames``: (S, L, N, 9, 3, 4) doubles), asynchronous on ``stream`` (a hipStream_t as
+    int, or a torch stream; None / 0 = the default stream) of the current device."""
+    lf = (n_seq, n_legs, n_frames)
+    _call("seqik_link_frames_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
+          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_origin, "origin", lf + (3,)),
+          _ptr(d_frames, "frames", lf + (9, 3, 4)), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h
+GAPS_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_gaps.h"]]
+#: status of a missing leg-frame in skip mode (``SEQIK_STATUS_MISSING``; scipy's statuses are -1..4)
+STATUS_MISSING = -100
+GAPS_SEQ, GAPS_GENERIC, GAPS_AFFINE = 0, 1, 2
+MISSING_MODES = ("raise", "skip")
+
+
+def check_missing_mode(missing) -> bool:
+    """True for ``"skip"``, False for ``"raise"``; anything else is a ``ValueError``."""
+    if missing not in MISSING_MODES:
+        raise ValueError(f"missing key points: expected one of {MISSING_MODES}, got {missing!r}")
+    return missing == "skip"
+
+
 def _gaps_flags(kind, affine) -> int:
     return (GAPS_GENERIC if _fk_kind(kind) == 1 else GAPS_SEQ) | (GAPS_AFFINE if affine else 0)
 
@@ -598,14 +523,10 @@ def gaps_compact_device(d_pose, n_seq, n_legs, n_frames, legs, d_cpose, d_map, d
     frame map (S, L, N) int32 (compact slot, -1 = missing) and n_valid (S, L) int32.  Raw device pointers (ints) or torch
     tensors; asynchronous on ``stream`` (a hipStream_t as int, or a torch stream).  ``kind`` ("seq" / "generic") and
     ``affine`` (the solve will use the fused alignment) decide which key points count (include/seqik_gaps.h)."""
-    arr = (SeqikLegParams * n_legs)(*legs)
     lf, ch = (n_seq, n_legs, n_frames), (n_seq, n_legs)
-    rc = load().seqik_gaps_compact_device(_ptr(d_pose, "pose", lf + (5, 3)), int(n_seq), int(n_legs), int(n_frames),
-                                          _gaps_flags(kind, affine), arr, _ptr(d_cpose, "cpose", lf + (5, 3)),
-                                          _ptr(d_map, "map", lf, "int32"), _ptr(d_n_valid, "n_valid", ch, "int32"),
-                                          _stream_ptr(stream))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_gaps_compact_device", _ptr(d_pose, "pose", lf + (5, 3)), int(n_seq), int(n_legs), int(n_frames),
+          _gaps_flags(kind, affine), (SeqikLegParams * n_legs)(*legs), _ptr(d_cpose, "cpose", lf + (5, 3)),
+          _ptr(d_map, "map", lf, "int32"), _ptr(d_n_valid, "n_valid", ch, "int32"), _stream_ptr(stream))
 
 
 def gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cfk=0, d_fk=0, d_cstatus=0, d_status=0,
@@ -614,21 +535,11 @@ def gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cf
     ``STATUS_MISSING`` and 0 at the missing frames.  fk, status and nfev are optional pairs."""
     lf = (n_seq, n_legs, n_frames)
     sw = (1,) if _fk_kind(kind) == 1 else (4,)
-    rc = load().seqik_gaps_expand_device(_ptr(d_map, "map", lf, "int32"), int(n_seq), int(n_legs), int(n_frames),
-                                         _gaps_flags(kind, False), _ptr(d_cangles, "cangles", lf + (7,)),
-                                         _ptr(d_cfk, "cfk", lf + (9, 3)), _ptr(d_cstatus, "cstatus", lf + sw, "int32"),
-                                         _ptr(d_cnfev, "cnfev", lf + sw, "int32"), _ptr(d_angles, "angles", lf + (7,)),
-                                         _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_status, "status", lf + sw, "int32"),
-                                         _ptr(d_nfev, "nfev", lf + sw, "int32"), _stream_ptr(stream))
-    if rc != SEQIK_OK:
-        _raise(rc)
-
-
-def _stream_ptr(stream):
-    if stream is None:
-        return None
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
-    return ctypes.c_void_p(s or None)
+    _call("seqik_gaps_expand_device", _ptr(d_map, "map", lf, "int32"), int(n_seq), int(n_legs), int(n_frames),
+          _gaps_flags(kind, False), _ptr(d_cangles, "cangles", lf + (7,)), _ptr(d_cfk, "cfk", lf + (9, 3)),
+          _ptr(d_cstatus, "cstatus", lf + sw, "int32"), _ptr(d_cnfev, "cnfev", lf + sw, "int32"),
+          _ptr(d_angles, "angles", lf + (7,)), _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_status, "status", lf + sw, "int32"),
+          _ptr(d_nfev, "nfev", lf + sw, "int32"), _stream_ptr(stream))
 
 
 def solve_seq_gaps_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_cpose, d_map, d_n_valid, d_cangles,
@@ -669,8 +580,7 @@ def solve_seq_gaps_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_cpo
 
 
 #: entry points of include/seqik_resample.h (PCHIP resampling of joint angles), kept apart from the ABI-7 set of seqik.h
-RESAMPLE_EXPORTED_SYMBOLS = ["seqik_resample_count", "seqik_resample_workspace_bytes", "seqik_resample_pchip",
-                             "seqik_resample_pchip_device"]
+RESAMPLE_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_resample.h"]]
 RESAMPLE_BRIDGE = 1
 RESAMPLE_MODES = ("error", "bridge")
 RESAMPLE_MAX_WIDTH = 16
@@ -720,10 +630,8 @@ def resample_pchip(y, original_ts, new_ts, missing="error", max_gap=None, device
     n_out = resample_count(N, original_ts, new_ts)
     C = int(np.prod(y.shape[:-2], dtype=np.int64))
     out = np.full(y.shape[:-2] + (n_out, W), np.nan)
-    rc = load().seqik_resample_pchip(y.ctypes.data_as(_dp), C, N, W, float(original_ts), float(new_ts), flags, gap,
-                                     out.ctypes.data_as(_dp), n_out, int(device))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_resample_pchip", _data(y), C, N, W, float(original_ts), float(new_ts), flags, gap, _data(out), n_out,
+          int(device))
     return out
 
 
@@ -742,30 +650,46 @@ def resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d
     flags, gap = _resample_flags(missing, max_gap)
     n_out = resample_count(n_frames, original_ts, new_ts)
     ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
-    rc = load().seqik_resample_pchip_device(_ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
-                                            int(width), float(original_ts), float(new_ts), flags, gap,
-                                            _ptr(d_out, "out", (n_chains, n_out, width)), n_out, ws, _stream_ptr(stream))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_resample_pchip_device", _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
+          int(width), float(original_ts), float(new_ts), flags, gap, _ptr(d_out, "out", (n_chains, n_out, width)), n_out,
+          ws, _stream_ptr(stream))
     return n_out
 
 
 #: entry points of include/seqik_head_align.h (antenna alignment on the GPU), kept apart from the ABI-7 set of seqik.h
-HEAD_ALIGN_EXPORTED_SYMBOLS = ["seqik_head_align_stats_open", "seqik_head_align_stats_select",
-                               "seqik_head_align_stats_pick", "seqik_head_align_stats_close", "seqik_head_angles_raw",
-                               "seqik_head_angles_raw_device"]
+HEAD_ALIGN_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_head_align.h"]]
 #: what the antenna-alignment kernels are compiled from (``csrc_sha256(HEAD_ALIGN_SOURCES)`` ties
 #: profiles/head_align.json to a build; ``KERNEL_SOURCES`` stays the solver's own set)
 HEAD_ALIGN_SOURCES = ["seqik_head.hpp", "seqik_head_align.hpp", "seqik_head_align.hip"]
 HEAD_STAT_THRESHOLD = 5e-5
 
 
-def _head_arrays(r_head, l_head, min_points=1):
+def _head_arrays(r_head, l_head, min_points=1, points="key points >= {}"):
     r_head = np.ascontiguousarray(r_head, dtype=np.float64)
     l_head = np.ascontiguousarray(l_head, dtype=np.float64)
     if r_head.ndim != 3 or r_head.shape[2] != 3 or r_head.shape[1] < min_points or l_head.shape != r_head.shape:
-        raise ValueError(f"R_head / L_head must have the same shape (N, key points >= {min_points}, 3)")
+        raise ValueError(f"R_head / L_head must have the same shape (N, {points.format(min_points)}, 3)")
     return r_head, l_head
+
+
+def _head_inputs(r_head, l_head, neck, compute_ant, head_roll, **shape_text):
+    """What ``head_angles`` and ``head_angles_raw`` prepare alike -> (r_head, l_head, N, K, neck, neck stride, head_roll
+    (N,) or None, zeroed angles (7 or 3, N))."""
+    r_head, l_head = _head_arrays(r_head, l_head, **shape_text)
+    n, k = r_head.shape[:2]
+    if compute_ant and k < 2:
+        # what the reference's get_ant_vector runs into (head_inverse_kinematics.py:159-161)
+        raise IndexError(f"index 1 is out of bounds for axis 1 with size {k}: the antenna angles need the antenna base "
+                         "and tip; call compute_head_angles(compute_ant_angles=False)")
+    neck = np.ascontiguousarray(neck, dtype=np.float64).reshape(-1, 3)
+    if neck.shape[0] not in (1, n):
+        raise ValueError("Neck must hold one point or one point per frame")
+    stride = 3 if (neck.shape[0] == n and n > 1) else 0
+    if head_roll is not None and compute_ant:
+        head_roll = np.ascontiguousarray(np.broadcast_to(np.asarray(head_roll, dtype=np.float64).reshape(-1), (n,)))
+    else:
+        head_roll = None
+    return r_head, l_head, n, k, neck, stride, head_roll, np.zeros((7 if compute_ant else 3, n))
 
 
 def head_align_stats(r_head, l_head, thorax, ranks_for, threshold=HEAD_STAT_THRESHOLD, device=-1):
@@ -784,22 +708,13 @@ def head_align_stats(r_head, l_head, thorax, ranks_for, threshold=HEAD_STAT_THRE
         raise ValueError(f"Thorax must have shape ({n}, key points, 3), got {thorax.shape}")
     if n < 3:
         raise ValueError(f"the stationary-frame test needs at least 3 frames, got {n}")
-    lib = load()
     h = ctypes.c_void_p()
-    opt = SeqikOptions()
-    opt.device = device
-    rc = lib.seqik_head_align_stats_open(ctypes.byref(h), n, ctypes.byref(opt))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_head_align_stats_open", ctypes.byref(h), n, ctypes.byref(SeqikOptions(device=device)))
     try:
         n_stat = np.zeros(2, dtype=np.int64)
         bad = ctypes.c_int64(0)
-        i64p = ctypes.POINTER(ctypes.c_int64)
-        rc = lib.seqik_head_align_stats_select(h, r_head.ctypes.data, l_head.ctypes.data, thorax.ctypes.data, 0, n,
-                                               r_head.shape[1], thorax.shape[1], float(threshold),
-                                               n_stat.ctypes.data_as(i64p), ctypes.byref(bad))
-        if rc != SEQIK_OK:
-            _raise(rc)
+        _call("seqik_head_align_stats_select", h, r_head.ctypes.data, l_head.ctypes.data, thorax.ctypes.data, 0, n,
+              r_head.shape[1], thorax.shape[1], float(threshold), _data(n_stat, _i64p), ctypes.byref(bad))
         out = dict(n_stat=n_stat, n_nonfinite=int(bad.value), order=None)
         if bad.value or not n_stat.all():
             return out
@@ -808,14 +723,12 @@ def head_align_stats(r_head, l_head, thorax, ranks_for, threshold=HEAD_STAT_THRE
         if ranks_stat.ndim != 2 or ranks_stat.shape[1] != ranks_all.shape[0]:
             raise ValueError("ranks_for must return the same number of ranks for every size")
         order = np.zeros((2, 5, ranks_all.shape[0]))
-        rc = lib.seqik_head_align_stats_pick(h, ranks_stat.ctypes.data_as(i64p), ranks_all.ctypes.data_as(i64p),
-                                             ranks_all.shape[0], order.ctypes.data_as(_dp))
-        if rc != SEQIK_OK:
-            _raise(rc)
+        _call("seqik_head_align_stats_pick", h, _data(ranks_stat, _i64p), _data(ranks_all, _i64p), ranks_all.shape[0],
+              _data(order))
         out["order"] = order
         return out
     finally:
-        lib.seqik_head_align_stats_close(h)
+        load().seqik_head_align_stats_close(h)
 
 
 def _head_affine_pair(affine):
@@ -834,31 +747,12 @@ def head_angles_raw(r_head, l_head, neck, rest_head_pitch, rest_antenna_pitch, a
     ``SeqikHeadAffine``) applied in the kernel's prologue.  Returns the (7 or 3, N) angles -- the bits ``head_angles``
     gives on the host-aligned points -- or, with ``want_aligned``, ``(angles, r_aligned, l_aligned)`` with the aligned
     key points (N, min(K, 2), 3)."""
-    r_head, l_head = _head_arrays(r_head, l_head)
-    n, k = r_head.shape[:2]
-    if compute_ant and k < 2:
-        raise IndexError(f"index 1 is out of bounds for axis 1 with size {k}: the antenna angles need the antenna base "
-                         "and tip; call compute_head_angles(compute_ant_angles=False)")
-    neck = np.ascontiguousarray(neck, dtype=np.float64).reshape(-1, 3)
-    if neck.shape[0] not in (1, n):
-        raise ValueError("Neck must hold one point or one point per frame")
-    stride = 3 if (neck.shape[0] == n and n > 1) else 0
-    roll_p = None
-    if head_roll is not None and compute_ant:
-        head_roll = np.ascontiguousarray(np.broadcast_to(np.asarray(head_roll, dtype=np.float64).reshape(-1), (n,)))
-        roll_p = head_roll.ctypes.data_as(_dp)
-    out = np.zeros((7 if compute_ant else 3, n))
+    r_head, l_head, n, k, neck, stride, head_roll, out = _head_inputs(r_head, l_head, neck, compute_ant, head_roll)
     r_al = np.zeros((n, min(k, 2), 3)) if want_aligned else None
     l_al = np.zeros((n, min(k, 2), 3)) if want_aligned else None
-    opt = SeqikOptions()
-    opt.device = device
-    rc = load().seqik_head_angles_raw(r_head.ctypes.data_as(_dp), l_head.ctypes.data_as(_dp), n, k,
-                                      neck.ctypes.data_as(_dp), stride, float(rest_head_pitch), float(rest_antenna_pitch),
-                                      1 if compute_ant else 0, roll_p, _head_affine_pair(affine), out.ctypes.data_as(_dp),
-                                      r_al.ctypes.data_as(_dp) if want_aligned else None,
-                                      l_al.ctypes.data_as(_dp) if want_aligned else None, ctypes.byref(opt))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_head_angles_raw", _data(r_head), _data(l_head), n, k, _data(neck), stride, float(rest_head_pitch),
+          float(rest_antenna_pitch), 1 if compute_ant else 0, _data(head_roll), _head_affine_pair(affine), _data(out),
+          _data(r_al), _data(l_al), ctypes.byref(SeqikOptions(device=device)))
     return (out, r_al, l_al) if want_aligned else out
 
 
@@ -870,14 +764,11 @@ def head_angles_raw_device(d_r_head, d_l_head, n_frames, n_points, d_neck, neck_
     (a hipStream_t as int, or a torch stream) of the current device."""
     n, k = int(n_frames), int(n_points)
     al = (n, min(k, 2), 3)
-    rc = load().seqik_head_angles_raw_device(_ptr(d_r_head, "r_head", (n, k, 3)), _ptr(d_l_head, "l_head", (n, k, 3)), n, k,
-                                             _ptr(d_neck, "neck", (n if neck_stride else 1, 3)), int(neck_stride),
-                                             float(rest_head_pitch), float(rest_antenna_pitch), 1 if compute_ant else 0,
-                                             _ptr(d_head_roll, "head_roll", (n,)), _head_affine_pair(affine),
-                                             _ptr(d_angles, "angles", (7, n)), _ptr(d_r_aligned, "r_aligned", al),
-                                             _ptr(d_l_aligned, "l_aligned", al), _stream_ptr(stream))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_head_angles_raw_device", _ptr(d_r_head, "r_head", (n, k, 3)), _ptr(d_l_head, "l_head", (n, k, 3)), n, k,
+          _ptr(d_neck, "neck", (n if neck_stride else 1, 3)), int(neck_stride), float(rest_head_pitch),
+          float(rest_antenna_pitch), 1 if compute_ant else 0, _ptr(d_head_roll, "head_roll", (n,)),
+          _head_affine_pair(affine), _ptr(d_angles, "angles", (7, n)), _ptr(d_r_aligned, "r_aligned", al),
+          _ptr(d_l_aligned, "l_aligned", al), _stream_ptr(stream))
 
 
 class AlignStats:
@@ -888,36 +779,30 @@ class AlignStats:
     def __init__(self, n_legs, capacity_frames, device=-1):
         self.n_legs = int(n_legs)
         self._h = ctypes.c_void_p()
-        opt = SeqikOptions()
-        opt.device = device
-        rc = load().seqik_align_stats_open(ctypes.byref(self._h), self.n_legs, int(capacity_frames), ctypes.byref(opt))
-        if rc != SEQIK_OK:
+        try:
+            _call("seqik_align_stats_open", ctypes.byref(self._h), self.n_legs, int(capacity_frames),
+                  ctypes.byref(SeqikOptions(device=device)))
+        except Exception:
             self._h = ctypes.c_void_p()
-            _raise(rc)
+            raise
 
     def add(self, pose, n_seq=None, n_frames=None, layout=None, on_device=False, stream=0):
-        if on_device:
-            ptr = ctypes.c_void_p(int(pose))
+        if on_device:  # a raw device pointer or a tensor (its element count is checked in the dense layout only)
+            ptr = _ptr(pose, "pose", None if layout is not None else (n_seq, self.n_legs, n_frames, 5, 3))
         else:
             pose = np.ascontiguousarray(pose, dtype=np.float64)
             if layout is None:
                 if pose.ndim != 5 or pose.shape[1] != self.n_legs or pose.shape[3:] != (5, 3):
                     raise ValueError(f"pose must have shape (S, {self.n_legs}, N, 5, 3), got {pose.shape}")
                 n_seq, n_frames = pose.shape[0], pose.shape[2]
-            ptr = ctypes.c_void_p(pose.ctypes.data)
-        rc = load().seqik_align_stats_add(self._h, ptr, 1 if on_device else 0, int(n_seq), int(n_frames),
-                                          ctypes.byref(layout) if layout is not None else None,
-                                          ctypes.c_void_p(stream or None))
-        if rc != SEQIK_OK:
-            _raise(rc)
+            ptr = pose.ctypes.data
+        _call("seqik_align_stats_add", self._h, ptr, 1 if on_device else 0, int(n_seq), int(n_frames),
+              ctypes.byref(layout) if layout is not None else None, _stream_ptr(stream))
 
     def finish(self, ranks, stream=0):
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         out = np.zeros((self.n_legs, 7, len(ranks)))
-        rc = load().seqik_align_stats_finish(self._h, ranks.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(ranks),
-                                             out.ctypes.data_as(_dp), ctypes.c_void_p(stream or None))
-        if rc != SEQIK_OK:
-            _raise(rc)
+        _call("seqik_align_stats_finish", self._h, _data(ranks, _i64p), len(ranks), _data(out), _stream_ptr(stream))
         return out
 
     def reset(self):
@@ -955,25 +840,19 @@ class PeerBuffer:
             self.ptr = _mapped_ptr
         else:
             p = ctypes.c_void_p()
-            rc = load().seqik_peer_alloc(ctypes.byref(p), self.nbytes)
-            if rc != SEQIK_OK:
-                _raise(rc)
+            _call("seqik_peer_alloc", ctypes.byref(p), self.nbytes)
             self.ptr = p.value
 
     @classmethod
     def open(cls, handle: bytes, nbytes):
         assert len(handle) == PEER_HANDLE_BYTES
         p = ctypes.c_void_p()
-        rc = load().seqik_peer_open(handle, ctypes.byref(p))
-        if rc != SEQIK_OK:
-            _raise(rc)
+        _call("seqik_peer_open", handle, ctypes.byref(p))
         return cls(nbytes, _mapped_ptr=p.value)
 
     def handle(self) -> bytes:
         buf = ctypes.create_string_buffer(PEER_HANDLE_BYTES)
-        rc = load().seqik_peer_export(self.ptr, buf)
-        if rc != SEQIK_OK:
-            _raise(rc)
+        _call("seqik_peer_export", self.ptr, buf)
         return buf.raw
 
     @property
@@ -986,32 +865,25 @@ class PeerBuffer:
 
     def close(self):
         if self.ptr:
-            rc = load().seqik_peer_close(self.ptr) if self.mapped else load().seqik_peer_free(self.ptr)
-            self.ptr = None
-            if rc != SEQIK_OK:
-                _raise(rc)
+            ptr, self.ptr = self.ptr, None
+            _call("seqik_peer_close" if self.mapped else "seqik_peer_free", ptr)
 
 
 def peer_copy(dst_ptr, src_ptr, nbytes, stream=0):
-    """``seqik_peer_copy``: asynchronous device-to-device copy on ``stream`` (raw pointers)."""
-    rc = load().seqik_peer_copy(dst_ptr, src_ptr, nbytes, ctypes.c_void_p(stream))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    """``seqik_peer_copy``: asynchronous device-to-device copy of ``nbytes`` on ``stream`` (raw pointers or float64
+    tensors; a hipStream_t as int or a torch stream)."""
+    _call("seqik_peer_copy", _ptr(dst_ptr, "dst"), _ptr(src_ptr, "src"), nbytes, _stream_ptr(stream))
 
 
 def release_workspaces():
     """Frees the per-stream stage hand-off workspaces the library keeps between calls (drains the device)."""
-    rc = load().seqik_release_workspaces()
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_release_workspaces")
 
 
 def device_attributes(device=0):
     """(compute units, peak clock in kHz, HBM bytes) of a GPU."""
     cu, khz, mem = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
-    rc = load().seqik_device_attributes(device, ctypes.byref(cu), ctypes.byref(khz), ctypes.byref(mem))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_device_attributes", device, ctypes.byref(cu), ctypes.byref(khz), ctypes.byref(mem))
     return cu.value, khz.value, mem.value
 
 
@@ -1024,45 +896,14 @@ def solve_generic(pose, legs, want_fk=True, want_diag=False, device=-1, block_si
     ``missing``: ``"raise"`` or ``"skip"`` as for ``solve_seq`` (``seqik_solve_generic_gaps``; rows 0 and 4 count, row 4
     only with ``affine``); skip mode adds ``n_valid`` (S, L)."""
     skip = check_missing_mode(missing)
-    pose = np.ascontiguousarray(pose, dtype=np.float64)
-    if pose.ndim != 5 or pose.shape[3:] != (5, 3):
-        raise ValueError(f"pose must have shape (S, L, N, 5, 3), got {pose.shape}")
-    S, L, N = pose.shape[:3]
-    if len(legs) != L:
-        raise ValueError("one SeqikLegParams per leg expected")
-    if not skip:
-        _check_finite(pose)
-    angles = np.zeros((S, L, N, 7))
-    fk = np.full((S, L, N, 9, 3), np.nan) if want_fk else None
-    status = np.full((S, L, N), -1, dtype=np.int32) if want_diag else None
-    nfev = np.zeros((S, L, N), dtype=np.int32) if want_diag else None
-    if init_angles is not None:
-        init_angles = np.ascontiguousarray(init_angles, dtype=np.float64)
-        if init_angles.shape != (S, L, 7):
-            raise ValueError(f"init_angles must have shape {(S, L, 7)}")
-    opt = SeqikOptions()
-    opt.device = device
-    opt.block_size = block_size
-    opt.reserved[0] = lanes_per_wave
-    opt.reserved[1] = chain_queue
-    opt.reserved[3] = 0 if lane_groups else 3  # measurements: thin waves without the split over groups of 8 lanes
-    args = (pose.ctypes.data_as(_dp), S, L, N, (SeqikLegParams * L)(*legs),
-            angles.ctypes.data_as(_dp), fk.ctypes.data_as(_dp) if fk is not None else None,
-            status.ctypes.data_as(_ip) if status is not None else None,
-            nfev.ctypes.data_as(_ip) if nfev is not None else None,
-            init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
-            _affine_array(affine, L), ctypes.byref(opt))
-    if skip:
-        n_valid = np.zeros((S, L), dtype=np.int32)
-        rc = load().seqik_solve_generic_gaps(*args, n_valid.ctypes.data_as(_ip))
-    else:
-        rc = load().seqik_solve_generic(*args)
-    if rc != SEQIK_OK:
-        _raise(rc)
-    out = dict(angles=angles, fk=fk, status=status, nfev=nfev)
-    if skip:
-        out["n_valid"] = n_valid
-    return out
+    pose, (S, L, N) = _pose_batch(pose, legs, skip)
+    out = dict(angles=np.zeros((S, L, N, 7)), fk=np.full((S, L, N, 9, 3), np.nan) if want_fk else None,
+               status=np.full((S, L, N), -1, dtype=np.int32) if want_diag else None,
+               nfev=np.zeros((S, L, N), dtype=np.int32) if want_diag else None)
+    # reserved[3] = 3 (measurements): thin waves without the split over groups of 8 lanes
+    opt = SeqikOptions(device=device, block_size=block_size,
+                       reserved=(lanes_per_wave, chain_queue, 0, 0 if lane_groups else 3))
+    return _solve_host("seqik_solve_generic", skip, pose, legs, (), out, init_angles, affine, opt)
 
 
 def head_angles(r_head, l_head, neck, rest_head_pitch, rest_antenna_pitch, compute_ant=True, device=-1, head_roll=None):
@@ -1070,33 +911,11 @@ def head_angles(r_head, l_head, neck, rest_head_pitch, rest_antenna_pitch, compu
 
     K = key points per side: point 0 gives the head angles, point 1 (the antenna tip) the antenna angles; K = 1 is
     allowed without them.  ``head_roll`` (N,): derotate the antenna vectors by this roll instead of the frame's own."""
-    r_head = np.ascontiguousarray(r_head, dtype=np.float64)
-    l_head = np.ascontiguousarray(l_head, dtype=np.float64)
-    n = r_head.shape[0]
-    if r_head.ndim != 3 or r_head.shape[2] != 3 or r_head.shape[1] < 1 or l_head.shape != r_head.shape:
-        raise ValueError("R_head / L_head must have the same shape (N, key points, 3)")
-    k = r_head.shape[1]
-    if compute_ant and k < 2:
-        # what the reference's get_ant_vector runs into (head_inverse_kinematics.py:159-161)
-        raise IndexError(f"index 1 is out of bounds for axis 1 with size {k}: the antenna angles need the antenna base "
-                         "and tip; call compute_head_angles(compute_ant_angles=False)")
-    neck = np.ascontiguousarray(neck, dtype=np.float64).reshape(-1, 3)
-    if neck.shape[0] not in (1, n):
-        raise ValueError("Neck must hold one point or one point per frame")
-    stride = 3 if (neck.shape[0] == n and n > 1) else 0
-    roll_p = None
-    if head_roll is not None and compute_ant:
-        head_roll = np.ascontiguousarray(np.broadcast_to(np.asarray(head_roll, dtype=np.float64).reshape(-1), (n,)))
-        roll_p = head_roll.ctypes.data_as(_dp)
-    out = np.zeros((7 if compute_ant else 3, n))
-    opt = SeqikOptions()
-    opt.device = device
-    rc = load().seqik_head_angles_ex(r_head.ctypes.data_as(_dp), l_head.ctypes.data_as(_dp), n, k,
-                                     neck.ctypes.data_as(_dp), stride, float(rest_head_pitch),
-                                     float(rest_antenna_pitch), 1 if compute_ant else 0, roll_p,
-                                     out.ctypes.data_as(_dp), ctypes.byref(opt))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    r_head, l_head, n, k, neck, stride, head_roll, out = _head_inputs(r_head, l_head, neck, compute_ant, head_roll,
+                                                                      points="key points")
+    _call("seqik_head_angles_ex", _data(r_head), _data(l_head), n, k, _data(neck), stride, float(rest_head_pitch),
+          float(rest_antenna_pitch), 1 if compute_ant else 0, _data(head_roll), _data(out),
+          ctypes.byref(SeqikOptions(device=device)))
     return out
 
 
@@ -1110,13 +929,8 @@ def signed_angles(v1, v2, rot_axis, device=-1):
     if v1.shape[0] not in (1, n) or v2.shape[0] not in (1, n):
         raise ValueError(f"operands could not be broadcast together with shapes {v1.shape} {v2.shape}")
     out = np.zeros(n)
-    opt = SeqikOptions()
-    opt.device = device
-    rc = load().seqik_signed_angles(v1.ctypes.data_as(_dp), 3 if v1.shape[0] == n and n > 1 else 0, v2.ctypes.data_as(_dp),
-                                    3 if v2.shape[0] == n and n > 1 else 0, axis.ctypes.data_as(_dp), n,
-                                    out.ctypes.data_as(_dp), ctypes.byref(opt))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_signed_angles", _data(v1), 3 if v1.shape[0] == n and n > 1 else 0, _data(v2),
+          3 if v2.shape[0] == n and n > 1 else 0, _data(axis), n, _data(out), ctypes.byref(SeqikOptions(device=device)))
     return out
 
 
@@ -1150,20 +964,8 @@ def leg_params_from_arrays(seg, bounds, seeds) -> SeqikLegParams:
     return lp
 
 
-def _raise(rc: int):
-    msg = load().seqik_last_error().decode("utf-8", "replace")
-    if rc in (ERR_X0, ERR_BOUNDS, ERR_STAGE):
-        raise ValueError(msg)
-    if rc == ERR_ARG:
-        raise ValueError(f"seqik: bad argument: {msg}")
-    raise SeqikLibraryError(f"seqik: HIP error: {msg}")
-
-
 def validate_legs(legs, first_stage=1, last_stage=4):
-    arr = (SeqikLegParams * len(legs))(*legs)
-    rc = load().seqik_validate_legs(arr, len(legs), first_stage, last_stage)
-    if rc != SEQIK_OK:
-        _raise(rc)
+    _call("seqik_validate_legs", (SeqikLegParams * len(legs))(*legs), len(legs), first_stage, last_stage)
 
 
 def _check_finite(pose):
@@ -1179,6 +981,47 @@ def _affine_array(affine, n_legs):
     if len(affine) != n_legs:
         raise ValueError("one SeqikAffine per leg expected")
     return (SeqikAffine * n_legs)(*affine)
+
+
+def _pose_batch(pose, legs, skip):
+    """The checks ``solve_seq`` and ``solve_generic`` share -> (pose as a contiguous float64 array, (S, L, N))."""
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.ndim != 5 or pose.shape[3:] != (5, 3):
+        raise ValueError(f"pose must have shape (S, L, N, 5, 3), got {pose.shape}")
+    if len(legs) != pose.shape[1]:
+        raise ValueError("one SeqikLegParams per leg expected")
+    if not skip:
+        _check_finite(pose)
+    return pose, pose.shape[:3]
+
+
+def _solve_host(name, skip, pose, legs, stages, out, init_angles, affine, opt):
+    """Runs the host solver ``name`` -- in skip mode its ``_gaps`` twin, which also fills ``out["n_valid"]`` (S, L) -- into
+    the arrays of ``out`` (angles, and fk / status / nfev or None) and returns ``out``."""
+    S, L, N = pose.shape[:3]
+    if init_angles is not None:
+        init_angles = np.ascontiguousarray(init_angles, dtype=np.float64)
+        if init_angles.shape != (S, L, 7):
+            raise ValueError(f"init_angles must have shape {(S, L, 7)}")
+    args = (_data(pose), S, L, N, (SeqikLegParams * L)(*legs), *stages, _data(out["angles"]), _data(out["fk"]),
+            _data(out["status"], _ip), _data(out["nfev"], _ip), _data(init_angles), _affine_array(affine, L),
+            ctypes.byref(opt))
+    if skip:
+        out["n_valid"] = np.zeros((S, L), dtype=np.int32)
+        _call(name + "_gaps", *args, _data(out["n_valid"], _ip))
+    else:
+        _call(name, *args)
+    return out
+
+
+def _solve_options(block_size, lanes_per_wave, staged, interleave_legs, pipeline, frame_chunk, frame_halo, chunk_tol,
+                   chunk_rounds) -> SeqikOptions:
+    """``SeqikOptions`` with the launch and frame-chunk options ``solve_seq`` and ``solve_seq_device`` share."""
+    opt = SeqikOptions()
+    opt.block_size = block_size
+    opt.reserved[0], opt.reserved[1], opt.reserved[2], opt.reserved[3] = lanes_per_wave, staged, interleave_legs, pipeline
+    opt.frame_chunk, opt.frame_halo, opt.chunk_tol, opt.chunk_rounds = frame_chunk, frame_halo, chunk_tol, chunk_rounds
+    return opt
 
 
 def solve_seq(pose, legs, first_stage=1, last_stage=4, angles=None, want_fk=True, want_diag=False,
@@ -1207,65 +1050,32 @@ def solve_seq(pose, legs, first_stage=1, last_stage=4, angles=None, want_fk=True
     Returns dict(angles, fk or None, status or None, nfev or None, chunk_stats, chunk_flags).
     """
     skip = check_missing_mode(missing)
-    pose = np.ascontiguousarray(pose, dtype=np.float64)
-    if pose.ndim != 5 or pose.shape[3:] != (5, 3):
-        raise ValueError(f"pose must have shape (S, L, N, 5, 3), got {pose.shape}")
-    S, L, N = pose.shape[:3]
-    if len(legs) != L:
-        raise ValueError("one SeqikLegParams per leg expected")
+    pose, (S, L, N) = _pose_batch(pose, legs, skip)
     if skip and (first_stage, last_stage) != (1, 4):
         raise ValueError("missing='skip' needs all four stages (first_stage=1, last_stage=4)")
     if skip and want_chunk_flags:
         raise ValueError("missing='skip' does not report chunk_flags")
-    if not skip:
-        _check_finite(pose)
     if angles is None:
         angles = np.zeros((S, L, N, 7), dtype=np.float64)
     else:
         angles = np.array(angles, dtype=np.float64, order="C", copy=True)
         if angles.shape != (S, L, N, 7):
             raise ValueError(f"angles must have shape {(S, L, N, 7)}")
-    fk = np.full((S, L, N, 9, 3), np.nan) if (want_fk and last_stage == 4) else None
-    status = np.full((S, L, N, 4), -1, dtype=np.int32) if want_diag else None
-    nfev = np.zeros((S, L, N, 4), dtype=np.int32) if want_diag else None
-    arr = (SeqikLegParams * L)(*legs)
-    opt = SeqikOptions()
-    opt.device = device
-    opt.block_size = block_size
-    opt.reserved[0] = lanes_per_wave
-    opt.reserved[1] = staged
-    opt.reserved[2] = interleave_legs
-    opt.reserved[3] = pipeline
-    opt.frame_chunk, opt.frame_halo, opt.chunk_tol, opt.chunk_rounds = frame_chunk, frame_halo, chunk_tol, chunk_rounds
+    out = dict(angles=angles, fk=np.full((S, L, N, 9, 3), np.nan) if (want_fk and last_stage == 4) else None,
+               status=np.full((S, L, N, 4), -1, dtype=np.int32) if want_diag else None,
+               nfev=np.zeros((S, L, N, 4), dtype=np.int32) if want_diag else None)
     stats = np.zeros(N_CHUNK_STATS, dtype=np.int32)
-    opt.chunk_stats = stats.ctypes.data_as(_ip)
-    if init_angles is not None:
-        init_angles = np.ascontiguousarray(init_angles, dtype=np.float64)
-        if init_angles.shape != (S, L, 7):
-            raise ValueError(f"init_angles must have shape {(S, L, 7)}")
-    lib = load()
+    opt = _solve_options(block_size, lanes_per_wave, staged, interleave_legs, pipeline, frame_chunk, frame_halo, chunk_tol,
+                         chunk_rounds)
+    opt.device, opt.chunk_stats = device, _data(stats, _ip)
     flags = None
     if want_chunk_flags and frame_chunk != 0 and first_stage == 1 and last_stage == 4 and not want_diag:
         k = frame_chunk_plan(N, frame_chunk, frame_halo)[2]
         if k > 0:
             flags = np.zeros((S, L, k), dtype=np.uint8)
-            opt.chunk_flags = flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-    common = (angles.ctypes.data_as(_dp), fk.ctypes.data_as(_dp) if fk is not None else None,
-              status.ctypes.data_as(_ip) if status is not None else None,
-              nfev.ctypes.data_as(_ip) if nfev is not None else None,
-              init_angles.ctypes.data_as(_dp) if init_angles is not None else None,
-              _affine_array(affine, L), ctypes.byref(opt))
-    if skip:
-        n_valid = np.zeros((S, L), dtype=np.int32)
-        rc = lib.seqik_solve_seq_gaps(pose.ctypes.data_as(_dp), S, L, N, arr, first_stage, last_stage, *common,
-                                      n_valid.ctypes.data_as(_ip))
-    else:
-        rc = lib.seqik_solve_seq(pose.ctypes.data_as(_dp), S, L, N, arr, first_stage, last_stage, *common)
-    if rc != SEQIK_OK:
-        _raise(rc)
-    out = dict(angles=angles, fk=fk, status=status, nfev=nfev, chunk_stats=chunk_stats_dict(stats), chunk_flags=flags)
-    if skip:
-        out["n_valid"] = n_valid
+            opt.chunk_flags = _data(flags, _u8p)
+    _solve_host("seqik_solve_seq", skip, pose, legs, (first_stage, last_stage), out, init_angles, affine, opt)
+    out.update(chunk_stats=chunk_stats_dict(stats), chunk_flags=flags)
     return out
 
 
@@ -1274,34 +1084,34 @@ def solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk=0, d_
                      stage_events=None, lanes_per_wave=0, staged=0, interleave_legs=0,
                      frame_chunk=0, frame_halo=0, chunk_tol=0.0, chunk_rounds=0, d_chunk_stats=0, pipeline=0,
                      frame_lead=0, d_chunk_flags=0, d_chunk_states=0, chunk_resume=0):
-    """``seqik_solve_seq_device``: raw device pointers (ints), asynchronous on ``stream``.
-    ``layout``: a ``SeqikLayout`` (``planar_layout(n_frames)``) or None for the dense layout.
+    """``seqik_solve_seq_device``: raw device pointers (ints) or torch tensors, asynchronous on ``stream`` (a hipStream_t
+    as int, or a torch stream).
+    ``layout``: a ``SeqikLayout`` (``planar_layout(n_frames)``) or None for the dense layout (in which a tensor's element
+    count is checked as well).
     ``stage_events``: optional 5 raw hipEvent_t handles (e.g. ``torch.cuda.Event(...).cuda_event`` after a
     first ``record()``), recorded in front of each stage kernel and behind the last one."""
-    arr = (SeqikLegParams * n_legs)(*legs)
-    opt = SeqikOptions()
-    opt.block_size = block_size
-    opt.reserved[0] = lanes_per_wave
-    opt.reserved[1] = staged
-    opt.reserved[2] = interleave_legs
-    opt.reserved[3] = pipeline
-    opt.frame_chunk, opt.frame_halo, opt.chunk_tol, opt.chunk_rounds = frame_chunk, frame_halo, chunk_tol, chunk_rounds
+    opt = _solve_options(block_size, lanes_per_wave, staged, interleave_legs, pipeline, frame_chunk, frame_halo, chunk_tol,
+                         chunk_rounds)
     opt.frame_lead, opt.chunk_resume = int(frame_lead), int(chunk_resume)
-    if d_chunk_stats:  # device int32[16]
-        opt.chunk_stats = ctypes.cast(ctypes.c_void_p(int(d_chunk_stats)), _ip)
-    if d_chunk_flags:  # device uint8 [n_seq][n_legs][K]
-        opt.chunk_flags = ctypes.cast(ctypes.c_void_p(int(d_chunk_flags)), ctypes.POINTER(ctypes.c_uint8))
-    if d_chunk_states:  # device float64 [n_seq][n_legs][K][7]
-        opt.chunk_states = ctypes.cast(ctypes.c_void_p(int(d_chunk_states)), _dp)
+    stats = _ptr(d_chunk_stats, "chunk_stats", (N_CHUNK_STATS,), "int32")   # device int32[16]
+    if stats:
+        opt.chunk_stats = ctypes.cast(stats, _ip)
+    flags = _ptr(d_chunk_flags, "chunk_flags", None, "uint8")   # device uint8 [n_seq][n_legs][K]
+    if flags:
+        opt.chunk_flags = ctypes.cast(flags, _u8p)
+    states = _ptr(d_chunk_states, "chunk_states")   # device float64 [n_seq][n_legs][K][7]
+    if states:
+        opt.chunk_states = ctypes.cast(states, _dp)
     if stage_events is not None:
-        ev = (ctypes.c_void_p * 5)(*[ctypes.c_void_p(int(e)) for e in stage_events])
+        ev = (ctypes.c_void_p * 5)(*[int(e) for e in stage_events])
         opt.stage_events = ctypes.cast(ev, ctypes.POINTER(ctypes.c_void_p))
-    rc = load().seqik_solve_seq_device(ctypes.c_void_p(d_pose), n_seq, n_legs, n_frames, arr, first_stage,
-                                       last_stage, ctypes.c_void_p(d_angles), ctypes.c_void_p(d_fk or None),
-                                       ctypes.c_void_p(d_status or None), ctypes.c_void_p(d_nfev or None),
-                                       ctypes.c_void_p(d_init or None),
-                                       ctypes.byref(layout) if layout is not None else None,
-                                       _affine_array(affine, n_legs),
-                                       ctypes.byref(opt), ctypes.c_void_p(stream or None))
-    if rc != SEQIK_OK:
-        _raise(rc)
+    lf = (n_seq, n_legs, n_frames)
+
+    def shape(*tail):   # a tensor's element count is known in the dense layout only
+        return lf + tail if layout is None else None
+    _call("seqik_solve_seq_device", _ptr(d_pose, "pose", shape(5, 3)), n_seq, n_legs, n_frames,
+          (SeqikLegParams * n_legs)(*legs), first_stage, last_stage, _ptr(d_angles, "angles", shape(7)),
+          _ptr(d_fk, "fk", shape(9, 3)), _ptr(d_status, "status", shape(4), "int32"),
+          _ptr(d_nfev, "nfev", shape(4), "int32"), _ptr(d_init, "init", (n_seq, n_legs, 7)),
+          ctypes.byref(layout) if layout is not None else None, _affine_array(affine, n_legs), ctypes.byref(opt),
+          _stream_ptr(stream))

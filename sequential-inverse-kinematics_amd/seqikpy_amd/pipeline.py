@@ -60,7 +60,6 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
     n = pose.shape[2]
     affine = None if leg_affine is None else [_lib.make_affine(*leg_affine[leg]) for _, leg in segs]
     with_head = all(k in aligned_pos for k in (("R_head", "L_head", "Neck") if head_affine is None else ("R_head", "L_head")))
-    lib = _lib.load()
     with torch.cuda.device(device):
         leg_stream, head_stream = torch.cuda.Stream(), torch.cuda.Stream()
         d_pose = torch.from_numpy(pose).cuda(non_blocking=True)
@@ -110,11 +109,9 @@ def run_body_ik(aligned_pos: Dict[str, np.ndarray], kinematic_chain_class: Kinem
             d_r, d_l, d_n = (torch.from_numpy(a).cuda(non_blocking=True) for a in (r, l_, neck))
             d_head = torch.zeros((7, nh), dtype=torch.float64, device="cuda")
             head_stream.wait_stream(cur)
-            rc = lib.seqik_head_angles_device(d_r.data_ptr(), d_l.data_ptr(), nh, d_n.data_ptr(),
-                                              3 if (neck.shape[0] == nh and nh > 1) else 0, hk.rest_head_pitch,
-                                              hk.rest_antenna_pitch, 1, d_head.data_ptr(), head_stream.cuda_stream)
-            if rc != _lib.SEQIK_OK:
-                _lib._raise(rc)
+            _lib._call("seqik_head_angles_device", d_r.data_ptr(), d_l.data_ptr(), nh, d_n.data_ptr(),
+                       3 if (neck.shape[0] == nh and nh > 1) else 0, hk.rest_head_pitch, hk.rest_antenna_pitch, 1,
+                       d_head.data_ptr(), head_stream.cuda_stream)
         leg_stream.synchronize()
         head_stream.synchronize()
         _lib.check_faults()   # the device entry points do not synchronise: a kernel fault is reported here

@@ -32,7 +32,7 @@ def pinned_array(shape) -> np.ndarray:
     if not ptr:
         _lib._raise(_lib.ERR_HIP)
     buf = (ctypes.c_double * max(n, 1)).from_address(ptr)
-    weakref.finalize(buf, lib.seqik_host_free, ctypes.c_void_p(ptr))
+    weakref.finalize(buf, lib.seqik_host_free, ptr)
     return np.frombuffer(buf, dtype=np.float64, count=n).reshape(shape)
 
 
@@ -60,27 +60,24 @@ class SeqikStream:
                  want_fk: bool = True, n_slots: int = 3, carry: bool = False, generic: bool = False,
                  device: int = -1, block_size: int = 0, frame_chunk: int = 0, frame_halo: int = 0,
                  chunk_tol: float = 0.0):
-        self._lib = _lib.load()
+        self._lib = _lib.load()   # held for close(), which may run while the interpreter shuts down
         self.n_legs = len(legs)
         self.slab_seq, self.n_frames = int(slab_seq), int(n_frames)
         self.want_fk, self.layout = bool(want_fk), layout
         self._handle = ctypes.c_void_p()
-        opt = _lib.SeqikOptions()
-        opt.device = device
-        opt.block_size = block_size
         # frame chunks inside every slab (SeqikOptions.frame_chunk): with carry=True and ONE long recording per slab
         # (slab_seq = 1) this is BASELINE config 5 read literally -- a 10 M-frame recording streamed in time slabs, each
         # slab cut into chunks on the device, its first chunk warm-started from the carried last frame of the slab before
-        opt.frame_chunk, opt.frame_halo, opt.chunk_tol = int(frame_chunk), int(frame_halo), float(chunk_tol)
-        rc = self._lib.seqik_stream_open(ctypes.byref(self._handle), self.n_legs,
-                                         (_lib.SeqikLegParams * self.n_legs)(*legs),
-                                         _lib._affine_array(affine, self.n_legs), self.slab_seq, self.n_frames,
-                                         ctypes.byref(layout) if layout is not None else None,
-                                         1 if want_fk else 0, int(n_slots), 1 if carry else 0, 1 if generic else 0,
-                                         ctypes.byref(opt))
-        if rc != _lib.SEQIK_OK:
+        opt = _lib.SeqikOptions(device=device, block_size=block_size, frame_chunk=int(frame_chunk),
+                                frame_halo=int(frame_halo), chunk_tol=float(chunk_tol))
+        try:
+            _lib._call("seqik_stream_open", ctypes.byref(self._handle), self.n_legs,
+                       (_lib.SeqikLegParams * self.n_legs)(*legs), _lib._affine_array(affine, self.n_legs), self.slab_seq,
+                       self.n_frames, ctypes.byref(layout) if layout is not None else None, 1 if want_fk else 0,
+                       int(n_slots), 1 if carry else 0, 1 if generic else 0, ctypes.byref(opt))
+        except Exception:
             self._handle = ctypes.c_void_p()
-            _lib._raise(rc)
+            raise
         self._keep = []  # host arrays of slabs in flight (kept alive until wait())
 
     # shapes of one slab's host arrays (dense layout)
@@ -111,18 +108,15 @@ class SeqikStream:
                 raise ValueError("pose / angles do not hold n_seq x n_legs x n_frames leg-frames")
         if self.want_fk and (fk is None or fk.size != n_seq * per_seq * 27):
             raise ValueError("fk must hold n_seq x n_legs x n_frames x 9 x 3 values")
-        rc = self._lib.seqik_stream_submit(self._handle, ctypes.c_void_p(pose.ctypes.data), n_seq,
-                                           ctypes.c_void_p(angles.ctypes.data),
-                                           ctypes.c_void_p(fk.ctypes.data) if (self.want_fk and fk is not None) else None)
-        if rc != _lib.SEQIK_OK:
-            _lib._raise(rc)
+        _lib._call("seqik_stream_submit", self._handle, pose.ctypes.data, n_seq, angles.ctypes.data,
+                   fk.ctypes.data if (self.want_fk and fk is not None) else None)
         self._keep.append((pose, angles, fk))
 
     def wait(self):
-        rc = self._lib.seqik_stream_wait(self._handle)
-        self._keep.clear()
-        if rc != _lib.SEQIK_OK:
-            _lib._raise(rc)
+        try:
+            _lib._call("seqik_stream_wait", self._handle)
+        finally:
+            self._keep.clear()
 
     def reset_carry(self):
         self._lib.seqik_stream_reset_carry(self._handle)
@@ -133,15 +127,13 @@ class SeqikStream:
         ``n_seq`` as ``state = (ptr, n_seq)``."""
         if on_device:
             ptr, n_seq = state
-            ptr = int(ptr.data_ptr()) if hasattr(ptr, "data_ptr") else int(ptr)
-            rc = self._lib.seqik_stream_set_carry(self._handle, ctypes.c_void_p(ptr), int(n_seq), 1)
+            _lib._call("seqik_stream_set_carry", self._handle, _lib._ptr(ptr, "state", (n_seq, self.n_legs, 7)),
+                       int(n_seq), 1)
         else:
             arr = np.ascontiguousarray(state, dtype=np.float64)
             if arr.ndim != 3 or arr.shape[1:] != (self.n_legs, 7):
                 raise ValueError(f"state must have shape (n_seq, {self.n_legs}, 7)")
-            rc = self._lib.seqik_stream_set_carry(self._handle, ctypes.c_void_p(arr.ctypes.data), arr.shape[0], 0)
-        if rc != _lib.SEQIK_OK:
-            _lib._raise(rc)
+            _lib._call("seqik_stream_set_carry", self._handle, arr.ctypes.data, arr.shape[0], 0)
 
     def close(self):
         if self._handle:

@@ -43,6 +43,81 @@ def test_library_exports_every_declared_symbol(hiplib):
     assert lib.seqik_abi_version() == 7 == hiplib.ABI_VERSION
 
 
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double,
+             "size_t": ctypes.c_size_t}
+
+
+def header_prototypes(header):
+    """{name: (return type, [parameter, ...])} of every ``seqik_*`` prototype of include/<header>, as C text without
+    comments and preprocessor lines; ``(void)`` is an empty parameter list."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(seqik_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in out, name
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def is_pointer_type(t):
+    return t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+
+
+def assert_same_class(c_text, bound, is_parameter, where):
+    """``c_text``: a C return type, or a parameter with its name.  Anything with ``*`` matches any ctypes pointer type;
+    int, int32_t, int64_t, double and size_t match exactly; a function may return void."""
+    if "*" in c_text:
+        assert is_pointer_type(bound), (where, c_text, bound)
+        return
+    words = [w for w in c_text.split() if w != "const"]
+    if is_parameter:
+        assert len(words) == 2, (where, c_text)   # type and name
+    ctype = words[0]
+    if ctype == "void" and not is_parameter:
+        assert bound is None, (where, c_text, bound)
+    else:
+        assert ctype in C_SCALARS, (where, c_text)
+        assert bound is C_SCALARS[ctype], (where, c_text, bound)
+
+
+def test_signature_table_matches_the_prototypes(hiplib):
+    """Every header's prototypes against ``_lib.SIGNATURES`` -- the table ``load()`` binds the library with: the same
+    names per header, the same number of parameters, and the same class for the return value and every parameter."""
+    headers = ["seqik.h", "seqik_fk.h", "seqik_frames.h", "seqik_gaps.h", "seqik_resample.h", "seqik_head_align.h"]
+    assert sorted(hiplib.SIGNATURES) == sorted(headers)
+    lib = hiplib.load()
+    n_checked = 0
+    for header in headers:
+        protos = header_prototypes(header)
+        table = {sig[0]: sig[1:] for sig in hiplib.SIGNATURES[header]}
+        assert len(table) == len(hiplib.SIGNATURES[header]), header   # no name twice
+        assert sorted(table) == sorted(protos), header
+        for name, (ret, params) in protos.items():
+            restype, argtypes = table[name][0], list(table[name][1:])
+            assert len(argtypes) == len(params), (name, params, argtypes)
+            assert_same_class(ret, restype, False, name)
+            for p, a in zip(params, argtypes):
+                assert_same_class(p, a, True, name)
+            # ... and it is what the loaded library is bound with ((void) -> argtypes == [], not unset)
+            fn = getattr(lib, name)
+            assert fn.restype is restype and fn.argtypes is not None and list(fn.argtypes) == argtypes, name
+            n_checked += 1
+    assert n_checked == 60
+    # the parser sees what it should: a known prototype, in full
+    assert header_prototypes("seqik_resample.h")["seqik_resample_count"] == \
+        ("int64_t", ["int64_t n_frames", "double original_ts", "double new_ts"])
+    assert header_prototypes("seqik.h")["seqik_abi_version"] == ("int", [])
+    # the per-header name lists are the table's
+    for header, names in (("seqik.h", hiplib.EXPORTED_SYMBOLS), ("seqik_fk.h", hiplib.FK_EXPORTED_SYMBOLS),
+                          ("seqik_frames.h", hiplib.FRAMES_EXPORTED_SYMBOLS), ("seqik_gaps.h", hiplib.GAPS_EXPORTED_SYMBOLS),
+                          ("seqik_resample.h", hiplib.RESAMPLE_EXPORTED_SYMBOLS),
+                          ("seqik_head_align.h", hiplib.HEAD_ALIGN_EXPORTED_SYMBOLS)):
+        assert names == [sig[0] for sig in hiplib.SIGNATURES[header]]
+
+
 def test_struct_layout_matches_header(hiplib):
     assert ctypes.sizeof(hiplib.SeqikLegParams) == 8 * (4 + 14 + 27)
     assert ctypes.sizeof(hiplib.SeqikOptions) == 88  # ABI 3: + chunk_flags, chunk_states, chunk_resume

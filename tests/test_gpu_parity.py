@@ -203,6 +203,71 @@ def test_device_pointer_entry_point_with_torch(lib):
     assert np.array_equal(d_nfev.cpu().numpy(), host["nfev"])
 
 
+def test_device_wrappers_take_tensors_and_streams_like_raw_pointers(lib):
+    """``solve_seq_device``, ``forward_kinematics_device`` and ``link_frames_device``: torch tensors and a torch stream
+    give the bits that ``data_ptr()`` ints and the stream's handle as int give; a tensor of the wrong dtype or on the
+    CPU is a ``ValueError`` and nothing is enqueued (the outputs keep their fill)."""
+    import torch
+    z = load_golden("df3d_100")
+    legs = ["RF", "LF"]
+    params = _params(lib, z, legs)
+    S, L, N = 1, 2, 8
+    lf = (S, L, N)
+    d_pose = torch.from_numpy(_stack(z, legs, slice(0, N))).cuda()
+    side = torch.cuda.Stream()
+
+    def run(as_tensors):
+        f64 = dict(dtype=torch.float64, device="cuda")
+        out = dict(angles=torch.full(lf + (7,), np.nan, **f64), fk=torch.full(lf + (9, 3), np.nan, **f64),
+                   status=torch.full(lf + (4,), -7, dtype=torch.int32, device="cuda"),
+                   nfev=torch.full(lf + (4,), -7, dtype=torch.int32, device="cuda"),
+                   fk2=torch.full(lf + (9, 3), np.nan, **f64), dist=torch.full(lf + (4,), np.nan, **f64),
+                   frames=torch.full(lf + (9, 3, 4), np.nan, **f64))
+        d_origin = d_pose[:, :, :, 0, :].contiguous()
+        arg = (lambda t: t) if as_tensors else (lambda t: t.data_ptr())
+        stream = side if as_tensors else side.cuda_stream
+        assert isinstance(stream, torch.cuda.Stream if as_tensors else int)
+        side.wait_stream(torch.cuda.current_stream())
+        lib.solve_seq_device(arg(d_pose), S, L, N, params, arg(out["angles"]), arg(out["fk"]), arg(out["status"]),
+                             arg(out["nfev"]), stream=stream)
+        lib.forward_kinematics_device(arg(out["angles"]), S, L, N, params, arg(out["fk2"]), d_pose=arg(d_pose),
+                                      d_dist=arg(out["dist"]), stream=stream)
+        lib.link_frames_device(arg(out["angles"]), S, L, N, params, arg(out["frames"]), d_origin=arg(d_origin),
+                               stream=stream)
+        side.synchronize()
+        lib.check_faults()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    raw, ten = run(False), run(True)
+    for k in raw:
+        assert np.array_equal(raw[k], ten[k]), k
+    assert np.isfinite(raw["angles"]).all() and np.isfinite(raw["frames"]).all() and (raw["nfev"] > 0).all()
+    assert np.isfinite(raw["fk"]).all() and np.isfinite(raw["fk2"]).all() and np.isfinite(raw["dist"]).all()
+
+    d_ang = torch.full(lf + (7,), np.nan, dtype=torch.float64, device="cuda")
+    d_fk = torch.full(lf + (9, 3), np.nan, dtype=torch.float64, device="cuda")
+    d_fr = torch.full(lf + (9, 3, 4), np.nan, dtype=torch.float64, device="cuda")
+    d_in = torch.from_numpy(raw["angles"]).cuda()
+    for bad, match in ((d_pose.float(), "expected a float64 tensor"), (d_pose.cpu(), "expected a GPU tensor")):
+        with pytest.raises(ValueError, match=match):
+            lib.solve_seq_device(bad, S, L, N, params, d_ang, d_fk)
+    for bad, match in ((d_in.float(), "expected a float64 tensor"), (d_in.cpu(), "expected a GPU tensor")):
+        with pytest.raises(ValueError, match=match):
+            lib.forward_kinematics_device(bad, S, L, N, params, d_fk)
+        with pytest.raises(ValueError, match=match):
+            lib.link_frames_device(bad, S, L, N, params, d_fr)
+    # ... also when the bad tensor is an output that comes after good arguments
+    with pytest.raises(ValueError, match="expected a float64 tensor"):
+        lib.solve_seq_device(d_pose, S, L, N, params, d_ang, d_fk.float())
+    with pytest.raises(ValueError, match="expected a GPU tensor"):
+        lib.forward_kinematics_device(d_in, S, L, N, params, d_fk.cpu())
+    with pytest.raises(ValueError, match="angles: expected 126 elements"):
+        lib.link_frames_device(d_in, S, L, N + 1, params, d_fr)
+    torch.cuda.synchronize()
+    for t in (d_ang, d_fk, d_fr):
+        assert bool(torch.isnan(t).all())
+
+
 def test_planar_device_layout_equals_dense(lib):
     """SeqikLayout: pose [chain][5][frame][3] + angles [chain][7][frame] give the same bits as the dense
     layout, including a later-stage run that reads earlier angles through the strides."""
