@@ -7,7 +7,9 @@
 //   pchip_coefs / pchip_horner       the cubic of one interval in powers of (u - x_A), as scipy's CubicHermiteSpline
 //   resample_bridge_stencil / _ok    bridge mode: the interval and stencil between VALID knots from the neighbour tables
 //   resample_sample                  one output value: what the kernel's direct path runs per lane
-// resample_tables_chain / resample_chain apply them to one chain on the host: the restatement of the contract.  Every
+//   pchip_horner_d1 / _d2, pchip_eval_der, resample_sample_der   the same for the cubic's first and second derivative
+//                                    (include/seqik_resample_der.h; seqik_resample_der.hip)
+// resample_tables_chain / resample_chain (_der) apply them to one chain on the host: the restatement of the contract.  Every
 // operation is one IEEE binary64 operation or an explicit fused multiply-add (built with -ffp-contract=off), divisions are
 // the compiler's correctly rounded ones, so host and device agree bit for bit.
 #pragma once
@@ -213,6 +215,86 @@ inline void resample_chain(const double *y, const ResampleParams &p, int32_t *pr
     if (p.flags & SEQIK_RESAMPLE_BRIDGE) resample_tables_chain(y, p.n_frames, p.width, prev, next);
     for (int32_t i = 0; i < p.n_out; ++i)
         for (int c = 0; c < p.width; ++c) out[(int64_t)i * p.width + c] = resample_sample(y, prev, next, p, i, c);
+}
+
+// ---- derivatives of the interpolant (include/seqik_resample_der.h) ----
+constexpr int kResampleValue = 1, kResampleD1 = 2, kResampleD2 = 4;  // orders 0, 1, 2 as bits of `want`
+
+// d/ds and d2/ds2 of c0 s^3 + c1 s^2 + c2 s + c3; 3 c0, 2 c1 and 6 c0 are one rounding each
+SEQIK_HD double pchip_horner_d1(double c0, double c1, double c2, double s)
+{
+    const double r = fma_(fma_(3.0 * c0, s, 2.0 * c1), s, c2);
+    return r == r ? r : resample_nan();
+}
+
+SEQIK_HD double pchip_horner_d2(double c0, double c1, double s)
+{
+    const double r = fma_(6.0 * c0, s, 2.0 * c1);
+    return r == r ? r : resample_nan();
+}
+
+// pchip_eval for the orders in `want`: v[0] the value (pchip_eval's operations), v[1] and v[2] the first and second
+// derivative.  A sample ON knot B (the last knot's alone) takes that knot's derivative d_B as its first derivative, as it
+// takes y_B as its value; its second derivative is the last interval's at s = h.  Orders not asked for are left alone.
+SEQIK_HD void pchip_eval_der(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u,
+                             int want, double v[3])
+{
+    const PchipKnot none = {0.0, 0.0, false};
+    const double da = pchip_deriv(none, P, A, B, Q), db = pchip_deriv(P, A, B, Q, none);
+    double c0, c1;
+    pchip_coefs(A.x, A.y, B.x, B.y, da, db, c0, c1);
+    const double s = u - A.x;
+    const bool on_b = u == B.x;
+    if (want & kResampleValue) v[0] = on_b ? B.y : pchip_horner(c0, c1, da, A.y, s);
+    if (want & kResampleD1) v[1] = on_b ? (db == db ? db : resample_nan()) : pchip_horner_d1(c0, c1, da, s);
+    if (want & kResampleD2) v[2] = pchip_horner_d2(c0, c1, s);
+}
+
+// resample_sample for the orders in `want` (interval, stencil, bridge and max_gap rules are resample_sample's): where
+// the value is NaN by those rules every order is
+SEQIK_HD void resample_sample_der(const double *ych, const int32_t *prev, const int32_t *next, const ResampleParams &p,
+                                  int32_t i, int col, int want, double v[3])
+{
+    v[0] = v[1] = v[2] = resample_nan();
+    const int32_t n = p.n_frames;
+    const double u = resample_x(i, p.nts);
+    const int32_t j = resample_interval(u, p.ots, p.inv_ots, n);
+    const bool bridge = p.flags & SEQIK_RESAMPLE_BRIDGE;
+    int32_t iP, iA, iB, iQ;
+    if (bridge) {
+        bool tail;
+        if (!resample_bridge_stencil(prev, next, j, n, iP, iA, iB, iQ, tail)) return;
+        if (!resample_bridge_ok(u, iA, iB, tail, p.ots, p.max_gap)) return;
+    } else {
+        iA = j < n - 2 ? j : n - 2;
+        iB = iA + 1;
+        iP = iA - 1;
+        iQ = iA + 2;
+    }
+    const bool hp = iP >= 0, hq = iQ < n;
+    const PchipKnot P = {hp ? resample_x(iP, p.ots) : 0.0, hp ? ych[(int64_t)iP * p.width + col] : 0.0, hp};
+    const PchipKnot A = {resample_x(iA, p.ots), ych[(int64_t)iA * p.width + col], true};
+    const PchipKnot B = {resample_x(iB, p.ots), ych[(int64_t)iB * p.width + col], true};
+    const PchipKnot Q = {hq ? resample_x(iQ, p.ots) : 0.0, hq ? ych[(int64_t)iQ * p.width + col] : 0.0, hq};
+    if (!bridge && !(is_finite(P.y) && is_finite(A.y) && is_finite(B.y) && is_finite(Q.y))) return;
+    pchip_eval_der(P, A, B, Q, u, want, v);
+}
+
+// One chain on the host, the orders in `want`: out_k [n_out][width], a null one is not written.
+inline void resample_chain_der(const double *y, const ResampleParams &p, int32_t *prev, int32_t *next, double *out_value,
+                               double *out_d1, double *out_d2)
+{
+    if (p.flags & SEQIK_RESAMPLE_BRIDGE) resample_tables_chain(y, p.n_frames, p.width, prev, next);
+    const int want = (out_value ? kResampleValue : 0) | (out_d1 ? kResampleD1 : 0) | (out_d2 ? kResampleD2 : 0);
+    for (int32_t i = 0; i < p.n_out; ++i)
+        for (int c = 0; c < p.width; ++c) {
+            double v[3];
+            resample_sample_der(y, prev, next, p, i, c, want, v);
+            const int64_t e = (int64_t)i * p.width + c;
+            if (out_value) out_value[e] = v[0];
+            if (out_d1) out_d1[e] = v[1];
+            if (out_d2) out_d2[e] = v[2];
+        }
 }
 
 }  // namespace seqik

@@ -24,10 +24,10 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip"]
+                 "seqik_head_align.hip", "seqik_resample_der.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
-                "seqik_head_align.hpp"]
+                "seqik_head_align.hpp", "seqik_resample_kernels.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -230,6 +230,14 @@ SIGNATURES = {
         ("seqik_head_angles_raw_device", _int, _vp, _vp, _i64, _i32, _vp, _i64, _f64, _f64, _i32, _vp, _haff, _vp, _vp, _vp, _vp)),
 }
 
+# Entry points added behind ABI 7 without a change of it, in headers of their own: the same row shape, bound by ``load()``
+# in the same loop (``SIGNATURES`` stays the set of headers ABI 7 was cut with).
+EXTENSION_SIGNATURES = {
+    "seqik_resample_der.h": (
+        ("seqik_resample_der", _int, _dp, _i64, _i64, _i32, _f64, _f64, _i32, _i32, _dp, _dp, _dp, _i64, _i32),
+        ("seqik_resample_der_device", _int, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -332,7 +340,7 @@ def load():
         if L.seqik_abi_version() != ABI_VERSION:
             raise SeqikLibraryError(f"{LIB_PATH} has ABI {L.seqik_abi_version()}, this package needs {ABI_VERSION}: "
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for signatures in SIGNATURES.values():
+        for signatures in list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -653,6 +661,65 @@ def resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d
     _call("seqik_resample_pchip_device", _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
           int(width), float(original_ts), float(new_ts), flags, gap, _ptr(d_out, "out", (n_chains, n_out, width)), n_out,
           ws, _stream_ptr(stream))
+    return n_out
+
+
+#: entry points of include/seqik_resample_der.h (derivatives of the PCHIP interpolant), additive to ABI 7
+RESAMPLE_DER_EXPORTED_SYMBOLS = [sig[0] for sig in EXTENSION_SIGNATURES["seqik_resample_der.h"]]
+RESAMPLE_DER_ORDERS = (0, 1, 2)
+
+
+def _resample_orders(der):
+    """``der`` (an int or a sequence of ints) -> tuple of orders in 0..2 without repeats, or ``ValueError``."""
+    if isinstance(der, (bool, np.bool_)) or isinstance(der, (str, bytes)):
+        raise ValueError(f"der: expected orders out of {RESAMPLE_DER_ORDERS}, got {der!r}")
+    orders = (der,) if isinstance(der, (int, np.integer)) else tuple(der) if np.iterable(der) else None
+    if not orders or any(isinstance(o, (bool, np.bool_)) or not isinstance(o, (int, np.integer))
+                         or o not in RESAMPLE_DER_ORDERS for o in orders):
+        raise ValueError(f"der: expected one or more orders out of {RESAMPLE_DER_ORDERS}, got {der!r}")
+    if len(set(orders)) != len(orders):
+        raise ValueError(f"der: an order is given twice in {der!r}")
+    return tuple(int(o) for o in orders)
+
+
+def resample_pchip_der(y, original_ts, new_ts, der=(0, 1), missing="error", max_gap=None, device=-1):
+    """``seqik_resample_der`` on a host array: the derivatives of the interpolant ``resample_pchip`` evaluates, what
+    ``scipy.interpolate.pchip_interpolate(x, y, u, der=...)`` returns.  ``y``, the time steps, ``missing`` and ``max_gap``
+    are ``resample_pchip``'s, with the same checks; ``der``: the orders wanted out of 0 (the value, ``resample_pchip``'s
+    bits), 1 and 2, without repeats.  Returns a tuple of ``(..., n_out, W)`` arrays in the order of ``der``, in units of
+    ``y`` per unit of ``original_ts`` (squared for order 2).  Every order is NaN exactly where the value is."""
+    orders = _resample_orders(der)
+    flags, gap = _resample_flags(missing, max_gap)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim < 2:
+        raise ValueError(f"y must have shape (..., N, W), got {y.shape}")
+    N, W = y.shape[-2:]
+    if not 1 <= W <= RESAMPLE_MAX_WIDTH:
+        raise ValueError(f"the record width must lie in 1..{RESAMPLE_MAX_WIDTH}, got {W}")
+    if N < 2:
+        raise ValueError("The number of knots must be at least 2 (scipy: `x` must contain at least 2 elements)")
+    if not flags and not np.isfinite(y).all():
+        raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
+    n_out = resample_count(N, original_ts, new_ts)
+    C = int(np.prod(y.shape[:-2], dtype=np.int64))
+    planes = [np.full(y.shape[:-2] + (n_out, W), np.nan) if k in orders else None for k in RESAMPLE_DER_ORDERS]
+    _call("seqik_resample_der", _data(y), C, N, W, float(original_ts), float(new_ts), flags, gap, _data(planes[0]),
+          _data(planes[1]), _data(planes[2]), n_out, int(device))
+    return tuple(planes[k] for k in orders)
+
+
+def resample_der_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d_value=0, d_d1=0, d_d2=0, missing="error",
+                        max_gap=None, d_workspace=0, stream=0):
+    """``seqik_resample_der_device``: ``d_y`` (C, N, W) -> those of ``d_value``, ``d_d1``, ``d_d2`` (C, n_out, W) float64
+    that are given (0 / None: not computed, not written; at least one), raw device pointers (ints) or torch tensors,
+    asynchronous on ``stream``.  ``d_workspace`` and what is (not) checked: ``resample_pchip_device``.  Returns n_out."""
+    flags, gap = _resample_flags(missing, max_gap)
+    n_out = resample_count(n_frames, original_ts, new_ts)
+    ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
+    shape = (n_chains, n_out, width)
+    _call("seqik_resample_der_device", _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
+          int(width), float(original_ts), float(new_ts), flags, gap, _ptr(d_value, "value", shape), _ptr(d_d1, "d1", shape),
+          _ptr(d_d2, "d2", shape), n_out, ws, _stream_ptr(stream))
     return n_out
 
 

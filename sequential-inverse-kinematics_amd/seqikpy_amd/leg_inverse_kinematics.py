@@ -258,6 +258,42 @@ class LegInvKinBase(ABC):
             return angles_out
         return angles_out, {name: fk_out[name] for name, _, _ in self._leg_segments()}
 
+    # -- joint-angle velocities and accelerations (include/seqik_resample_der.h) ------------
+    def run_joint_velocities(self, original_ts, new_ts=None, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                             missing: str = "error", max_gap: Optional[int] = None, acceleration: bool = False,
+                             export_path: Union[Path, str] = None):
+        """The legs' joint angular velocities on the GPU: the first derivative of the interpolant ``run_resample``
+        evaluates (scipy's PCHIP, ``pchip_interpolate(..., der=1)``; ``seqik_resample_der``), in rad per unit of
+        ``original_ts``, at the samples ``i * new_ts``.  ``new_ts=None`` means ``original_ts``: the rates at the
+        recording's own frames (the knot derivatives).
+
+        ``joint_angles``, ``missing`` and ``max_gap`` are ``run_resample``'s: the angles go as ``(L, N, 7)`` records in
+        one call per frame count, so ``missing="bridge"`` bridges a leg-frame as a whole, and a rate is NaN exactly where
+        the resampled angle is.  Returns ``{"Angle_<leg>_<dof>": (n_out,)}``; with ``acceleration=True`` the pair
+        ``(velocities, accelerations)`` of such dictionaries (second derivative, rad per unit squared).
+        ``export_path``: writes ``leg_joint_velocities.pkl`` (and ``leg_joint_accelerations.pkl``) there."""
+        ja = self.joint_angles_dict if joint_angles is None else joint_angles
+        new_ts = original_ts if new_ts is None else new_ts
+        groups = {}
+        for segment_name, leg_name, arr in self._leg_segments():
+            ang = self._fk_angles(ja, leg_name)
+            groups.setdefault(ang.shape[0], []).append((leg_name, ang))
+        vel, acc = {}, {}
+        for items in groups.values():
+            res = _lib.resample_pchip_der(np.stack([a for _, a in items]), original_ts, new_ts,
+                                          der=(1, 2) if acceleration else (1,), missing=missing, max_gap=max_gap,
+                                          device=self.device)
+            for li, (leg_name, _) in enumerate(items):
+                for di, dof in enumerate(DOFS):
+                    vel[f"Angle_{leg_name}_{dof}"] = res[0][li, :, di].copy()
+                    if acceleration:
+                        acc[f"Angle_{leg_name}_{dof}"] = res[1][li, :, di].copy()
+        if export_path is not None:
+            save_file(Path(export_path) / "leg_joint_velocities.pkl", vel)
+            if acceleration:
+                save_file(Path(export_path) / "leg_joint_accelerations.pkl", acc)
+        return (vel, acc) if acceleration else vel
+
     def _resample_origin(self, origin, segment_name, leg_name, segment_array):
         if origin is not None:
             o = np.asarray(origin, dtype=np.float64)

@@ -82,7 +82,12 @@ def _reference_grid_check(n_frames, original_ts):
                          f"{n_frames} * {original_ts!r}, {original_ts!r}) holds {n_knots} knots for {n_frames} samples")
 
 
-def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error", max_gap=None):
+def _is_plain_value(der):
+    """``der=0`` as an int: the interpolant's value alone, the code path without derivatives."""
+    return isinstance(der, (int, np.integer)) and not isinstance(der, (bool, np.bool_)) and der == 0
+
+
+def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error", max_gap=None, der=0):
     """Resamples one series from time step ``original_ts`` to ``new_ts`` with a shape-preserving cubic (PCHIP) over
     ``[0, N * original_ts)`` (``seqikpy/utils.py:332-349``).  As there: if the interpolation fails, infinities and the
     last sample are zeroed IN the caller's array and it is tried once more.
@@ -91,7 +96,16 @@ def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error
     modifies ``signal``: where the reference raises (non-finite values, fewer than 2 samples, a knot grid that
     ``np.arange`` makes longer than the series) it raises ``ValueError`` before anything is launched.
     ``missing="bridge"`` (GPU only) resamples over the finite samples alone and so fills the NaN frames of
-    ``missing_key_points="skip"``; ``max_gap``: longest run of missing frames that is filled (None: any)."""
+    ``missing_key_points="skip"``; ``max_gap``: longest run of missing frames that is filled (None: any).
+
+    ``der``: the derivative order of the interpolant to return -- 0 (default: the value, the code path as it was), 1
+    (velocity, per unit of ``original_ts``) or 2 (acceleration) -- or a sequence of orders without repeats, which
+    returns a list with one array per order.  The host path hands ``der`` to ``pchip_interpolate``; ``on_gpu=True``
+    computes it with ``_lib.resample_pchip_der`` (include/seqik_resample_der.h), NaN exactly where the value is NaN."""
+    plain = _is_plain_value(der)
+    if not plain:
+        from . import _lib
+        orders = _lib._resample_orders(der)     # scipy alone would take any order: both paths accept the same ones
     if on_gpu:
         from . import _lib
         y = np.asarray(signal, dtype=np.float64)
@@ -100,12 +114,20 @@ def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error
         if y.shape[0] < 2:
             raise ValueError("`x` must contain at least 2 elements.")
         _reference_grid_check(y.shape[0], original_ts)
-        return _lib.resample_pchip(y[:, None], original_ts, new_ts, missing=missing, max_gap=max_gap)[:, 0]
+        if plain:
+            return _lib.resample_pchip(y[:, None], original_ts, new_ts, missing=missing, max_gap=max_gap)[:, 0]
+        res = _lib.resample_pchip_der(y[:, None], original_ts, new_ts, der=orders, missing=missing, max_gap=max_gap)
+        res = [r[:, 0].copy() for r in res]
+        return res if np.iterable(der) else res[0]
     if missing != "error" or max_gap is not None:
         raise ValueError("missing / max_gap need on_gpu=True (the host path is the reference's own)")
     from scipy.interpolate import pchip_interpolate
     total = signal.shape[0] * original_ts
     x_old, x_new = np.arange(0, total, original_ts), np.arange(0, total, new_ts)
+    if not plain:
+        if np.iterable(der):
+            return [np.array(r) for r in pchip_interpolate(x_old, signal, x_new, der=list(orders))]
+        return np.array(pchip_interpolate(x_old, signal, x_new, der=orders[0]))
     try:
         return np.array(pchip_interpolate(x_old, signal, x_new))
     except BaseException:  # noqa: B036 -- the reference's own breadth
@@ -118,14 +140,15 @@ def interpolate_joint_angles(joint_angles_dict, **kwargs):
     """``interpolate_signal`` over every series of a joint-angle dictionary (``run_ik_and_fk``'s first result);
     ``original_ts`` / ``new_ts`` as keyword arguments (``seqikpy/utils.py:352-360``).  With ``on_gpu=True`` ALL series go
     to the GPU in one call per series length (each series a chain of width 1) and the reference's dictionary comes
-    back; ``missing`` / ``max_gap`` as for ``interpolate_signal``."""
+    back; ``missing`` / ``max_gap`` / ``der`` as for ``interpolate_signal`` (a sequence ``der`` gives every entry a list)."""
     if not kwargs.get("on_gpu", False):
         return {dof: interpolate_signal(signal=series, **kwargs) for dof, series in joint_angles_dict.items()}
     from . import _lib
     opts = dict(kwargs)
     opts.pop("on_gpu")
     original_ts, new_ts = opts.pop("original_ts"), opts.pop("new_ts")
-    missing, max_gap = opts.pop("missing", "error"), opts.pop("max_gap", None)
+    missing, max_gap, der = opts.pop("missing", "error"), opts.pop("max_gap", None), opts.pop("der", 0)
+    orders = None if _is_plain_value(der) else _lib._resample_orders(der)
     if opts:
         raise TypeError(f"interpolate_signal() got an unexpected keyword argument {sorted(opts)[0]!r}")
     groups = {}
@@ -139,8 +162,14 @@ def interpolate_joint_angles(joint_angles_dict, **kwargs):
         groups.setdefault(y.shape[0], []).append((dof, y))
     out = {}
     for items in groups.values():
-        res = _lib.resample_pchip(np.stack([y for _, y in items])[:, :, None], original_ts, new_ts, missing=missing,
-                                  max_gap=max_gap)
+        stacked = np.stack([y for _, y in items])[:, :, None]
+        if orders is None:
+            res = _lib.resample_pchip(stacked, original_ts, new_ts, missing=missing, max_gap=max_gap)
+            for k, (dof, _) in enumerate(items):
+                out[dof] = res[k, :, 0].copy()
+            continue
+        res = _lib.resample_pchip_der(stacked, original_ts, new_ts, der=orders, missing=missing, max_gap=max_gap)
         for k, (dof, _) in enumerate(items):
-            out[dof] = res[k, :, 0].copy()
+            per_order = [r[k, :, 0].copy() for r in res]
+            out[dof] = per_order if np.iterable(der) else per_order[0]
     return {dof: out[dof] for dof in joint_angles_dict}

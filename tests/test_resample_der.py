@@ -1,0 +1,878 @@
+"""Joint-angle velocities and accelerations: the first and second derivative of the PCHIP interpolant
+(include/seqik_resample_der.h, csrc/seqik_resample.hpp: resample_sample_der, csrc/seqik_resample_der.hip).
+
+Every output is pinned three ways: to the host-run rules bit for bit (the GPU tier), to a 200-bit yardstick within a
+bound measured on scipy (both tiers), and the value plane to the bits of the existing entry points.
+
+YARDSTICK.  ``mp_pchip_der(x_valid, y_valid, u, k)``: the k-th derivative of the interpolant the two headers describe,
+written from them and scipy's documentation (half-open intervals [x_A, x_B), the last one closed and continued), nothing
+taken from csrc.  mpmath at 200 bits; knot derivatives as in tests/test_resample_accuracy.py (restated here); on every
+interval the derivative of the Hermite form is a polynomial in t = (u - x_A) / h,
+    h p'   = (6 (y_A - y_B) + 3 h (d_A + d_B)) t^2 - (6 (y_A - y_B) + 2 h (2 d_A + d_B)) t + h d_A
+    h^2 p'' = 2 (6 (y_A - y_B) + 3 h (d_A + d_B)) t - (6 (y_A - y_B) + 2 h (2 d_A + d_B)),
+whose coefficients are computed once per interval.  Kept as a float64 pair (hi, lo).
+
+BOUND.  u = 2^-53.  Per sample and column |got - truth| <= K_k u S_k with S_k = S / h^k: S the stencil scale of the
+accuracy module (max |y| over the knots P, A, B, Q of the sample's stencil that exist) and h the SHORTEST knot spacing in
+that stencil.  S = 0 asks for exactly 0.  Every sample of the contract's finite range counts, none is left out; outside
+it the output must be NaN.  K_ref,k is the smallest power of two above the worst ratio of scipy's own
+``pchip_interpolate(der=k)`` on exactly these inputs, K_k = 4 K_ref,k (the margin of the accuracy module, for its reason:
+the rule and scipy's cubic form differ by a small factor).  ``test_k_ref_is_measured_on_scipy`` fails when scipy needs more.
+
+INPUTS.  The families a..h, the bridge variants and STEPS of tests/test_resample_accuracy.py (150 knots, members 0..6),
+all of magnitude 2^-200 .. 2^200; scipy returns finite derivatives on all of them, none was replaced.
+
+MEASURED (EXPERIMENTS.md, "Resampling derivatives"; the tests print the figures, ``-s``):
+    K_ref,1 = 64 (scipy's largest ratio: 48.191, sawtooth e/last3), K_1 = 256;  K_ref,2 = 64 (scipy 56.462, sawtooth e), K_2 = 256.
+"""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import DOFS, PKG_PARENT, ROOT, load_golden
+from test_capi_symbols import assert_same_class, header_prototypes
+from test_resample import (STEP_PAIRS, ResampleHarness, gap_mask, rs_harness, scipy_bridge, shipped_angles,  # noqa: F401
+                           with_gaps)
+from test_resample_accuracy import (ALL_CASES, CASE_IDS, MEMBERS, N_KNOTS, SEAM_RATIOS, STEPS, bits_equal, bridge_mask,
+                                    case, family, grid, nonfinite_inputs, predicted_nan, stencil_scale)
+
+import mpmath
+from mpmath.libmp import from_float, mpf_add, mpf_mul, mpf_sub, to_float
+
+U = 2.0 ** -53
+K_REF = {1: 64, 2: 64}
+K = {k: 4 * v for k, v in K_REF.items()}
+BRIDGE = 1
+_dp = ctypes.POINTER(ctypes.c_double)
+_MP = mpmath.mp.clone()
+_MP.prec = 200
+
+
+# ------------------------------------------------------ host rules ------------------------------------------------------
+
+class DerHarness:
+    """ctypes front end of tests/harness/resample_der_harness.hip"""
+
+    def __init__(self, so):
+        self.lib = ctypes.CDLL(so)
+        i32, f64 = ctypes.c_int32, ctypes.c_double
+        self.lib.harness_resample_chain_der.restype = ctypes.c_int
+        self.lib.harness_resample_chain_der.argtypes = [_dp, i32, i32, f64, f64, i32, i32, _dp, _dp, _dp, i32]
+        self.lib.harness_knot_derivatives.restype = ctypes.c_int
+        self.lib.harness_knot_derivatives.argtypes = [_dp, i32, i32, f64, i32, _dp]
+
+    def chain(self, y, ots, nts, bridge=False, max_gap=None, orders=(0, 1, 2)):
+        """y (N,) or (N, W) -> one (n_out,) or (n_out, W) array per order"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        y2 = np.ascontiguousarray(y[:, None] if y.ndim == 1 else y)
+        n, w = y2.shape
+        n_out = len(np.arange(0, n * ots, nts))
+        planes = [np.full((n_out, w), 12345.0) if k in orders else None for k in range(3)]
+        rc = self.lib.harness_resample_chain_der(y2.ctypes.data_as(_dp), n, w, ots, nts, BRIDGE if bridge else 0,
+                                                 -1 if max_gap is None else max_gap,
+                                                 *[p.ctypes.data_as(_dp) if p is not None else None for p in planes], n_out)
+        assert rc == 0
+        return tuple(planes[k][:, 0] if y.ndim == 1 else planes[k] for k in orders)
+
+    def chains(self, y, ots, nts, bridge=False, max_gap=None, orders=(0, 1, 2)):
+        """(C, N, W) -> one (C, n_out, W) array per order"""
+        res = [self.chain(c, ots, nts, bridge, max_gap, orders) for c in np.asarray(y, dtype=np.float64)]
+        return tuple(np.stack([r[k] for r in res]) for k in range(len(orders)))
+
+    def knot_derivatives(self, y, ots, bridge=False):
+        y2 = np.ascontiguousarray(y, dtype=np.float64)
+        n, w = y2.shape
+        d = np.full((n, w), 12345.0)
+        assert self.lib.harness_knot_derivatives(y2.ctypes.data_as(_dp), n, w, ots, BRIDGE if bridge else 0,
+                                                 d.ctypes.data_as(_dp)) == 0
+        return d
+
+
+@pytest.fixture(scope="module")
+def der_harness(hiplib):
+    hiplib.load()   # the product library first, as rs_harness does
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "tests", "harness", "resample_der_harness.hip")
+    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    so = os.path.join(out_dir, "libresample_der_harness.so")
+    deps = [src, os.path.join(ROOT, "include", "seqik_resample.h")] + [
+        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_resample.hpp")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
+                               "-shared", "-o", so, src])
+    return DerHarness(so)
+
+
+# ------------------------------------------------------ yardstick ------------------------------------------------------
+
+def _sgn(v):
+    return (v > 0) - (v < 0)
+
+
+def _mp_edge(h0, h1, m0, m1):
+    d = ((2 * h0 + h1) * m0 - h0 * m1) / (h0 + h1)
+    if _sgn(d) != _sgn(m0):
+        return _MP.mpf(0)
+    if _sgn(m0) != _sgn(m1) and abs(d) > 3 * abs(m0):
+        return 3 * m0
+    return d
+
+
+def mp_knot_derivatives(X, Y):
+    n = len(X)
+    H = [X[k + 1] - X[k] for k in range(n - 1)]
+    M = [(Y[k + 1] - Y[k]) / H[k] for k in range(n - 1)]
+    if n == 2:
+        return H, [M[0], M[0]]
+    D = [_mp_edge(H[0], H[1], M[0], M[1])]
+    for k in range(1, n - 1):
+        m0, m1 = M[k - 1], M[k]
+        if _sgn(m0) != _sgn(m1) or m0 == 0 or m1 == 0:
+            D.append(_MP.mpf(0))
+        else:
+            w1, w2 = 2 * H[k] + H[k - 1], H[k] + 2 * H[k - 1]
+            D.append((w1 + w2) / (w1 / m0 + w2 / m1))
+    D.append(_mp_edge(H[-1], H[-2], M[-1], M[-2]))
+    return H, D
+
+
+def mp_pchip_der(x_valid, y_valid, u, orders=(1, 2)):
+    """{k: (hi, lo)}: the k-th derivative of the interpolant over the knots (x_valid, y_valid) at the samples u, all
+    float64 and taken as exact; hi the float64 nearest to the exact value, lo what is left."""
+    mpf = _MP.mpf
+    X, Y = [mpf(float(v)) for v in x_valid], [mpf(float(v)) for v in y_valid]
+    n = len(X)
+    assert n >= 2
+    H, D = mp_knot_derivatives(X, Y)
+    j = np.clip(np.searchsorted(x_valid, u, side="right") - 1, 0, n - 2)
+    P, R = _MP.prec, "n"
+    raw = []
+    for k in range(n - 1):
+        h, ih = H[k], 1 / H[k]
+        q2 = 6 * (Y[k] - Y[k + 1]) + 3 * h * (D[k] + D[k + 1])
+        q1 = 6 * (Y[k] - Y[k + 1]) + 2 * h * (2 * D[k] + D[k + 1])
+        raw.append((X[k]._mpf_, ih._mpf_, (q2 * ih)._mpf_, (-q1 * ih)._mpf_, D[k]._mpf_, (2 * q2 * ih * ih)._mpf_,
+                    (-q1 * ih * ih)._mpf_))
+    out = {k: (np.empty(len(u)), np.empty(len(u))) for k in orders}
+    for i in range(len(u)):
+        xa, ih, a2, a1, a0, b1, b0 = raw[int(j[i])]
+        t = mpf_mul(mpf_sub(from_float(float(u[i])), xa, P, R), ih, P, R)
+        for k in orders:
+            if k == 1:
+                v = mpf_add(mpf_mul(mpf_add(mpf_mul(a2, t, P, R), a1, P, R), t, P, R), a0, P, R)
+            else:
+                v = mpf_add(mpf_mul(b1, t, P, R), b0, P, R)
+            hi = to_float(v, rnd=R)
+            out[k][0][i] = hi
+            out[k][1][i] = to_float(mpf_sub(v, from_float(float(hi)), P, R), rnd=R)
+    return out
+
+
+def shortest_spacing(xv, u):
+    """h per sample: the shortest spacing between neighbouring knots of the stencil P, A, B, Q, as far as they exist"""
+    nv = len(xv)
+    j = np.clip(np.searchsorted(xv, u, side="right") - 1, 0, nv - 2)
+    d = np.diff(xv)
+    h = d[j]
+    h = np.minimum(h, np.where(j > 0, d[np.maximum(j - 1, 0)], np.inf))
+    return np.minimum(h, np.where(j + 2 < nv, d[np.minimum(j + 1, nv - 2)], np.inf))
+
+
+_TRUTH = {}
+
+
+def truth(cs, si):
+    """{k: (hi, lo, S_k)} (n_out, 7) and the finite range `inside` of step pair si of a case of the accuracy module"""
+    key = (cs.label, si)
+    if key not in _TRUTH:
+        xv, yv, u, inside = cs.valid(*STEPS[si])
+        res = {k: (np.full((len(u), MEMBERS), np.nan), np.full((len(u), MEMBERS), np.nan)) for k in (1, 2)}
+        for c in range(MEMBERS):
+            col = mp_pchip_der(xv, yv[:, c], u[inside])
+            for k in (1, 2):
+                res[k][0][inside, c], res[k][1][inside, c] = col[k]
+        S, h = stencil_scale(xv, yv, u), shortest_spacing(xv, u)[:, None]
+        _TRUTH[key] = ({k: (res[k][0], res[k][1], S / h ** k) for k in (1, 2)}, inside)
+    return _TRUTH[key]
+
+
+RATIOS = {}
+
+
+def worst_ratio(cs, si, k, got, cols=slice(None)):
+    """max |got - truth| / (u S_k) over the finite range; exact zeros where S == 0, NaN outside the range"""
+    per_order, inside = truth(cs, si)
+    hi, lo, S = (a[:, cols] for a in per_order[k])
+    assert got.shape == hi.shape, (got.shape, hi.shape)
+    assert np.isnan(got[~inside]).all(), (cs.label, si, k, "finite outside the contract's range")
+    g, h, l, s = got[inside], hi[inside], lo[inside], S[inside]
+    assert np.isfinite(g).all(), (cs.label, si, k, "not finite inside the contract's range")
+    err = np.abs((g - h) - l)
+    assert (err[s == 0] == 0).all() and (g[s == 0] == 0).all(), (cs.label, si, k, "S == 0 asks for exactly 0")
+    return float((err[s > 0] / (U * s[s > 0])).max())
+
+
+def note(who, cs, k, ratio):
+    RATIOS[who, cs.label, k] = max(RATIOS.get((who, cs.label, k), 0.0), ratio)
+
+
+def scipy_der(cs, si, k):
+    from scipy.interpolate import pchip_interpolate
+    xv, yv, u, inside = cs.valid(*STEPS[si])
+    got = np.stack([pchip_interpolate(xv, yv[:, c], u, der=k) for c in range(MEMBERS)], axis=1)
+    assert np.isfinite(got).all(), (cs.label, si, k, "scipy itself is not finite here: replace the input")
+    got[~inside] = np.nan
+    return got
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# CPU tier
+# ---------------------------------------------------------------------------------------------------------------------
+
+DER_SYMBOLS = ["seqik_resample_der", "seqik_resample_der_device"]
+
+
+def test_header_and_extension_table(hiplib):
+    assert sorted(hiplib.EXTENSION_SIGNATURES) == ["seqik_resample_der.h"]
+    assert "seqik_resample_der.h" not in hiplib.SIGNATURES
+    protos = header_prototypes("seqik_resample_der.h")
+    table = {sig[0]: sig[1:] for sig in hiplib.EXTENSION_SIGNATURES["seqik_resample_der.h"]}
+    assert sorted(table) == sorted(protos) == sorted(DER_SYMBOLS)
+    assert hiplib.RESAMPLE_DER_EXPORTED_SYMBOLS == [s[0] for s in hiplib.EXTENSION_SIGNATURES["seqik_resample_der.h"]]
+    lib = hiplib.load()
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name][0], list(table[name][1:])
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        assert_same_class(ret, restype, False, name)
+        for p, a in zip(params, argtypes):
+            assert_same_class(p, a, True, name)
+        fn = getattr(lib, name)             # the library exports it and load() bound it with the table's row
+        assert fn.restype is restype and list(fn.argtypes) == argtypes, name
+    assert [p.split()[-1].lstrip("*") for p in protos["seqik_resample_der"][1][8:11]] == ["out_value", "out_d1", "out_d2"]
+    for other in (hiplib.EXPORTED_SYMBOLS, hiplib.FK_EXPORTED_SYMBOLS, hiplib.FRAMES_EXPORTED_SYMBOLS,
+                  hiplib.GAPS_EXPORTED_SYMBOLS, hiplib.RESAMPLE_EXPORTED_SYMBOLS, hiplib.HEAD_ALIGN_EXPORTED_SYMBOLS):
+        assert not set(DER_SYMBOLS) & set(other)
+    assert lib.seqik_abi_version() == 7 == hiplib.ABI_VERSION
+    assert "seqik_resample_der.hip" in hiplib.COMPILE_UNITS
+    assert {"seqik_resample_der.hip", "seqik_resample_kernels.hpp", "seqik_resample.hpp"} <= set(hiplib.SOURCES)
+    assert "seqik_resample_der.h" in open(os.path.join(ROOT, "setup.py")).read()
+    assert not {"seqik_resample.hip", "seqik_resample.hpp", "seqik_resample_kernels.hpp"} & set(hiplib.KERNEL_SOURCES)
+
+
+def _c_call(hiplib, y=1, planes=(1, 1, 1), n_chains=2, n_frames=100, width=7, ots=1e-2, nts=1e-3, flags=0, max_gap=-1,
+            n_out=None, ws=1, device_entry=True):
+    """The C entry points with made-up non-null pointers: the error text of a REFUSED call.  A call that would pass the
+    checks is never made (it would launch on made-up pointers)."""
+    lib = hiplib.load()
+    fake = ctypes.c_void_p(4096)
+    cnt = lib.seqik_resample_count(n_frames, ots, nts)
+    if n_out is None:
+        n_out = cnt if cnt > 0 else 10
+    good = (y and any(planes) and n_chains >= 0 and 1 <= width <= 16 and cnt > 0 and n_out == cnt and flags in (0, 1)
+            and (ws or not flags or not device_entry))
+    assert not good, "a call that passes the checks must not be made with made-up pointers"
+    yp = fake if y else None
+    pl = [fake if p else None for p in planes]
+    if device_entry:
+        rc = lib.seqik_resample_der_device(yp, n_chains, n_frames, width, ots, nts, flags, max_gap, *pl, n_out,
+                                           fake if ws else None, None)
+    else:
+        rc = lib.seqik_resample_der(ctypes.cast(yp, _dp), n_chains, n_frames, width, ots, nts, flags, max_gap,
+                                    *[ctypes.cast(p, _dp) for p in pl], n_out, -1)
+    assert rc == hiplib.ERR_ARG, rc
+    return lib.seqik_last_error().decode()
+
+
+@pytest.mark.parametrize("device_entry", [True, False])
+def test_c_entry_points_refuse_bad_arguments_before_any_launch(hiplib, device_entry):
+    d = dict(device_entry=device_entry)
+    assert "all null" in _c_call(hiplib, planes=(0, 0, 0), **d)
+    for planes in ((1, 1, 1), (0, 1, 0), (0, 0, 1), (1, 0, 0)):
+        d["planes"] = planes
+        assert "null" in _c_call(hiplib, y=0, **d)
+        assert "n_chains" in _c_call(hiplib, n_chains=-1, **d)
+        assert "at least 2" in _c_call(hiplib, n_frames=1, **d)
+        assert "2^31" in _c_call(hiplib, n_frames=2 ** 31, **d)
+        for w in (0, 17, -3):
+            assert "width" in _c_call(hiplib, width=w, **d)
+        for ts in (0.0, -1e-2, float("nan"), float("inf")):
+            assert "finite and positive" in _c_call(hiplib, ots=ts, **d)
+            assert "finite and positive" in _c_call(hiplib, nts=ts, **d)
+        assert "n_out" in _c_call(hiplib, n_out=999, **d)
+        assert "n_out" in _c_call(hiplib, n_out=1001, **d)
+        assert "flags" in _c_call(hiplib, flags=2, **d)
+        assert "flags" in _c_call(hiplib, flags=-1, **d)
+        if device_entry:
+            assert "workspace" in _c_call(hiplib, flags=1, ws=0, **d)
+    # no chains: nothing to launch
+    fake = ctypes.c_void_p(4096)
+    lib = hiplib.load()
+    assert lib.seqik_resample_der_device(fake, 0, 100, 7, 1e-2, 1e-3, 0, -1, None, fake, None, 1000, None, None) == 0
+
+
+def test_python_argument_handling(hiplib, monkeypatch):
+    from scipy.interpolate import pchip_interpolate
+    from seqikpy_amd import utils
+    y = np.linspace(0, 1, 50) ** 2
+    for bad in (3, -1, (0, 0), (1, 2, 1), (), "1", 1.0, (0, 1.5), True, None, [[1]]):
+        with pytest.raises(ValueError, match="der"):
+            hiplib.resample_pchip_der(y[:, None], 1e-2, 1e-3, der=bad)
+        with pytest.raises(ValueError, match="der"):
+            utils.interpolate_signal(y, 1e-2, 1e-3, der=bad, on_gpu=True)
+        with pytest.raises(ValueError, match="der"):
+            utils.interpolate_signal(y, 1.0, 0.5, der=bad)
+    # the checks of resample_pchip
+    nan = y.copy(); nan[7] = np.nan
+    with pytest.raises(ValueError, match="finite"):
+        hiplib.resample_pchip_der(nan[:, None], 1e-2, 1e-3)
+    with pytest.raises(ValueError, match="missing"):
+        hiplib.resample_pchip_der(y[:, None], 1e-2, 1e-3, missing="skip")
+    with pytest.raises(ValueError, match="max_gap"):
+        hiplib.resample_pchip_der(y[:, None], 1e-2, 1e-3, max_gap=3)
+    with pytest.raises(ValueError, match="at least 2"):
+        hiplib.resample_pchip_der(y[:1, None], 1e-2, 1e-3)
+    with pytest.raises(ValueError, match="width"):
+        hiplib.resample_pchip_der(np.zeros((10, 17)), 1e-2, 1e-3)
+    with pytest.raises(ValueError, match="shape"):
+        hiplib.resample_pchip_der(y, 1e-2, 1e-3)
+    # the order of the results follows der, and only the planes asked for are passed on (no GPU: the call is recorded)
+    seen = []
+
+    def fake_call(name, *args):
+        seen.append((name, [a is not None for a in args[8:11]]))
+        for k, a in enumerate(args[8:11]):
+            if a is not None:
+                a[0] = k            # marks the plane: element 0 holds its order
+    monkeypatch.setattr(hiplib, "_call", fake_call)
+    for der, want in (((0, 1), [0, 1]), ((2, 0), [2, 0]), ((1,), [1]), (2, [2]), ([2, 1, 0], [2, 1, 0]), (0, [0])):
+        res = hiplib.resample_pchip_der(y[:, None], 1e-2, 1e-3, der=der)
+        assert isinstance(res, tuple) and [int(r[0, 0]) for r in res] == want and all(r.shape == (500, 1) for r in res)
+        assert seen[-1] == ("seqik_resample_der", [k in want for k in range(3)])
+    got = utils.interpolate_signal(y, 1e-2, 1e-3, der=[2, 1], on_gpu=True)
+    assert isinstance(got, list) and [int(g[0]) for g in got] == [2, 1] and got[0].shape == (500,)
+    got = utils.interpolate_signal(y, 1e-2, 1e-3, der=2, on_gpu=True)
+    assert isinstance(got, np.ndarray) and got.shape == (500,) and got[0] == 2
+    got = utils.interpolate_joint_angles({"a": y, "b": y[:40]}, original_ts=1e-2, new_ts=1e-3, der=(1, 0), on_gpu=True)
+    assert list(got) == ["a", "b"] and [int(g[0]) for g in got["a"]] == [1, 0]
+    monkeypatch.undo()
+    # host path: der goes to scipy; der=0 is the function as it was
+    x, u = np.arange(0, 50, 1.0), np.arange(0, 50, 0.5)
+    assert np.array_equal(utils.interpolate_signal(y, 1.0, 0.5), pchip_interpolate(x, y, u))
+    assert np.array_equal(utils.interpolate_signal(y, 1.0, 0.5, der=0), pchip_interpolate(x, y, u))
+    assert np.array_equal(utils.interpolate_signal(y, 1.0, 0.5, der=1), pchip_interpolate(x, y, u, der=1))
+    both = utils.interpolate_signal(y, 1.0, 0.5, der=[2, 0])
+    assert isinstance(both, list) and np.array_equal(both[0], pchip_interpolate(x, y, u, der=2))
+    assert np.array_equal(both[1], pchip_interpolate(x, y, u))
+    d = utils.interpolate_joint_angles({"a": y, "b": -y}, original_ts=1.0, new_ts=0.5, der=1)
+    assert np.array_equal(d["b"], pchip_interpolate(x, -y, u, der=1))
+    inf = y.copy(); inf[3] = np.inf
+    utils.interpolate_signal(inf, 1.0, 0.5, der=0)         # today's in-place repair, unchanged
+    assert inf[3] == 0 and inf[-1] == 0
+    import inspect
+    from seqikpy_amd.leg_inverse_kinematics import LegInvKinGeneric, LegInvKinSeq
+    for cls in (LegInvKinSeq, LegInvKinGeneric):
+        ps = inspect.signature(cls.run_joint_velocities).parameters
+        assert list(ps) == ["self", "original_ts", "new_ts", "joint_angles", "missing", "max_gap", "acceleration",
+                            "export_path"]
+        assert [ps[k].default for k in list(ps)[2:]] == [None, None, "error", None, False, None]
+    assert inspect.signature(utils.interpolate_signal).parameters["der"].default == 0
+
+
+@pytest.mark.parametrize("f,v", ALL_CASES, ids=CASE_IDS)
+def test_value_plane_is_the_existing_rules_bits(rs_harness, der_harness, f, v):
+    cs = case(f, v)
+    for ots, nts in STEPS + [(1e-2, 1e-2)]:
+        for w in (7, 1):
+            y = cs.data(w)
+            want = rs_harness.chain(y, ots, nts, bridge=cs.bridge)
+            v0, d1, d2 = der_harness.chain(y, ots, nts, bridge=cs.bridge)
+            assert bits_equal(v0, want), (cs.label, ots, nts, w)
+            # ... and an order does not depend on which others are asked for
+            assert bits_equal(der_harness.chain(y, ots, nts, bridge=cs.bridge, orders=(1,))[0], d1)
+            assert bits_equal(der_harness.chain(y, ots, nts, bridge=cs.bridge, orders=(0, 2))[1], d2)
+            # every order is NaN exactly where the value is
+            assert np.array_equal(np.isnan(d1), np.isnan(want)) and np.array_equal(np.isnan(d2), np.isnan(want))
+            assert not np.isinf(d1).any() and not np.isinf(d2).any()
+
+
+@pytest.mark.parametrize("ts", [1e-2, 1 / 30, 1.0])
+def test_equal_steps_give_the_knot_derivatives(der_harness, ts):
+    """a sample on a knot gets pchip_deriv of that knot bit for bit -- the last (valid) one included, where it is returned
+    and not evaluated"""
+    for f, v in ALL_CASES:
+        cs = case(f, v)
+        y = cs.data(7)
+        d = der_harness.knot_derivatives(y, ts, bridge=cs.bridge)
+        (d1,) = der_harness.chain(y, ts, ts, bridge=cs.bridge, orders=(1,))
+        keep = np.flatnonzero(~cs.mask)
+        assert np.isfinite(d[keep]).all()
+        assert bits_equal(d1[:N_KNOTS][keep], d[keep]), (cs.label, ts)
+        if cs.bridge:
+            assert np.isnan(d[cs.mask]).all()
+
+
+@pytest.mark.parametrize("value", [0.0, -0.0, 1.0, -2.5, 1e6 + 1e-3, 1e-300, -1e300, 0.1])
+def test_a_constant_series_has_zero_derivatives(der_harness, value):
+    for ots, nts in STEPS:
+        y = np.full((N_KNOTS, 7), value)
+        v0, d1, d2 = der_harness.chain(y, ots, nts)
+        assert (v0 == value).all() and (d1 == 0).all() and (d2 == 0).all()
+        y[bridge_mask("a", "gaps")] = np.nan
+        v0, d1, d2 = der_harness.chain(y, ots, nts, bridge=True)
+        ok = ~np.isnan(v0)
+        assert ok.mean() > 0.9 and (d1[ok] == 0).all() and (d2[ok] == 0).all()
+        assert np.isnan(d1[~ok]).all() and np.isnan(d2[~ok]).all()
+
+
+@pytest.mark.parametrize("f,v", ALL_CASES, ids=CASE_IDS)
+def test_negation_commutes(der_harness, f, v):
+    cs = case(f, v)
+    for ots, nts in STEPS:
+        y = cs.data(7)
+        pos, neg = der_harness.chain(y, ots, nts, bridge=cs.bridge), der_harness.chain(-y, ots, nts, bridge=cs.bridge)
+        for p, q in zip(pos, neg):
+            assert np.array_equal(np.isnan(p), np.isnan(q))
+            ok = ~np.isnan(p)
+            assert np.array_equal(q[ok], -p[ok]), (cs.label, ots, nts)
+
+
+@pytest.mark.parametrize("k", [-300, 300])
+def test_power_of_two_scaling_commutes(der_harness, k):
+    for f, v in (("b", None), ("h", None), ("e", "gaps"), ("h", "last3")):      # magnitude about 1
+        cs = case(f, v)
+        assert 0.5 < np.abs(cs.y).max() < 8
+        for ots, nts in STEPS:
+            y = cs.data(7)
+            base = der_harness.chain(y, ots, nts, bridge=cs.bridge)
+            got = der_harness.chain(np.ldexp(y, k), ots, nts, bridge=cs.bridge)
+            for b, g in zip(base, got):
+                ok = ~np.isnan(b)
+                assert np.array_equal(np.isnan(g), ~ok) and np.isfinite(g[ok]).all()
+                assert np.array_equal(g[ok], np.ldexp(b[ok], k)), (k, cs.label, ots, nts)
+                assert np.abs(b[ok]).max() > 0
+
+
+@pytest.mark.parametrize("width", [1, 7])
+def test_nan_masks_of_every_order_equal_the_values(rs_harness, der_harness, width):
+    y = family("a")[:, :width]
+    chains, bad = nonfinite_inputs(y)
+    for ots, nts in STEPS:
+        clean = der_harness.chain(y, ots, nts)
+        got = der_harness.chains(chains, ots, nts)
+        hit = predicted_nan(bad, ots, nts)
+        assert hit.any() and not hit.all()
+        for k in range(3):
+            assert np.array_equal(np.isnan(got[k]), hit), (width, ots, nts, k)
+            assert not np.isinf(got[k]).any()
+            assert np.array_equal(got[k][~hit], np.broadcast_to(clean[k], got[k].shape)[~hit])
+        # bridge mode: the same records are missing knots; every order's mask is the value's, and the existing rules'
+        bgot = der_harness.chains(chains, ots, nts, bridge=True)
+        want = rs_harness.chains(chains, ots, nts, bridge=True)
+        assert bits_equal(bgot[0], want)
+        for k in (1, 2):
+            assert np.array_equal(np.isnan(bgot[k]), np.isnan(want)), (width, ots, nts, k)
+            assert not np.isinf(bgot[k]).any()
+        assert np.isnan(want).any() and np.isfinite(want).any()
+
+
+def test_yardstick_on_cubics_and_lines():
+    """mp_pchip_der reproduces what needs no rule: lines, and a cubic that PCHIP reproduces exactly (monotone data whose
+    knot derivatives the three-point and harmonic rules happen to hit are rare, so: two knots -> the line; knots on a
+    line -> slope and 0; and the Hermite cubic of hand-computed derivatives on a stencil where every rule is known)."""
+    x = np.array([0.0, 0.5, 2.0, 2.25, 7.0])
+    u = np.linspace(0.0, 8.0, 33)
+    tiny = 2.0 ** -170
+    r = mp_pchip_der(x[:2], np.array([1.0, 3.0]), u)
+    assert np.abs(r[1][0] - 4.0).max() <= tiny and np.abs(r[1][1]).max() <= tiny and not r[2][0].any() and not r[2][1].any()
+    r = mp_pchip_der(x, 3.0 - 0.5 * x, u)
+    assert np.abs(r[1][0] + 0.5).max() <= tiny and np.abs(r[1][1]).max() <= tiny
+    assert np.abs(r[2][0]).max() <= tiny and np.abs(r[2][1]).max() <= tiny
+    # y = x^3 on knots 1, 2, 3 (equal steps): slopes 7 and 19; d_1 = 2 * 7 * 19 / 26 (harmonic mean, equal weights),
+    # ends: ((2 h + h) m0 - h m1) / 2 h = (3 * 7 - 19) / 2 = 1 and (3 * 19 - 7) / 2 = 25; the cubic on [1, 2] through
+    # (1, 1), (2, 8) with d = 1, 133 / 13: c0 = d_A + d_B - 2 m = 1 + 133/13 - 14, c1 = 3 m - 2 d_A - d_B
+    xs, ys = np.array([1.0, 2.0, 3.0]), np.array([1.0, 8.0, 27.0])
+    d0, d1 = 1.0, 133.0 / 13.0
+    c0, c1 = d0 + d1 - 14.0, 21.0 - 2.0 * d0 - d1
+    s = np.array([0.0, 0.25, 0.5, 0.875])
+    r = mp_pchip_der(xs, ys, 1.0 + s)
+    assert np.abs(r[1][0] - (3 * c0 * s * s + 2 * c1 * s + d0)).max() <= 1e-14
+    assert np.abs(r[2][0] - (6 * c0 * s + 2 * c1)).max() <= 1e-13
+    # half-open intervals: on the interior knot the RIGHT cubic's second derivative; on the last knot d_B and the last
+    # interval's second derivative at s = h; behind it the last cubic goes on
+    c0r, c1r = d1 + 25.0 - 38.0, 57.0 - 2.0 * d1 - 25.0
+    r = mp_pchip_der(xs, ys, np.array([2.0, 3.0, 3.5]))
+    assert abs(r[1][0][0] - d1) <= 1e-15 and abs(r[2][0][0] - 2 * c1r) <= 1e-13
+    assert abs(r[1][0][1] - 25.0) <= 1e-14 and abs(r[2][0][1] - (6 * c0r + 2 * c1r)) <= 1e-13
+    assert abs(r[1][0][2] - (3 * c0r * 2.25 + 2 * c1r * 1.5 + d1)) <= 1e-13
+    from scipy.interpolate import pchip_interpolate
+    y = np.array([1.0, -2.0, 4.0, 4.0, 1e-3])
+    for k in (1, 2):
+        hi = mp_pchip_der(x, y, u)[k][0]
+        assert np.abs(hi - pchip_interpolate(x, y, u, der=k)).max() <= 256 * U * 4.0 / 0.25 ** k
+
+
+def test_k_ref_is_measured_on_scipy():
+    """scipy's own pchip_interpolate(der=k), on every input of this module, stays within K_ref,k u S_k of the yardstick:
+    K_k = 4 K_ref,k rests on this measurement.  A scipy / numpy that needs more fails here."""
+    worst = {1: 0.0, 2: 0.0}
+    for f, v in ALL_CASES:
+        cs = case(f, v)
+        for k in (1, 2):
+            for si in range(len(STEPS)):
+                r = worst_ratio(cs, si, k, scipy_der(cs, si, k))
+                note("scipy", cs, k, r)
+                worst[k] = max(worst[k], r)
+        print(f"scipy       {cs.label:9s} worst |err| / (u S_k): der 1 {RATIOS['scipy', cs.label, 1]:.3f}, "
+              f"der 2 {RATIOS['scipy', cs.label, 2]:.3f}")
+    print(f"scipy overall: der 1 {worst[1]:.3f} (K_ref {K_REF[1]}), der 2 {worst[2]:.3f} (K_ref {K_REF[2]})")
+    for k in (1, 2):
+        assert worst[k] <= K_REF[k]
+        assert K[k] == 4 * K_REF[k] and K_REF[k] & (K_REF[k] - 1) == 0
+
+
+@pytest.mark.parametrize("f,v", ALL_CASES, ids=CASE_IDS)
+def test_host_rules_inside_the_bound(der_harness, f, v):
+    cs = case(f, v)
+    for si, (ots, nts) in enumerate(STEPS):
+        got7 = der_harness.chain(cs.data(7), ots, nts, bridge=cs.bridge, orders=(1, 2))
+        got1 = der_harness.chain(cs.data(1), ots, nts, bridge=cs.bridge, orders=(1, 2))
+        for k in (1, 2):
+            r7 = worst_ratio(cs, si, k, got7[k - 1])
+            r1 = worst_ratio(cs, si, k, got1[k - 1][:, None], slice(0, 1))
+            note("host", cs, k, max(r7, r1))
+            print(f"host build  {cs.label:9s} {ots:g}->{nts:g} der {k}: width 7 {r7:.3f}, width 1 {r1:.3f} (K = {K[k]})")
+            assert max(r7, r1) <= K[k], (cs.label, ots, nts, k, r7, r1)
+            assert bits_equal(got1[k - 1], got7[k - 1][:, 0])
+
+
+def real_data_bound(y, xv, u, k):
+    """K_k u S_k per sample and column, for knots xv with values y"""
+    return K[k] * U * stencil_scale(xv, y, u) / shortest_spacing(xv, u)[:, None] ** k
+
+
+@pytest.mark.parametrize("leg", ["RF", "LF"])
+def test_host_rules_equal_scipy_on_the_shipped_angles(der_harness, leg):
+    from scipy.interpolate import pchip_interpolate
+    Y = shipped_angles()[leg]
+    for pi, (ots, nts, nf) in enumerate(STEP_PAIRS):
+        y = Y[:nf]
+        x, u = grid(nf, ots, nts)
+        got = der_harness.chain(y, ots, nts, orders=(1, 2))
+        for k in (1, 2):
+            ref = np.stack([pchip_interpolate(x, y[:, c], u, der=k) for c in range(7)], axis=1)
+            err, bound = np.abs(got[k - 1] - ref), real_data_bound(y, x, u, k)
+            print(f"{leg} {ots:g}->{nts:g} der {k}: max |host - scipy| / bound = {(err / bound).max():.3g}")
+            assert (err <= bound).all(), (ots, nts, k)
+        # bridge mode against scipy over the valid knots
+        mask = gap_mask(nf, 10 + pi, 5 if pi % 2 else 0, 0 if pi % 2 else 5)
+        gy = with_gaps(y, mask, 20 + pi)
+        _, inside = scipy_bridge(y, mask, ots, nts)
+        got = der_harness.chain(gy, ots, nts, bridge=True, orders=(1, 2))
+        keep = ~mask
+        for k in (1, 2):
+            ref = np.stack([pchip_interpolate(x[keep], y[keep, c], u, der=k) for c in range(7)], axis=1)
+            assert np.isnan(got[k - 1][~inside]).all() and np.isfinite(got[k - 1][inside]).all()
+            err, bound = np.abs(got[k - 1] - ref)[inside], real_data_bound(y[keep], x[keep], u, k)[inside]
+            print(f"{leg} bridge {ots:g}->{nts:g} der {k}: max |host - scipy| / bound = {(err / bound).max():.3g}")
+            assert (err <= bound).all(), (ots, nts, k, "bridge")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU tier
+# ---------------------------------------------------------------------------------------------------------------------
+
+GUARD = 64
+SENTINEL_F64 = -7.0e77
+SENTINEL_I32 = -123456789
+
+
+def device_run(hiplib, y, ots, nts, bridge=False, max_gap=None, orders=(0, 1, 2)):
+    """seqik_resample_der_device on (C, N, W) through raw pointers.  All three planes are allocated, each between 64
+    sentinel words, as is the int32 workspace; only the planes of `orders` are passed.  Returns one array per order after
+    checking that nothing else was written: the guards, the planes not asked for, the workspace in default mode."""
+    import torch
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    C, N, W = y.shape
+    n_out = hiplib.resample_count(N, ots, nts)
+    cnt = C * n_out * W
+    d_y = torch.from_numpy(y).cuda()
+    bufs = [torch.full((2 * GUARD + cnt,), SENTINEL_F64, dtype=torch.float64, device="cuda") for _ in range(3)]
+    ptrs = [b[GUARD:GUARD + cnt].data_ptr() if k in orders else 0 for k, b in enumerate(bufs)]
+    ws_buf = torch.full((2 * GUARD + 2 * C * N,), SENTINEL_I32, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    got = hiplib.resample_der_device(d_y.data_ptr(), C, N, W, ots, nts, *ptrs, missing="bridge" if bridge else "error",
+                                     max_gap=max_gap, d_workspace=ws_buf[GUARD:].data_ptr() if bridge else 0)
+    assert got == n_out
+    torch.cuda.synchronize()
+    ws = ws_buf.cpu().numpy()
+    for g in (ws[:GUARD], ws[-GUARD:]):
+        assert (g == SENTINEL_I32).all(), "the table kernels wrote outside the workspace"
+    if not bridge:
+        assert (ws == SENTINEL_I32).all(), "default mode touched the workspace"
+    res = []
+    for k, b in enumerate(bufs):
+        out = b.cpu().numpy()
+        assert (out[:GUARD] == SENTINEL_F64).all() and (out[-GUARD:] == SENTINEL_F64).all(), (k, "wrote outside a plane")
+        if k in orders:
+            assert not (out[GUARD:-GUARD] == SENTINEL_F64).any(), (k, "an output element was never written")
+        else:
+            assert (out == SENTINEL_F64).all(), (k, "a plane that was not asked for was written")
+    return tuple(bufs[k].cpu().numpy()[GUARD:-GUARD].reshape(C, n_out, W) for k in orders)
+
+
+def existing_entry(hiplib, y, ots, nts, bridge=False, max_gap=None):
+    """seqik_resample_pchip_device on the same input"""
+    import torch
+    C, N, W = y.shape
+    n_out = hiplib.resample_count(N, ots, nts)
+    d_y = torch.from_numpy(np.ascontiguousarray(y)).cuda()
+    d_out = torch.empty((C, n_out, W), dtype=torch.float64, device="cuda")
+    d_ws = torch.empty((2, C, N), dtype=torch.int32, device="cuda") if bridge else 0
+    hiplib.resample_pchip_device(d_y, C, N, W, ots, nts, d_out, missing="bridge" if bridge else "error", max_gap=max_gap,
+                                 d_workspace=d_ws)
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy()
+
+
+def assert_planes_equal(got, want, what):
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert bits_equal(g, w), (what, "plane", k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("f,v", ALL_CASES, ids=CASE_IDS)
+def test_device_equals_host_rules_and_meets_the_bound(hiplib, der_harness, f, v):
+    cs = case(f, v)
+    for si, (ots, nts) in enumerate(STEPS):
+        for w in (7, 1):
+            y = cs.data(w).reshape(1, N_KNOTS, w)
+            want = der_harness.chains(y, ots, nts, bridge=cs.bridge)
+            got = device_run(hiplib, y, ots, nts, bridge=cs.bridge)
+            assert_planes_equal(got, want, (cs.label, ots, nts, w))
+            assert bits_equal(got[0], existing_entry(hiplib, y, ots, nts, bridge=cs.bridge)), (cs.label, ots, nts, w)
+            host = hiplib.resample_pchip_der(y, ots, nts, der=(0, 1, 2), missing="bridge" if cs.bridge else "error")
+            assert_planes_equal(host, want, (cs.label, ots, nts, w, "host entry"))
+            for k in (1, 2):
+                r = worst_ratio(cs, si, k, got[k][0], slice(0, w))
+                note("device", cs, k, r)
+                assert r <= K[k], (cs.label, ots, nts, w, k, r)
+    print(f"device      {cs.label:9s} worst |err| / (u S_k): der 1 {RATIOS['device', cs.label, 1]:.3f}, "
+          f"der 2 {RATIOS['device', cs.label, 2]:.3f} (K = {K[1]}, {K[2]})")
+
+
+def tiles_per_chain(n_out, width, ots, nts):
+    """the launch geometry of csrc/seqik_resample_kernels.hpp: tiles of 64 * rows flat output elements"""
+    lines = (256 // width - 4) * (ots / nts) * width / 64.0
+    rows = 64 if lines >= 64 else max(int(lines), 1)
+    return -(-n_out * width // (64 * rows))
+
+
+def gappy_chains(rng, width, chains=5):
+    """5 chains each of 150, 173 and 200 knots (one call has one length), clean and with about 20 % of the records
+    missing and one long gap"""
+    out = []
+    for n in (150, 173, 200):
+        y = np.cumsum(rng.normal(size=(chains, n, width)), axis=1)
+        g = y.copy()
+        hit = rng.random((chains, n)) < 0.2
+        hit[:, 60:75] = True
+        cs, ns = np.nonzero(hit)
+        g[cs, ns, rng.integers(0, width, len(cs))] = rng.choice([np.nan, np.inf, -np.inf], len(cs))
+        out.append((y, g))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", range(1, 17))
+def test_every_width_bit_for_bit(hiplib, der_harness, width):
+    rng = np.random.default_rng(700 + width)
+    odd = 0
+    for y, gy in gappy_chains(rng, width):
+        for ots, nts in ((1e-2, 1e-4), (1e-2, 7e-4), (1e-2, 1.3e-2)):
+            n_out = hiplib.resample_count(y.shape[1], ots, nts)
+            odd += (n_out * width) % 64 != 0
+            if nts == 1e-4:                 # every width and length has a call of several tiles per chain
+                assert tiles_per_chain(n_out, width, ots, nts) >= 2
+            assert_planes_equal(device_run(hiplib, y, ots, nts), der_harness.chains(y, ots, nts), (width, ots, nts))
+            assert_planes_equal(device_run(hiplib, gy, ots, nts, bridge=True),
+                                der_harness.chains(gy, ots, nts, bridge=True), (width, ots, nts, "bridge"))
+    assert odd >= 3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [1, 7, 16])
+def test_staged_direct_seam(hiplib, der_harness, width):
+    """ratios at which one launch holds staged and direct tiles, and gaps that push single tiles over the edge"""
+    rng = np.random.default_rng(800 + width)
+    n, ots = 2000, 1e-2
+    y = np.cumsum(rng.normal(size=(2, n, width)), axis=1)
+    gy = y.copy()
+    for c in range(2):
+        k = int(rng.integers(1, 20))
+        while k < n - 1:
+            g = int(rng.integers(1, 41))
+            gy[c, k:min(k + g, n - 1), rng.integers(0, width)] = np.nan
+            k += g + int(rng.integers(1, 60))
+    for ratio in SEAM_RATIOS:
+        nts = ratio * ots
+        assert_planes_equal(device_run(hiplib, y, ots, nts), der_harness.chains(y, ots, nts), (width, ratio))
+        for max_gap in (None, 5):
+            assert_planes_equal(device_run(hiplib, gy, ots, nts, bridge=True, max_gap=max_gap),
+                                der_harness.chains(gy, ots, nts, bridge=True, max_gap=max_gap), (width, ratio, max_gap))
+
+
+SUBSETS = [(0,), (1,), (2,), (0, 1), (0, 2), (1, 2), (0, 1, 2)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bridge", [False, True])
+def test_output_subsets_give_the_same_bits_and_write_nothing_else(hiplib, der_harness, bridge):
+    rng = np.random.default_rng(900)
+    for n, width, ots, nts in ((150, 7, 1e-2, 1e-3), (150, 13, 1e-2, 1.3e-2), (2000, 5, 1e-2, 0.13), (173, 1, 1e-2, 7e-4)):
+        y = np.cumsum(rng.normal(size=(3, n, width)), axis=1)
+        if bridge:
+            y[rng.random((3, n)) < 0.2, rng.integers(0, width)] = np.nan
+        assert (hiplib.resample_count(n, ots, nts) * width) % 64 != 0
+        full = device_run(hiplib, y, ots, nts, bridge=bridge)
+        assert_planes_equal(full, der_harness.chains(y, ots, nts, bridge=bridge), (n, width))
+        for orders in SUBSETS:
+            got = device_run(hiplib, y, ots, nts, bridge=bridge, orders=orders)     # checks the planes not asked for
+            assert_planes_equal(got, [full[k] for k in orders], (n, width, orders))
+            host = hiplib.resample_pchip_der(y, ots, nts, der=orders, missing="bridge" if bridge else "error")
+            assert_planes_equal(host, got, (n, width, orders, "host entry"))
+
+
+@pytest.mark.gpu
+def test_bridge_edge_cases(hiplib, der_harness, rs_harness):
+    rng = np.random.default_rng(1000)
+    n, w = 160, 7
+    y = np.cumsum(rng.normal(size=(6, n, w)), axis=1)
+    y[rng.random((6, n)) < 0.15, rng.integers(0, w)] = np.nan
+    y[0, :5] = np.nan                       # the first 5 knots missing
+    y[1, -5:] = np.inf                      # the last 5
+    y[2, :5] = np.nan
+    y[2, -5:] = np.nan
+    y[3] = np.nan
+    y[3, 77] = 1.0                          # one valid knot
+    y[4] = np.nan                           # none
+    y[5, 30:34] = np.nan                    # a gap of exactly 4 around max_gap = 3
+    y[5, 29], y[5, 34] = 1.0, 2.0
+    for ots, nts in ((1e-2, 1e-3), (1e-2, 1e-2), (1e-2, 1.3e-2), (1.0, 0.25)):
+        for max_gap in (None, 0, 3):
+            got = device_run(hiplib, y, ots, nts, bridge=True, max_gap=max_gap)
+            want = der_harness.chains(y, ots, nts, bridge=True, max_gap=max_gap)
+            assert_planes_equal(got, want, (ots, nts, max_gap))
+            assert bits_equal(got[0], rs_harness.chains(y, ots, nts, bridge=True, max_gap=max_gap))
+            for k in (1, 2):
+                assert np.array_equal(np.isnan(got[k]), np.isnan(got[0]))
+            assert np.isnan(got[0][3:5]).all() and np.isfinite(got[0][:3]).any(axis=(1, 2)).all()
+            x, u = grid(n, ots, nts)
+            assert np.isnan(got[1][0][u < x[5]]).all() and np.isnan(got[1][1][u >= x[n - 6] + ots]).all()
+            if max_gap is not None:
+                inside = (u > x[29]) & (u < x[34])
+                assert np.isnan(got[1][5][inside]).all() and np.isnan(got[2][5][inside]).all()
+
+
+@pytest.mark.gpu
+def test_device_entry_point_only_enqueues(hiplib, der_harness):
+    import torch
+    rng = np.random.default_rng(1100)
+    C, N, W = 6, 3000, 7
+    ys = [np.cumsum(rng.normal(size=(C, N, W)) * 0.05, axis=1) for _ in range(2)]
+    for y in ys:
+        y[rng.random((C, N)) < 0.05] = np.nan
+    want = [der_harness.chains(y, 1e-2, 1e-3, bridge=True) for y in ys]
+    n_out = hiplib.resample_count(N, 1e-2, 1e-3)
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    d_y = [torch.from_numpy(y).cuda() for y in ys]
+    d_out = [[torch.full((C, n_out, W), 7.0, dtype=torch.float64, device="cuda") for _ in range(3)] for _ in ys]
+    d_ws = [torch.empty((2, C, N), dtype=torch.int32, device="cuda") for _ in ys]
+    torch.cuda.synchronize()
+    for k in range(2):
+        hiplib.resample_der_device(d_y[k], C, N, W, 1e-2, 1e-3, *d_out[k], missing="bridge", d_workspace=d_ws[k],
+                                   stream=streams[k])
+    for s in streams:
+        s.synchronize()
+    for k in range(2):
+        assert_planes_equal([t.cpu().numpy() for t in d_out[k]], want[k], k)
+    # default mode on a non-default stream, raw pointers, no workspace, the derivative planes alone
+    fin = np.nan_to_num(ys[0], nan=0.5)
+    d_f = torch.from_numpy(fin).cuda()
+    torch.cuda.synchronize()
+    hiplib.resample_der_device(d_f.data_ptr(), C, N, W, 1e-2, 1e-3, 0, d_out[0][1].data_ptr(), d_out[0][2].data_ptr(),
+                               stream=streams[1].cuda_stream)
+    streams[1].synchronize()
+    ref = der_harness.chains(fin, 1e-2, 1e-3, orders=(1, 2))
+    assert_planes_equal([d_out[0][1].cpu().numpy(), d_out[0][2].cpu().numpy()], ref, "default")
+    assert bits_equal(d_out[0][0].cpu().numpy(), want[0][0])          # the value plane was not passed: untouched
+    with pytest.raises(ValueError, match="elements"):
+        hiplib.resample_der_device(d_f, C, N, W, 1e-2, 1e-3, d_d1=d_out[0][1][:, :-1])
+    with pytest.raises(ValueError, match="all null"):
+        hiplib.resample_der_device(d_f, C, N, W, 1e-2, 1e-3)
+
+
+@pytest.mark.gpu
+def test_python_methods(hiplib, der_harness):
+    from seqikpy_amd import utils
+    from seqikpy_amd.data import BOUNDS, INITIAL_ANGLES
+    from seqikpy_amd.kinematic_chain import KinematicChainSeq
+    from seqikpy_amd.leg_inverse_kinematics import LegInvKinSeq
+    z = load_golden("df3d_100")
+    rng = np.random.default_rng(1200)
+    legs = ["RF", "LF"]
+    gapped = {}
+    for l in legs:
+        p = np.array(z[f"{l}_pose"], dtype=np.float64, copy=True)
+        hit = rng.random(p.shape[0]) < 0.1
+        hit[40:46] = True
+        hit[0] = hit[-1] = False
+        p[hit, rng.integers(1, 5), :] = np.nan
+        gapped[f"{l}_leg"] = p
+    ik = LegInvKinSeq(gapped, KinematicChainSeq(BOUNDS, legs), INITIAL_ANGLES, log_level="ERROR")
+    ja, _ = ik.run_ik_and_fk(missing_key_points="skip")
+    assert all(ik.missing_frames[l].sum() >= 6 for l in legs)
+    stacked = np.stack([np.stack([ja[f"Angle_{l}_{d}"] for d in DOFS], axis=1) for l in legs])
+    with pytest.raises(ValueError, match="finite"):
+        ik.run_joint_velocities(1e-2)
+    for new_ts, n_out in ((None, 100), (1e-3, 1000)):
+        nts = 1e-2 if new_ts is None else new_ts
+        for max_gap in (None, 3):
+            d1, d2 = hiplib.resample_pchip_der(stacked, 1e-2, nts, der=(1, 2), missing="bridge", max_gap=max_gap)
+            vel, acc = ik.run_joint_velocities(1e-2, new_ts, missing="bridge", max_gap=max_gap, acceleration=True)
+            only = ik.run_joint_velocities(1e-2, new_ts, missing="bridge", max_gap=max_gap)
+            assert list(vel) == list(acc) == list(only) == [f"Angle_{l}_{d}" for l in legs for d in DOFS]
+            for li, l in enumerate(legs):
+                for di, d in enumerate(DOFS):
+                    key = f"Angle_{l}_{d}"
+                    assert vel[key].shape == (n_out,)
+                    assert bits_equal(vel[key], d1[li, :, di]) and bits_equal(acc[key], d2[li, :, di])
+                    assert bits_equal(only[key], vel[key])
+            want = der_harness.chains(stacked, 1e-2, nts, bridge=True, max_gap=max_gap, orders=(1, 2))
+            assert bits_equal(d1, want[0]) and bits_equal(d2, want[1])
+        if new_ts is None:
+            # at the recording's own frames a solved frame's velocity is its knot derivative; frames 0 and 99 were solved
+            d = der_harness.knot_derivatives(stacked[0], 1e-2, bridge=True)
+            solved = ~ik.missing_frames["RF"]
+            got = np.stack([vel[f"Angle_RF_{d_}"] for d_ in DOFS], axis=1)
+            assert bits_equal(got[solved], d[solved]) and np.isfinite(got[solved]).all()
+    # utils: all series in one call equal the per-series calls; der as an int or a list
+    angles = shipped_angles()
+    series = {f"Angle_{leg}_{d}": angles[leg][:1000, i].copy() for leg in legs for i, d in enumerate(DOFS)}
+    vel = utils.interpolate_joint_angles(series, original_ts=1e-2, new_ts=1e-3, on_gpu=True, der=1)
+    both = utils.interpolate_joint_angles(series, original_ts=1e-2, new_ts=1e-3, on_gpu=True, der=[0, 2])
+    plain = utils.interpolate_joint_angles(series, original_ts=1e-2, new_ts=1e-3, on_gpu=True)
+    assert list(vel) == list(series)
+    for key, s in series.items():
+        one = utils.interpolate_signal(s, 1e-2, 1e-3, on_gpu=True, der=1)
+        assert one.shape == (10000,) and bits_equal(vel[key], one)
+        assert bits_equal(one, der_harness.chain(s, 1e-2, 1e-3, orders=(1,))[0])
+        assert isinstance(both[key], list) and bits_equal(both[key][0], plain[key])
+        assert bits_equal(both[key][1], utils.interpolate_signal(s, 1e-2, 1e-3, on_gpu=True, der=2))
