@@ -430,7 +430,16 @@ int seqik_stream_close(SeqikStream *s);
  *   _open     room for capacity_frames frames per leg on device opt->device
  *   _add      appends n_seq x n_frames frames of every leg: pose [n_seq][n_legs][n_frames][5][3] or `layout`
  *             (pose strides only), host memory (pose_on_device = 0, blocking) or device memory (enqueued on
- *             hip_stream); slabs may come in any order
+ *             hip_stream); slabs may come in any order.  Host memory is staged as one contiguous piece of
+ *             n_seq * n_legs chain strides, so its layout must keep every key point of a chain inside the chain's
+ *             stride, the rule of seqik_stream_open: pose_chain, pose_row, pose_frame > 0 and
+ *             4*pose_row + (n_frames-1)*pose_frame + 3 <= pose_chain; anything else is SEQIK_ERR_ARG before any
+ *             device work, and the handle stays usable.  For device memory the caller owns the extent: pose_row,
+ *             pose_frame > 0, and pose_chain > 0 unless n_seq * n_legs == 1.
+ *             Non-finite input is the caller's business: the sort orders keys by their bits, so a NaN goes to the
+ *             end its sign bit selects (numpy puts every NaN last, and its quantile is then NaN); this is why
+ *             AlignPose.leg_affines(on_gpu=True) takes the host path when the input holds a non-finite value.
+ *             -0.0 and +0.0 compare equal: the sign of a zero returned from a run of mixed zeros is unspecified.
  *   _finish   sorts; out [n_legs][7][n_ranks] = value at the 0-based ranks `ranks[i]` of each ascending series
  *             (series order: coxa x, y, z, then the four segment lengths); blocking
  *   _reset    forget the frames added so far;  _close  free everything

@@ -109,21 +109,40 @@ int seqik_align_stats_add(SeqikAlignStats *s, const double *pose, int32_t pose_o
 {
     if (!s || !pose) return bad_arg("seqik_align_stats_add", "null pointer");
     if (n_seq < 0 || n_frames < 0) return bad_arg("seqik_align_stats_add", "negative size");
-    const int64_t add = n_seq * n_frames;
-    if (add == 0) return SEQIK_OK;
-    if (s->count + add > s->capacity) return bad_arg("seqik_align_stats_add", "more frames than the capacity");
+    if (n_seq == 0 || n_frames == 0) return SEQIK_OK;
+    int64_t add = 0;
+    if (__builtin_mul_overflow(n_seq, n_frames, &add) || add > s->capacity - s->count)
+        return bad_arg("seqik_align_stats_add", "more frames than the capacity");
+    // the layout is judged before the first HIP call: a refused call leaves the handle and the device untouched
+    int64_t pc = n_frames * 15, pr = 3, pf = 15;  // (n_frames <= capacity: no overflow)
+    if (layout) { pc = layout->pose_chain; pr = layout->pose_row; pf = layout->pose_frame; }
+    size_t stage_bytes = 0;
+    if (!pose_on_device) {
+        // host memory is staged as ONE contiguous piece of n_seq * n_legs chain strides (as seqik_stream_open's slabs
+        // are), so every element the kernel addresses must lie inside its chain's stride
+        int64_t rows = 0, frames = 0, last = 0;
+        const bool ok = pc > 0 && pr > 0 && pf > 0 && !__builtin_mul_overflow((int64_t)4, pr, &rows) &&
+                        !__builtin_mul_overflow(n_frames - 1, pf, &frames) &&
+                        !__builtin_add_overflow(rows, frames, &last) && !__builtin_add_overflow(last, (int64_t)3, &last) &&
+                        last <= pc;
+        if (!ok)
+            return bad_arg("seqik_align_stats_add",
+                           "host layout: all three pose strides must be > 0 and every key point of a chain must lie "
+                           "inside its chain stride (4*pose_row + (n_frames-1)*pose_frame + 3 <= pose_chain)");
+        if (__builtin_mul_overflow((size_t)pc, (size_t)n_seq * (size_t)s->n_legs, &stage_bytes) ||
+            __builtin_mul_overflow(stage_bytes, sizeof(double), &stage_bytes))
+            return bad_arg("seqik_align_stats_add", "host layout: the slab's size overflows");
+    } else {  // device memory: the caller owns the extent
+        if (pc < 0 || pr <= 0 || pf <= 0) return bad_arg("seqik_align_stats_add", "layout strides must be positive");
+        if (pc == 0 && (n_seq > 1 || s->n_legs > 1))
+            return bad_arg("seqik_align_stats_add", "device layout: pose_chain must be > 0 for more than one chain");
+    }
     seqik::DeviceScope scope;
     HIP_TRY(scope.enter(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    int64_t pc = n_frames * 15, pr = 3, pf = 15;
-    if (layout) {
-        if (layout->pose_chain < 0 || layout->pose_row <= 0 || layout->pose_frame <= 0)
-            return bad_arg("seqik_align_stats_add", "layout strides must be positive");
-        pc = layout->pose_chain; pr = layout->pose_row; pf = layout->pose_frame;
-    }
     const double *d_pose = pose;
     if (!pose_on_device) {
-        const size_t bytes = sizeof(double) * (size_t)pc * n_seq * s->n_legs;
+        const size_t bytes = stage_bytes;
         if (bytes > s->stage_bytes) {
             if (s->d_stage) { HIP_TRY(hipStreamSynchronize(stream)); (void)hipFree(s->d_stage); s->d_stage = nullptr; s->stage_bytes = 0; }
             HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_stage), bytes));

@@ -854,6 +854,14 @@ class AlignStats:
             raise
 
     def add(self, pose, n_seq=None, n_frames=None, layout=None, on_device=False, stream=0):
+        """Appends ``n_seq x n_frames`` frames of every leg.  A host slab is copied to the GPU as one piece of
+        ``n_seq * n_legs`` chain strides, so its ``layout`` must keep every key point of a chain inside the chain's
+        stride: ``pose_chain``, ``pose_row``, ``pose_frame`` > 0 and
+        ``4*pose_row + (n_frames-1)*pose_frame + 3 <= pose_chain`` (the rule of ``seqik_stream_open``; ``planar_layout``
+        satisfies it), and the array must hold ``pose_chain * n_seq * n_legs`` doubles: ``ValueError`` otherwise.  For
+        device memory the caller owns the extent (``pose_chain`` may exceed what a chain needs; 0 only for one chain)."""
+        if (on_device or layout is not None) and (n_seq is None or n_frames is None):
+            raise ValueError("n_seq and n_frames are required with a layout or device memory")
         if on_device:  # a raw device pointer or a tensor (its element count is checked in the dense layout only)
             ptr = _ptr(pose, "pose", None if layout is not None else (n_seq, self.n_legs, n_frames, 5, 3))
         else:
@@ -862,6 +870,9 @@ class AlignStats:
                 if pose.ndim != 5 or pose.shape[1] != self.n_legs or pose.shape[3:] != (5, 3):
                     raise ValueError(f"pose must have shape (S, {self.n_legs}, N, 5, 3), got {pose.shape}")
                 n_seq, n_frames = pose.shape[0], pose.shape[2]
+            elif pose.size < layout.pose_chain * int(n_seq) * self.n_legs:
+                raise ValueError(f"pose holds {pose.size} doubles, the layout addresses "
+                                 f"{layout.pose_chain * int(n_seq) * self.n_legs} (pose_chain * n_seq * n_legs)")
             ptr = pose.ctypes.data
         _call("seqik_align_stats_add", self._h, ptr, 1 if on_device else 0, int(n_seq), int(n_frames),
               ctypes.byref(layout) if layout is not None else None, _stream_ptr(stream))
