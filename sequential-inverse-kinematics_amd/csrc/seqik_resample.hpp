@@ -6,9 +6,10 @@
 //   pchip_deriv                      the derivative at a knot from its (up to four) neighbours
 //   pchip_coefs / pchip_horner       the cubic of one interval in powers of (u - x_A), as scipy's CubicHermiteSpline
 //   resample_bridge_stencil / _ok    bridge mode: the interval and stencil between VALID knots from the neighbour tables
-//   resample_sample                  one output value: what the kernel's direct path runs per lane
-//   pchip_horner_d1 / _d2, pchip_eval_der, resample_sample_der   the same for the cubic's first and second derivative
-//                                    (include/seqik_resample_der.h; seqik_resample_der.hip)
+//   resample_neighbours              the knots a knot's derivative is made from, in either mode
+//   pchip_horner / _d1 / _d2, pchip_cubic_orders   the cubic's value, first and second derivative; the on-knot-B rule
+//   pchip_eval_der / resample_sample_der   the orders asked for of one output sample (include/seqik_resample_der.h): what
+//                                    the kernel's direct path runs per lane; pchip_eval / resample_sample: the value alone
 // resample_tables_chain / resample_chain (_der) apply them to one chain on the host: the restatement of the contract.  Every
 // operation is one IEEE binary64 operation or an explicit fused multiply-add (built with -ffp-contract=off), divisions are
 // the compiler's correctly rounded ones, so host and device agree bit for bit.
@@ -25,6 +26,21 @@ struct ResampleParams {
     int32_t n_frames, n_out;   // both below 2^31
     int32_t width, flags, max_gap;
 };
+
+SEQIK_HD ResampleParams resample_params(double ots, double nts, int32_t n_frames, int32_t n_out, int32_t width,
+                                        int32_t flags, int32_t max_gap)
+{
+    ResampleParams p;
+    p.ots = ots;
+    p.inv_ots = 1.0 / ots;
+    p.nts = nts;
+    p.n_frames = n_frames;
+    p.n_out = n_out;
+    p.width = width;
+    p.flags = flags;
+    p.max_gap = max_gap;
+    return p;
+}
 
 // numpy's length rule for np.arange(0, n_frames * ots, nts), as a double (the caller checks the range)
 inline double resample_count_f64(int64_t n_frames, double ots, double nts)
@@ -108,17 +124,51 @@ SEQIK_HD double pchip_horner(double c0, double c1, double c2, double c3, double 
     return r == r ? r : resample_nan();
 }
 
-// the stencil P, A, B, Q of interval (A, B) as knots.  A sample ON knot B takes that knot's value: the power form at
-// s = h equals it only up to rounding.  Every knot but the last (valid) one starts an interval of its own, where s = 0
-// returns y_A exactly, so this is the last knot's sample alone.
-SEQIK_HD double pchip_eval(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u)
+// d/ds and d2/ds2 of c0 s^3 + c1 s^2 + c2 s + c3; 3 c0, 2 c1 and 6 c0 are one rounding each
+SEQIK_HD double pchip_horner_d1(double c0, double c1, double c2, double s)
 {
-    if (u == B.x) return B.y;
+    const double r = fma_(fma_(3.0 * c0, s, 2.0 * c1), s, c2);
+    return r == r ? r : resample_nan();
+}
+
+SEQIK_HD double pchip_horner_d2(double c0, double c1, double s)
+{
+    const double r = fma_(6.0 * c0, s, 2.0 * c1);
+    return r == r ? r : resample_nan();
+}
+
+constexpr int kResampleValue = 1, kResampleD1 = 2, kResampleD2 = 4;  // orders 0, 1, 2 as bits of `want`
+constexpr int kResampleAll = kResampleValue | kResampleD1 | kResampleD2;
+
+// The orders in `want` of the cubic c0 s^3 + c1 s^2 + dA s + yA at s: v[0] the value, v[1] and v[2] the first and second
+// derivative; orders not asked for are left alone.  on_b: the sample sits ON knot B.  It takes that knot's value y_B (the
+// power form at s = h equals it only up to rounding) and that knot's derivative d_B as its first derivative; its second
+// derivative is the cubic's at s = h.  Every knot but the last (valid) one starts an interval of its own, where s = 0
+// returns y_A and d_A exactly, so this is the last knot's sample alone.  yb, db are read only when on_b.
+SEQIK_HD void pchip_cubic_orders(double c0, double c1, double da, double ya, double s, bool on_b, double yb, double db,
+                                 int want, double v[3])
+{
+    if (want & kResampleValue) v[0] = on_b ? yb : pchip_horner(c0, c1, da, ya, s);
+    if (want & kResampleD1) v[1] = on_b ? (db == db ? db : resample_nan()) : pchip_horner_d1(c0, c1, da, s);
+    if (want & kResampleD2) v[2] = pchip_horner_d2(c0, c1, s);
+}
+
+// the stencil P, A, B, Q of interval (A, B) as knots: the orders in `want` of the interpolant at u
+SEQIK_HD void pchip_eval_der(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u,
+                             int want, double v[3])
+{
     const PchipKnot none = {0.0, 0.0, false};
     const double da = pchip_deriv(none, P, A, B, Q), db = pchip_deriv(P, A, B, Q, none);
     double c0, c1;
     pchip_coefs(A.x, A.y, B.x, B.y, da, db, c0, c1);
-    return pchip_horner(c0, c1, da, A.y, u - A.x);
+    pchip_cubic_orders(c0, c1, da, A.y, u - A.x, u == B.x, B.y, db, want, v);
+}
+
+SEQIK_HD double pchip_eval(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u)
+{
+    double v[3];
+    pchip_eval_der(P, A, B, Q, u, kResampleValue, v);
+    return v[0];
 }
 
 // Bridge mode.  prev[j] = last valid knot <= j (-1: none), next[j] = first valid knot >= j (n: none).  For the raw
@@ -157,101 +207,39 @@ SEQIK_HD bool resample_bridge_ok(double u, int32_t A, int32_t B, bool tail, doub
     return true;
 }
 
-// One output value: sample i, column col of the chain at ych ([n_frames][width]); prev / next: the chain's tables in
-// bridge mode.
-SEQIK_HD double resample_sample(const double *ych, const int32_t *prev, const int32_t *next, const ResampleParams &p,
-                                int32_t i, int col)
+// The knots the derivative at knot g is made from (pchip_deriv's m2, m1, p1, p2), in bridge mode its VALID neighbours
+// from the tables.  false: g is a missing knot, or has no neighbour at all (fewer than two valid knots).
+struct PchipNeighbours {
+    int32_t m2, m1, p1, p2;
+    bool hm2, hm1, hp1, hp2;  // m2 / p2 count only at an end, where pchip_deriv reads them
+};
+
+SEQIK_HD bool resample_neighbours(const int32_t *prev, const int32_t *next, bool bridge, int32_t g, int32_t n,
+                                  PchipNeighbours &k)
 {
-    const int32_t n = p.n_frames;
-    const double u = resample_x(i, p.nts);
-    const int32_t j = resample_interval(u, p.ots, p.inv_ots, n);
-    const bool bridge = p.flags & SEQIK_RESAMPLE_BRIDGE;
-    int32_t iP, iA, iB, iQ;
     if (bridge) {
-        bool tail;
-        if (!resample_bridge_stencil(prev, next, j, n, iP, iA, iB, iQ, tail)) return resample_nan();
-        if (!resample_bridge_ok(u, iA, iB, tail, p.ots, p.max_gap)) return resample_nan();
+        if (prev[g] != g) return false;
+        k.m1 = g > 0 ? prev[g - 1] : -1;
+        k.p1 = g + 1 < n ? next[g + 1] : n;
+        k.m2 = k.m1 > 0 ? prev[k.m1 - 1] : -1;
+        k.p2 = k.p1 + 1 < n ? next[k.p1 + 1] : n;
     } else {
-        iA = j < n - 2 ? j : n - 2;
-        iB = iA + 1;
-        iP = iA - 1;
-        iQ = iA + 2;
+        k.m1 = g - 1;
+        k.p1 = g + 1;
+        k.m2 = g - 2;
+        k.p2 = g + 2;
     }
-    const bool hp = iP >= 0, hq = iQ < n;
-    const PchipKnot P = {hp ? resample_x(iP, p.ots) : 0.0, hp ? ych[(int64_t)iP * p.width + col] : 0.0, hp};
-    const PchipKnot A = {resample_x(iA, p.ots), ych[(int64_t)iA * p.width + col], true};
-    const PchipKnot B = {resample_x(iB, p.ots), ych[(int64_t)iB * p.width + col], true};
-    const PchipKnot Q = {hq ? resample_x(iQ, p.ots) : 0.0, hq ? ych[(int64_t)iQ * p.width + col] : 0.0, hq};
-    if (!bridge && !(is_finite(P.y) && is_finite(A.y) && is_finite(B.y) && is_finite(Q.y))) return resample_nan();
-    return pchip_eval(P, A, B, Q, u);
+    k.hm1 = k.m1 >= 0;
+    k.hp1 = k.p1 < n;
+    if (!k.hm1 && !k.hp1) return false;
+    k.hm2 = k.hm1 && !k.hp1 && k.m2 >= 0;
+    k.hp2 = !k.hm1 && k.hp1 && k.p2 < n;
+    return true;
 }
 
-// a knot is missing when any value of its record is non-finite
-SEQIK_HD bool resample_knot_valid(const double *rec, int width)
-{
-    bool ok = true;
-    for (int k = 0; k < width; ++k) ok = ok && is_finite(rec[k]);
-    return ok;
-}
-
-// One chain on the host: the neighbour tables.
-inline void resample_tables_chain(const double *y, int32_t n, int width, int32_t *prev, int32_t *next)
-{
-    int32_t last = -1;
-    for (int32_t j = 0; j < n; ++j) {
-        if (resample_knot_valid(y + (int64_t)j * width, width)) last = j;
-        prev[j] = last;
-    }
-    int32_t first = n;
-    for (int32_t j = n - 1; j >= 0; --j) {
-        if (prev[j] == j) first = j;
-        next[j] = first;
-    }
-}
-
-// One chain on the host: y [n_frames][width] -> out [n_out][width]; prev / next are filled here in bridge mode.
-inline void resample_chain(const double *y, const ResampleParams &p, int32_t *prev, int32_t *next, double *out)
-{
-    if (p.flags & SEQIK_RESAMPLE_BRIDGE) resample_tables_chain(y, p.n_frames, p.width, prev, next);
-    for (int32_t i = 0; i < p.n_out; ++i)
-        for (int c = 0; c < p.width; ++c) out[(int64_t)i * p.width + c] = resample_sample(y, prev, next, p, i, c);
-}
-
-// ---- derivatives of the interpolant (include/seqik_resample_der.h) ----
-constexpr int kResampleValue = 1, kResampleD1 = 2, kResampleD2 = 4;  // orders 0, 1, 2 as bits of `want`
-
-// d/ds and d2/ds2 of c0 s^3 + c1 s^2 + c2 s + c3; 3 c0, 2 c1 and 6 c0 are one rounding each
-SEQIK_HD double pchip_horner_d1(double c0, double c1, double c2, double s)
-{
-    const double r = fma_(fma_(3.0 * c0, s, 2.0 * c1), s, c2);
-    return r == r ? r : resample_nan();
-}
-
-SEQIK_HD double pchip_horner_d2(double c0, double c1, double s)
-{
-    const double r = fma_(6.0 * c0, s, 2.0 * c1);
-    return r == r ? r : resample_nan();
-}
-
-// pchip_eval for the orders in `want`: v[0] the value (pchip_eval's operations), v[1] and v[2] the first and second
-// derivative.  A sample ON knot B (the last knot's alone) takes that knot's derivative d_B as its first derivative, as it
-// takes y_B as its value; its second derivative is the last interval's at s = h.  Orders not asked for are left alone.
-SEQIK_HD void pchip_eval_der(const PchipKnot &P, const PchipKnot &A, const PchipKnot &B, const PchipKnot &Q, double u,
-                             int want, double v[3])
-{
-    const PchipKnot none = {0.0, 0.0, false};
-    const double da = pchip_deriv(none, P, A, B, Q), db = pchip_deriv(P, A, B, Q, none);
-    double c0, c1;
-    pchip_coefs(A.x, A.y, B.x, B.y, da, db, c0, c1);
-    const double s = u - A.x;
-    const bool on_b = u == B.x;
-    if (want & kResampleValue) v[0] = on_b ? B.y : pchip_horner(c0, c1, da, A.y, s);
-    if (want & kResampleD1) v[1] = on_b ? (db == db ? db : resample_nan()) : pchip_horner_d1(c0, c1, da, s);
-    if (want & kResampleD2) v[2] = pchip_horner_d2(c0, c1, s);
-}
-
-// resample_sample for the orders in `want` (interval, stencil, bridge and max_gap rules are resample_sample's): where
-// the value is NaN by those rules every order is
+// One output sample, the orders in `want` (v as pchip_cubic_orders): sample i, column col of the chain at ych
+// ([n_frames][width]); prev / next: the chain's tables in bridge mode.  Where the interval, stencil, bridge and max_gap
+// rules refuse a value every order is NaN.
 SEQIK_HD void resample_sample_der(const double *ych, const int32_t *prev, const int32_t *next, const ResampleParams &p,
                                   int32_t i, int col, int want, double v[3])
 {
@@ -280,7 +268,39 @@ SEQIK_HD void resample_sample_der(const double *ych, const int32_t *prev, const 
     pchip_eval_der(P, A, B, Q, u, want, v);
 }
 
-// One chain on the host, the orders in `want`: out_k [n_out][width], a null one is not written.
+SEQIK_HD double resample_sample(const double *ych, const int32_t *prev, const int32_t *next, const ResampleParams &p,
+                                int32_t i, int col)
+{
+    double v[3];
+    resample_sample_der(ych, prev, next, p, i, col, kResampleValue, v);
+    return v[0];
+}
+
+// a knot is missing when any value of its record is non-finite
+SEQIK_HD bool resample_knot_valid(const double *rec, int width)
+{
+    bool ok = true;
+    for (int k = 0; k < width; ++k) ok = ok && is_finite(rec[k]);
+    return ok;
+}
+
+// One chain on the host: the neighbour tables.
+inline void resample_tables_chain(const double *y, int32_t n, int width, int32_t *prev, int32_t *next)
+{
+    int32_t last = -1;
+    for (int32_t j = 0; j < n; ++j) {
+        if (resample_knot_valid(y + (int64_t)j * width, width)) last = j;
+        prev[j] = last;
+    }
+    int32_t first = n;
+    for (int32_t j = n - 1; j >= 0; --j) {
+        if (prev[j] == j) first = j;
+        next[j] = first;
+    }
+}
+
+// One chain on the host: y [n_frames][width] -> out_value, out_d1, out_d2 [n_out][width], a null one is not asked for and
+// not written; prev / next are filled here in bridge mode.
 inline void resample_chain_der(const double *y, const ResampleParams &p, int32_t *prev, int32_t *next, double *out_value,
                                double *out_d1, double *out_d2)
 {
@@ -295,6 +315,11 @@ inline void resample_chain_der(const double *y, const ResampleParams &p, int32_t
             if (out_d1) out_d1[e] = v[1];
             if (out_d2) out_d2[e] = v[2];
         }
+}
+
+inline void resample_chain(const double *y, const ResampleParams &p, int32_t *prev, int32_t *next, double *out)
+{
+    resample_chain_der(y, p, prev, next, out, nullptr, nullptr);
 }
 
 }  // namespace seqik

@@ -24,10 +24,10 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip", "seqik_resample_der.hip"]
+                 "seqik_head_align.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
-                "seqik_head_align.hpp", "seqik_resample_kernels.hpp"]
+                "seqik_head_align.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -613,17 +613,9 @@ def _resample_flags(missing, max_gap):
     return (RESAMPLE_BRIDGE if missing == "bridge" else 0), (-1 if max_gap is None else int(max_gap))
 
 
-def resample_pchip(y, original_ts, new_ts, missing="error", max_gap=None, device=-1):
-    """``seqik_resample_pchip`` on a host array: records ``(..., N, W)`` float64 (W in 1..16) at time step
-    ``original_ts`` -> ``(..., n_out, W)`` at ``new_ts`` with scipy's PCHIP (``pchip_interpolate``), every leading index a
-    chain of its own.  Knot j sits at ``j * original_ts``, sample i at ``i * new_ts``, ``n_out = resample_count(...)``;
-    the samples behind the last knot continue the last cubic, as scipy does.
-
-    ``missing``: ``"error"`` (default) refuses non-finite input with ``ValueError``, as scipy does; ``"bridge"`` treats a
-    record with a non-finite value as a missing knot and resamples every chain over its valid knots alone
-    (``pchip_interpolate(x[valid], y[valid], u)``): NaN in front of the first valid knot, from one ``original_ts`` behind
-    the last one, and throughout a chain with fewer than two valid knots.  ``max_gap`` (bridge mode): samples strictly
-    inside an interval that spans more than ``max_gap`` missing knots stay NaN; None = no limit."""
+def _resample_host_args(y, original_ts, new_ts, missing, max_gap):
+    """What ``resample_pchip`` and ``resample_pchip_der`` check and hand on: the contiguous float64 ``y`` (..., N, W), the
+    shape of one output plane, and the arguments of the C call in front of and behind the output pointers."""
     flags, gap = _resample_flags(missing, max_gap)
     y = np.ascontiguousarray(y, dtype=np.float64)
     if y.ndim < 2:
@@ -637,9 +629,23 @@ def resample_pchip(y, original_ts, new_ts, missing="error", max_gap=None, device
         raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
     n_out = resample_count(N, original_ts, new_ts)
     C = int(np.prod(y.shape[:-2], dtype=np.int64))
-    out = np.full(y.shape[:-2] + (n_out, W), np.nan)
-    _call("seqik_resample_pchip", _data(y), C, N, W, float(original_ts), float(new_ts), flags, gap, _data(out), n_out,
-          int(device))
+    return y.shape[:-2] + (n_out, W), (_data(y), C, N, W, float(original_ts), float(new_ts), flags, gap), n_out
+
+
+def resample_pchip(y, original_ts, new_ts, missing="error", max_gap=None, device=-1):
+    """``seqik_resample_pchip`` on a host array: records ``(..., N, W)`` float64 (W in 1..16) at time step
+    ``original_ts`` -> ``(..., n_out, W)`` at ``new_ts`` with scipy's PCHIP (``pchip_interpolate``), every leading index a
+    chain of its own.  Knot j sits at ``j * original_ts``, sample i at ``i * new_ts``, ``n_out = resample_count(...)``;
+    the samples behind the last knot continue the last cubic, as scipy does.
+
+    ``missing``: ``"error"`` (default) refuses non-finite input with ``ValueError``, as scipy does; ``"bridge"`` treats a
+    record with a non-finite value as a missing knot and resamples every chain over its valid knots alone
+    (``pchip_interpolate(x[valid], y[valid], u)``): NaN in front of the first valid knot, from one ``original_ts`` behind
+    the last one, and throughout a chain with fewer than two valid knots.  ``max_gap`` (bridge mode): samples strictly
+    inside an interval that spans more than ``max_gap`` missing knots stay NaN; None = no limit."""
+    shape, front, n_out = _resample_host_args(y, original_ts, new_ts, missing, max_gap)
+    out = np.full(shape, np.nan)
+    _call("seqik_resample_pchip", *front, _data(out), n_out, int(device))
     return out
 
 
@@ -649,19 +655,26 @@ def resample_workspace_bytes(n_chains, n_frames, missing="error") -> int:
     return int(load().seqik_resample_workspace_bytes(int(n_chains), int(n_frames), _resample_flags(missing, None)[0]))
 
 
+def _resample_device_call(name, d_y, n_chains, n_frames, width, original_ts, new_ts, planes, missing, max_gap,
+                          d_workspace, stream):
+    """``name`` (one of the two ``_device`` entry points) with ``planes``: (argument name, pointer or tensor) per output."""
+    flags, gap = _resample_flags(missing, max_gap)
+    n_out = resample_count(n_frames, original_ts, new_ts)
+    ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
+    _call(name, _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames), int(width), float(original_ts),
+          float(new_ts), flags, gap, *[_ptr(d, what, (n_chains, n_out, width)) for what, d in planes], n_out, ws,
+          _stream_ptr(stream))
+    return n_out
+
+
 def resample_pchip_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d_out, missing="error", max_gap=None,
                           d_workspace=0, stream=0):
     """``seqik_resample_pchip_device``: ``d_y`` (C, N, W) -> ``d_out`` (C, n_out, W) float64, raw device pointers (ints) or
     torch tensors, asynchronous on ``stream`` (a hipStream_t as int, or a torch stream).  Nothing is checked per frame:
     in the default mode a non-finite knot makes the samples whose stencil touches it NaN.  ``d_workspace`` (bridge mode):
     ``resample_workspace_bytes`` bytes; as a tensor, int32 of ``2 * C * N`` elements (prev, then next).  Returns n_out."""
-    flags, gap = _resample_flags(missing, max_gap)
-    n_out = resample_count(n_frames, original_ts, new_ts)
-    ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
-    _call("seqik_resample_pchip_device", _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
-          int(width), float(original_ts), float(new_ts), flags, gap, _ptr(d_out, "out", (n_chains, n_out, width)), n_out,
-          ws, _stream_ptr(stream))
-    return n_out
+    return _resample_device_call("seqik_resample_pchip_device", d_y, n_chains, n_frames, width, original_ts, new_ts,
+                                 [("out", d_out)], missing, max_gap, d_workspace, stream)
 
 
 #: entry points of include/seqik_resample_der.h (derivatives of the PCHIP interpolant), additive to ABI 7
@@ -689,22 +702,9 @@ def resample_pchip_der(y, original_ts, new_ts, der=(0, 1), missing="error", max_
     bits), 1 and 2, without repeats.  Returns a tuple of ``(..., n_out, W)`` arrays in the order of ``der``, in units of
     ``y`` per unit of ``original_ts`` (squared for order 2).  Every order is NaN exactly where the value is."""
     orders = _resample_orders(der)
-    flags, gap = _resample_flags(missing, max_gap)
-    y = np.ascontiguousarray(y, dtype=np.float64)
-    if y.ndim < 2:
-        raise ValueError(f"y must have shape (..., N, W), got {y.shape}")
-    N, W = y.shape[-2:]
-    if not 1 <= W <= RESAMPLE_MAX_WIDTH:
-        raise ValueError(f"the record width must lie in 1..{RESAMPLE_MAX_WIDTH}, got {W}")
-    if N < 2:
-        raise ValueError("The number of knots must be at least 2 (scipy: `x` must contain at least 2 elements)")
-    if not flags and not np.isfinite(y).all():
-        raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
-    n_out = resample_count(N, original_ts, new_ts)
-    C = int(np.prod(y.shape[:-2], dtype=np.int64))
-    planes = [np.full(y.shape[:-2] + (n_out, W), np.nan) if k in orders else None for k in RESAMPLE_DER_ORDERS]
-    _call("seqik_resample_der", _data(y), C, N, W, float(original_ts), float(new_ts), flags, gap, _data(planes[0]),
-          _data(planes[1]), _data(planes[2]), n_out, int(device))
+    shape, front, n_out = _resample_host_args(y, original_ts, new_ts, missing, max_gap)
+    planes = [np.full(shape, np.nan) if k in orders else None for k in RESAMPLE_DER_ORDERS]
+    _call("seqik_resample_der", *front, *[_data(plane) for plane in planes], n_out, int(device))
     return tuple(planes[k] for k in orders)
 
 
@@ -713,14 +713,8 @@ def resample_der_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d_v
     """``seqik_resample_der_device``: ``d_y`` (C, N, W) -> those of ``d_value``, ``d_d1``, ``d_d2`` (C, n_out, W) float64
     that are given (0 / None: not computed, not written; at least one), raw device pointers (ints) or torch tensors,
     asynchronous on ``stream``.  ``d_workspace`` and what is (not) checked: ``resample_pchip_device``.  Returns n_out."""
-    flags, gap = _resample_flags(missing, max_gap)
-    n_out = resample_count(n_frames, original_ts, new_ts)
-    ws = _ptr(d_workspace, "workspace", (2, n_chains, n_frames), "int32")
-    shape = (n_chains, n_out, width)
-    _call("seqik_resample_der_device", _ptr(d_y, "y", (n_chains, n_frames, width)), int(n_chains), int(n_frames),
-          int(width), float(original_ts), float(new_ts), flags, gap, _ptr(d_value, "value", shape), _ptr(d_d1, "d1", shape),
-          _ptr(d_d2, "d2", shape), n_out, ws, _stream_ptr(stream))
-    return n_out
+    return _resample_device_call("seqik_resample_der_device", d_y, n_chains, n_frames, width, original_ts, new_ts,
+                                 [("value", d_value), ("d1", d_d1), ("d2", d_d2)], missing, max_gap, d_workspace, stream)
 
 
 #: entry points of include/seqik_head_align.h (antenna alignment on the GPU), kept apart from the ABI-7 set of seqik.h

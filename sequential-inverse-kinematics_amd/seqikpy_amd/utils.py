@@ -87,6 +87,18 @@ def _is_plain_value(der):
     return isinstance(der, (int, np.integer)) and not isinstance(der, (bool, np.bool_)) and der == 0
 
 
+def _resample_series_on_gpu(stacked, orders, original_ts, new_ts, missing, max_gap):
+    """Series of one length, stacked (C, N), each a chain of width 1 -> one (C, n_out) array per order; ``orders`` None:
+    the value alone through ``_lib.resample_pchip``, else ``_lib.resample_pchip_der``."""
+    from . import _lib
+    y = stacked[:, :, None]
+    if orders is None:
+        res = (_lib.resample_pchip(y, original_ts, new_ts, missing=missing, max_gap=max_gap),)
+    else:
+        res = _lib.resample_pchip_der(y, original_ts, new_ts, der=orders, missing=missing, max_gap=max_gap)
+    return [r[:, :, 0] for r in res]
+
+
 def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error", max_gap=None, der=0):
     """Resamples one series from time step ``original_ts`` to ``new_ts`` with a shape-preserving cubic (PCHIP) over
     ``[0, N * original_ts)`` (``seqikpy/utils.py:332-349``).  As there: if the interpolation fails, infinities and the
@@ -103,21 +115,18 @@ def interpolate_signal(signal, original_ts, new_ts, on_gpu=False, missing="error
     returns a list with one array per order.  The host path hands ``der`` to ``pchip_interpolate``; ``on_gpu=True``
     computes it with ``_lib.resample_pchip_der`` (include/seqik_resample_der.h), NaN exactly where the value is NaN."""
     plain = _is_plain_value(der)
+    orders = None
     if not plain:
         from . import _lib
         orders = _lib._resample_orders(der)     # scipy alone would take any order: both paths accept the same ones
     if on_gpu:
-        from . import _lib
         y = np.asarray(signal, dtype=np.float64)
         if y.ndim != 1:
             raise ValueError(f"signal must be one series (N,), got shape {y.shape}")
         if y.shape[0] < 2:
             raise ValueError("`x` must contain at least 2 elements.")
         _reference_grid_check(y.shape[0], original_ts)
-        if plain:
-            return _lib.resample_pchip(y[:, None], original_ts, new_ts, missing=missing, max_gap=max_gap)[:, 0]
-        res = _lib.resample_pchip_der(y[:, None], original_ts, new_ts, der=orders, missing=missing, max_gap=max_gap)
-        res = [r[:, 0].copy() for r in res]
+        res = [r[0].copy() for r in _resample_series_on_gpu(y[None], orders, original_ts, new_ts, missing, max_gap)]
         return res if np.iterable(der) else res[0]
     if missing != "error" or max_gap is not None:
         raise ValueError("missing / max_gap need on_gpu=True (the host path is the reference's own)")
@@ -162,14 +171,8 @@ def interpolate_joint_angles(joint_angles_dict, **kwargs):
         groups.setdefault(y.shape[0], []).append((dof, y))
     out = {}
     for items in groups.values():
-        stacked = np.stack([y for _, y in items])[:, :, None]
-        if orders is None:
-            res = _lib.resample_pchip(stacked, original_ts, new_ts, missing=missing, max_gap=max_gap)
-            for k, (dof, _) in enumerate(items):
-                out[dof] = res[k, :, 0].copy()
-            continue
-        res = _lib.resample_pchip_der(stacked, original_ts, new_ts, der=orders, missing=missing, max_gap=max_gap)
+        res = _resample_series_on_gpu(np.stack([y for _, y in items]), orders, original_ts, new_ts, missing, max_gap)
         for k, (dof, _) in enumerate(items):
-            per_order = [r[k, :, 0].copy() for r in res]
+            per_order = [r[k].copy() for r in res]
             out[dof] = per_order if np.iterable(der) else per_order[0]
     return {dof: out[dof] for dof in joint_angles_dict}

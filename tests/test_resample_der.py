@@ -1,5 +1,5 @@
 """Joint-angle velocities and accelerations: the first and second derivative of the PCHIP interpolant
-(include/seqik_resample_der.h, csrc/seqik_resample.hpp: resample_sample_der, csrc/seqik_resample_der.hip).
+(include/seqik_resample_der.h, csrc/seqik_resample.hpp: resample_sample_der, csrc/seqik_resample.hip).
 
 Every output is pinned three ways: to the host-run rules bit for bit (the GPU tier), to a 200-bit yardstick within a
 bound measured on scipy (both tiers), and the value plane to the bits of the existing entry points.
@@ -27,13 +27,11 @@ MEASURED (EXPERIMENTS.md, "Resampling derivatives"; the tests print the figures,
 """
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import DOFS, PKG_PARENT, ROOT, load_golden
+from conftest import DOFS, ROOT, load_golden
 from test_capi_symbols import assert_same_class, header_prototypes
 from test_resample import (STEP_PAIRS, ResampleHarness, gap_mask, rs_harness, scipy_bridge, shipped_angles,  # noqa: F401
                            with_gaps)
@@ -55,7 +53,7 @@ _MP.prec = 200
 # ------------------------------------------------------ host rules ------------------------------------------------------
 
 class DerHarness:
-    """ctypes front end of tests/harness/resample_der_harness.hip"""
+    """ctypes front end of the derivative entry points of tests/harness/resample_harness.hip"""
 
     def __init__(self, so):
         self.lib = ctypes.CDLL(so)
@@ -93,21 +91,8 @@ class DerHarness:
 
 
 @pytest.fixture(scope="module")
-def der_harness(hiplib):
-    hiplib.load()   # the product library first, as rs_harness does
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "resample_der_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libresample_der_harness.so")
-    deps = [src, os.path.join(ROOT, "include", "seqik_resample.h")] + [
-        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_resample.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return DerHarness(so)
+def der_harness(rs_harness):
+    return DerHarness(rs_harness.lib._name)   # the library rs_harness built (tests/test_resample.py)
 
 
 # ------------------------------------------------------ yardstick ------------------------------------------------------
@@ -260,10 +245,11 @@ def test_header_and_extension_table(hiplib):
                   hiplib.GAPS_EXPORTED_SYMBOLS, hiplib.RESAMPLE_EXPORTED_SYMBOLS, hiplib.HEAD_ALIGN_EXPORTED_SYMBOLS):
         assert not set(DER_SYMBOLS) & set(other)
     assert lib.seqik_abi_version() == 7 == hiplib.ABI_VERSION
-    assert "seqik_resample_der.hip" in hiplib.COMPILE_UNITS
-    assert {"seqik_resample_der.hip", "seqik_resample_kernels.hpp", "seqik_resample.hpp"} <= set(hiplib.SOURCES)
+    assert "seqik_resample.hip" in hiplib.COMPILE_UNITS
+    assert {"seqik_resample.hip", "seqik_resample.hpp"} <= set(hiplib.SOURCES)
     assert "seqik_resample_der.h" in open(os.path.join(ROOT, "setup.py")).read()
-    assert not {"seqik_resample.hip", "seqik_resample.hpp", "seqik_resample_kernels.hpp"} & set(hiplib.KERNEL_SOURCES)
+    assert not {"seqik_resample.hip", "seqik_resample.hpp"} & set(hiplib.KERNEL_SOURCES)
+    assert not {"seqik_resample_der.hip", "seqik_resample_kernels.hpp"} & set(hiplib.SOURCES + hiplib.KERNEL_SOURCES)
 
 
 def _c_call(hiplib, y=1, planes=(1, 1, 1), n_chains=2, n_frames=100, width=7, ots=1e-2, nts=1e-3, flags=0, max_gap=-1,
@@ -669,7 +655,7 @@ def test_device_equals_host_rules_and_meets_the_bound(hiplib, der_harness, f, v)
 
 
 def tiles_per_chain(n_out, width, ots, nts):
-    """the launch geometry of csrc/seqik_resample_kernels.hpp: tiles of 64 * rows flat output elements"""
+    """the launch geometry of csrc/seqik_resample.hip: tiles of 64 * rows flat output elements"""
     lines = (256 // width - 4) * (ots / nts) * width / 64.0
     rows = 64 if lines >= 64 else max(int(lines), 1)
     return -(-n_out * width // (64 * rows))
