@@ -80,7 +80,7 @@ inline void make_leg_consts(const SeqikLegParams &lp, const SeqikAffine *aff, Le
         const int na = kNumActive[stage - 1];
         const double *seed = lp.seeds + kSeedOffset[stage - 1];
         sc.max_nfev = 100 * n;
-        sc.pad_ = 0;
+        sc.fd_wide = 0;
         // translations: CTr_pitch carries -coxa, FTi -femur, TiTa -tibia, claw -tarsus
         switch (stage) {
         case 1: sc.tz_a = 0.0; sc.tz_b = 0.0; sc.tz_last = -lp.seg[0]; break;
@@ -115,6 +115,8 @@ inline void make_leg_consts(const SeqikLegParams &lp, const SeqikAffine *aff, Le
             sc.ub_out[j] = hi;
             sincos_cw(lo, sc.sc_lb[j][0], sc.sc_lb[j][1]);
             sincos_cw(hi, sc.sc_ub[j][0], sc.sc_ub[j][1]);
+            // may the finite-difference step of this joint skip _adjust_scheme_to_bounds' distance logic?
+            if (fd_limits_wide(sc.lb[j], sc.ub[j])) sc.fd_wide |= 1 << j;
         }
         // inert entries of the start vector, made strictly feasible as scipy does, then the
         // partial sums of squares that ||x0 / sqrt(v)|| and ||x|| need (link order, from 0.0)

@@ -81,6 +81,14 @@ SEQIK_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, 
 #ifndef SEQIK_FAST_PATHS
 #define SEQIK_FAST_PATHS 1   // wave-uniform fast paths, see "Wave-uniform fast paths" below; 0 = plain code (A/B)
 #endif
+// The three cuts of the per-pass path (round 7), one bit each so that each can be built and counted alone:
+//   1  fd_step without its distance logic where the limits are wide against the step (fd_limits_wide, fd_jacobian)
+//   2  sincos_cw's quadrant signs by XOR into the sign bit
+//   4  stage 1's end-effector evaluation with the identity prefix written out (residual_sc_stage1)
+// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all three.
+#ifndef SEQIK_PASS_CUTS
+#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 7 : 0)
+#endif
 // "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
 SEQIK_HD bool wave_any(bool c)
 {
@@ -297,7 +305,8 @@ struct StageConst {
     double thr_lb_g[2], thr_ub_g[2];  // thr_lb / thr_ub, NaN where the bound is infinite (the comparison is then false)
     double sc_lb[2][2], sc_ub[2][2];  // [joint][sin, cos] of lb_out / ub_out
     int32_t max_nfev;      // 100 * number of links of the stage chain (4, 6, 8, 9)
-    int32_t pad_;
+    int32_t fd_wide;       // bit j: the limits of active joint j are wide against the finite-difference step (fd_limits_wide);
+                           // 3 = fd_step is fd_step_wide for the whole stage (the unused slot of stage 4 has limits -1, 1)
 };
 
 // Optional fused alignment (AlignPose.align_leg, seqikpy/alignment.py:436-487): the key points
@@ -336,6 +345,12 @@ struct Frame {
     double r[9];
     double t[3];
 };
+
+// v with its sign bit flipped where bit 31 of `sign_bit` is set (the other bits of `sign_bit` must be 0): -v or v
+SEQIK_HD double flip_sign_if(double v, uint32_t sign_bit)
+{
+    return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, v) ^ ((uint64_t)sign_bit << 32));
+}
 
 // ---------------------------------------------------------------------------
 // sin / cos -- same algorithm and constants as oracle_sincos()
@@ -377,8 +392,18 @@ SEQIK_HD void sincos_cw(double x, double &sn, double &cs)
     int q = ((int)fn) & 3;
     double s_sel = (q & 1) ? kc : ks;
     double c_sel = (q & 1) ? ks : kc;
+#if SEQIK_PASS_CUTS & 2
+    // quadrant signs: sin is negated in quadrants 2 and 3 (bit 1 of q), cos in quadrants 1 and 2 (bit 1 of q + 1).  A
+    // negation is a flip of the sign bit, so the bit is moved to position 31 and XORed into the high word: three 32-bit
+    // integer instructions per output where the compare + select forms below need a compare that writes a mask and two
+    // selects.  Same bits for every operand (the plain form's `-v` is the same flip).
+    const uint32_t uq = (uint32_t)q;
+    sn = flip_sign_if(s_sel, (uq & 2u) << 30);
+    cs = flip_sign_if(c_sel, ((uq + 1u) & 2u) << 30);
+#else
     sn = (q & 2) ? -s_sel : s_sel;
     cs = ((q == 1) || (q == 2)) ? -c_sel : c_sel;
+#endif
 }
 
 // next representable double after b in the direction of `toward` (b != toward)
@@ -608,6 +633,29 @@ SEQIK_HD double fd_step(double x, double lb, double ub)
     if (violated && fitting) h = -h;
     else if (!fitting) h = (upper_dist >= lower_dist) ? upper_dist : -lower_dist;
     return h;
+}
+
+// Are the limits of a joint wide against the finite-difference step?  (Host: make_leg_consts -> StageConst::fd_wide.)
+// True when a bound is infinite or ub - lb >= 4 RSTEP max(1, |lb|, |ub|).  Then, for every x in [lb, ub]:
+//   * |h| = RSTEP max(1, |x|) <= RSTEP max(1, |lb|, |ub|) =: hmax (RSTEP is a power of two: the products are exact);
+//   * one of the exact distances x - lb, ub - x is at least (ub - lb) / 2 and rounding takes off at most half an ulp, so
+//     max(fl(x - lb), fl(ub - x)) >= (ub - lb) / 2 * (1 - 2^-53) >= 2 hmax (1 - 2^-53) / (1 + 2^-53) > hmax (the second
+//     step: the test above was made on fl(ub - lb) <= (ub - lb)(1 + 2^-53)); with an infinite bound that distance is inf;
+//   * so fd_step's `fitting` is true, its `!fitting` replacement cannot be taken, and its result is `violated ? -h : h`.
+// Every shipped limit pair is ~1e8 times wider than h; fd_step's distance logic only matters for made-up limits a few
+// 1e-8 apart, and those keep the general routine.
+SEQIK_HD bool fd_limits_wide(double lb, double ub)
+{
+    const double RSTEP = 1.4901161193847656e-08;
+    if (!is_finite(lb) || !is_finite(ub)) return true;
+    return ub - lb >= 4.0 * RSTEP * fmax(1.0, fmax(fabs(lb), fabs(ub)));
+}
+
+// fd_step for x in [lb, ub] when fd_limits_wide(lb, ub): the nominal step, its two compares and a sign flip
+SEQIK_HD double fd_step_wide(double x, double lb, double ub)
+{
+    const double h = fd_step_nominal(x);
+    return fd_step_violates(x, h, lb, ub) ? -h : h;
 }
 
 // SVD of the augmented matrix [[J_h], [diag(q)]] restricted to the active columns, by
@@ -1232,8 +1280,8 @@ SEQIK_HD void frame_after_active(const StageProblem<STAGE> &P, double sa, double
 // End-effector residual for given sin/cos pairs of the active joints.
 // pe (nullable): the end-effector position itself, f = pe - target
 template <int STAGE>
-SEQIK_HD void residual_sc(const StageProblem<STAGE> &P, double sa, double ca, double sb, double cb, double *f,
-                          double *pe = nullptr)
+SEQIK_HD void residual_sc_general(const StageProblem<STAGE> &P, double sa, double ca, double sb, double cb, double *f,
+                                  double *pe = nullptr)
 {
     Frame after;
     frame_after_active<STAGE>(P, sa, ca, sb, cb, after);
@@ -1243,6 +1291,47 @@ SEQIK_HD void residual_sc(const StageProblem<STAGE> &P, double sa, double ca, do
         if (pe) pe[i] = e;
         f[i] = e - P.target[i];
     }
+}
+
+// The same for STAGE 1 in closed form.  Stage 1's prefix is the identity and its active links carry no translation (tz_a =
+// tz_b = 0.0: make_leg_consts), so the general chain product multiplies by literal ones and zeros.  The compiler folds the
+// ones; it may not fold `0 * c` (a zero with c's sign) or `+ 0.0`.  Written out, with z = "a zero of some sign":
+//   frame after link a (X):  r = [1 z z; 0 ca' -sa'; 0 sa' ca'],  t = (+0, +0, +0)      (0 * 0 + 0 and 1 * 0 + 0 are +0)
+//     where ca' = fma(0, sa, ca), -sa' = fma(0, ca, -sa), ...: the operand itself when it is not a zero, else a zero;
+//   frame after link b (Y):  third column r02 = fma(z, cb, sb), r12 = fma(-sa', cb, 0 * sb), r22 = fma(ca', cb, 0 * sb),
+//                            t = (r_i2 of link a) * 0 + (+0) = (+0, +0, +0) for finite sin / cos;
+//   end effector:            e_i = r_i2 * tz_last + (+0).
+// A multiply-add whose exact product is not zero and whose addend is a zero rounds the product alone -- the value, zero
+// sign of an underflow included, of the plain multiplication -- and x + (+-0) = x for x != 0.  So wherever none of sa, sb
+// (cos is never 0) is a zero, r02 = sb, r12 = (-sa) * cb, r22 = ca * cb bit for bit.  Where one is (sin(+-0); seeds of
+// exactly 0 occur), the general r_i2 is a zero whose sign depends on the dropped terms, and so may be the closed one with
+// another sign -- but e_i = (+-0) * tz_last + (+0) = +0 in both: the `+ 0.0` of the translation, which is kept, absorbs
+// every sign.  Hence no operand needs a guard, and f / pe carry the general form's bits for all finite inputs
+// (tests/test_pass_path_cuts.py compares the two forms, zero operands and zero signs included).  Only the three
+// evaluations of a pass use this; the hand-off frame at a frame's end -- where the signs of the zeros of r would have to be
+// reproduced, and whose instructions cost nothing (EXPERIMENTS.md 3.16) -- stays frame_after_active.
+SEQIK_HD void residual_sc_stage1(double tz_last, const double *target, double sa, double ca, double sb, double cb, double *f,
+                                 double *pe)
+{
+    const double e[3] = {sb * tz_last + 0.0, ((-sa) * cb) * tz_last + 0.0, (ca * cb) * tz_last + 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (pe) pe[i] = e[i];
+        f[i] = e[i] - target[i];
+    }
+}
+
+template <int STAGE>
+SEQIK_HD void residual_sc(const StageProblem<STAGE> &P, double sa, double ca, double sb, double cb, double *f,
+                          double *pe = nullptr)
+{
+#if SEQIK_PASS_CUTS & 4
+    if constexpr (STAGE == 1) {
+        residual_sc_stage1(P.tz_last, P.target, sa, ca, sb, cb, f, pe);
+        return;
+    }
+#endif
+    residual_sc_general<STAGE>(P, sa, ca, sb, cb, f, pe);
 }
 
 // End-effector residual at (xa, xb); also returns the sin/cos pairs.
@@ -1260,12 +1349,20 @@ SEQIK_HD void eval_residual(const StageProblem<STAGE> &P, double xa, double xb, 
 // link a and reuses link b's sin/cos, column b the other way round.
 template <int STAGE>
 SEQIK_HD void fd_jacobian(const StageProblem<STAGE> &P, const double *x, const double *f0, const double *lb,
-                          const double *ub, double sa, double ca, double sb, double cb, double J[3][2])
+                          const double *ub, double sa, double ca, double sb, double cb, bool fd_general, double J[3][2])
 {
     using T = StageTraits<STAGE>;
 #if SEQIK_FAST_PATHS
+    // fd_general (wave-uniform, formed once per stage: run_stage): some joint of the stage has limits that are not wide
+    // against the step (StageConst::fd_wide).  Otherwise fd_step is fd_step_wide: a select on the compares that the
+    // test for the nominal step makes anyway, no ballot and no branch.
     double h_a = fd_step_nominal(x[0]), h_b = (T::NA == 2) ? fd_step_nominal(x[1]) : 0.0;
-    if (wave_any(fd_step_violates(x[0], h_a, lb[0], ub[0]) || (T::NA == 2 && fd_step_violates(x[1], h_b, lb[1], ub[1])))) {
+    const bool viol_a = fd_step_violates(x[0], h_a, lb[0], ub[0]);
+    const bool viol_b = T::NA == 2 && fd_step_violates(x[1], h_b, lb[1], ub[1]);
+    if ((SEQIK_PASS_CUTS & 1) && !fd_general) {
+        h_a = viol_a ? -h_a : h_a;
+        if constexpr (T::NA == 2) h_b = viol_b ? -h_b : h_b;
+    } else if (wave_any(viol_a || viol_b)) {
         SEQIK_BLK_COUNT(CNT_FD_SLOW);
         h_a = fd_step(x[0], lb[0], ub[0]);
         if constexpr (T::NA == 2) h_b = fd_step(x[1], lb[1], ub[1]);
@@ -1344,13 +1441,17 @@ SEQIK_HD bool pair_is_odd()
 // fd_jacobian with one column per lane of a pair (stages with two active joints)
 template <int STAGE>
 SEQIK_HD void fd_jacobian_pair(const StageProblem<STAGE> &P, const double *x, const double *f0, const double *lb,
-                               const double *ub, double sa, double ca, double sb, double cb, bool odd, double J[3][2])
+                               const double *ub, double sa, double ca, double sb, double cb, bool odd, bool fd_general,
+                               double J[3][2])
 {
     static_assert(StageTraits<STAGE>::NA == 2, "one active joint: nothing to split");
     const double xj = odd ? x[1] : x[0];
 #if SEQIK_FAST_PATHS
     double h = fd_step_nominal(xj);
-    if (wave_any(fd_step_violates(xj, h, odd ? lb[1] : lb[0], odd ? ub[1] : ub[0]))) {
+    const bool viol = fd_step_violates(xj, h, odd ? lb[1] : lb[0], odd ? ub[1] : ub[0]);
+    if ((SEQIK_PASS_CUTS & 1) && !fd_general) {
+        h = viol ? -h : h;   // fd_step_wide, see fd_jacobian
+    } else if (wave_any(viol)) {
         SEQIK_BLK_COUNT(CNT_FD_SLOW);
         h = fd_step(xj, odd ? lb[1] : lb[0], odd ? ub[1] : ub[0]);
     }
@@ -1565,6 +1666,9 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
     const double *lb = sc.lb;
     const double *ub = sc.ub;
     const int max_nfev = sc.max_nfev;
+    // does fd_step need its distance logic for some joint of this stage, in some lane of this wavefront?  Decided once,
+    // here (fd_limits_wide); wave-uniform, so the test in every pass is a scalar branch
+    const bool fd_general = !(SEQIK_PASS_CUTS & 1) || wave_any(sc.fd_wide != 3);
 
     StageProblem<STAGE> P;
     P.tz_a = sc.tz_a; P.tz_b = sc.tz_b; P.tz_last = sc.tz_last;
@@ -1780,8 +1884,8 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
             bool derive = true;
             if constexpr (LAT) derive = wave_any(!jac_valid);   // wave-uniform: nobody moved since the last pass
             if (derive) {
-            if constexpr (PAIRED) fd_jacobian_pair<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, odd, J);
-            else fd_jacobian<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, J);
+            if constexpr (PAIRED) fd_jacobian_pair<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, odd, fd_general, J);
+            else fd_jacobian<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, fd_general, J);
             SEQIK_BLK_END_OF(BLK_FD_JACOBIAN);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
