@@ -16,7 +16,8 @@
  * of the recording with the missing frames deleted; the frame-chunk geometry depends on n_frames alone, so chunked
  * results are pinned as well.  A missing leg-frame gets NaN angles and FK, status SEQIK_STATUS_MISSING (every stage
  * entry), nfev 0.  A chain without any non-missing frame is solved on a finite filler (the straight leg: key point k at
- * (0, 0, -(seg[0] + ... + seg[k-1]))) and all its outputs are then missing; the call still returns SEQIK_OK.
+ * (0, 0, -(seg[0] + ... + seg[k-1])), which is -0.0 for key point 0) and all its outputs are then missing; the call still
+ * returns SEQIK_OK.
  *
  * Layouts are the dense ones of seqik.h:
  *   pose, cpose  [n_seq][n_legs][n_frames][5][3]

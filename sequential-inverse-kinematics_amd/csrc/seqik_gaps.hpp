@@ -21,11 +21,11 @@ struct GapsLeg {
 
 inline void make_gaps_leg(const SeqikLegParams &lp, GapsLeg &gl)
 {
+    // z[k] = -(seg[0] + .. + seg[k-1]); the empty sum of key point 0 is negated too: -0.0, as numpy's -cumsum gives it
     double s = 0.0;
-    gl.z[0] = 0.0;
-    for (int k = 1; k < 5; ++k) {
-        s += lp.seg[k - 1];
+    for (int k = 0; k < 5; ++k) {
         gl.z[k] = -s;
+        if (k < 4) s += lp.seg[k];
     }
 }
 
@@ -56,7 +56,7 @@ SEQIK_HD int64_t gaps_slot(bool missing, int64_t t, int64_t r, int64_t n_valid)
 // element e of a padding slot: the last non-missing record (nullable when the chain has none: the filler)
 SEQIK_HD double gaps_pad_value(const double *last, const GapsLeg &gl, int e)
 {
-    double z = 0.0;
+    double z = gl.z[0];
 #pragma unroll
     for (int k = 1; k < 5; ++k) z = (e / 3 == k) ? gl.z[k] : z;  // static indices: no private array on the device
     return last ? last[e] : (e % 3 == 2 ? z : 0.0);

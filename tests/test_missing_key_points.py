@@ -8,125 +8,25 @@ and the LegInvKin* dictionaries."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, LegParamsC, leg_arrays, load_golden
+from conftest import ROOT, leg_arrays, load_golden
+from gaps_model import (inject_gaps, load_gaps_harness, np_compact, np_compact_batch, np_expand, np_expand_batch,
+                        np_missing, rows_read)
 
 GAPS_SYMBOLS = ["seqik_gaps_compact_device", "seqik_gaps_expand_device", "seqik_solve_seq_gaps",
                 "seqik_solve_generic_gaps"]
 MISSING = -100
 
 
-def _lp(seg):
-    lp = LegParamsC()
-    for i in range(4):
-        lp.seg[i] = float(seg[i])
-    return lp
-
-
-def rows_read(kind, affine):
-    rows = [0, 1, 2, 3, 4] if kind == "seq" else [0, 4]
-    return [r for r in rows if not (affine and r == 0)]
-
-
-def np_missing(pose, kind="seq", affine=False):
-    """(..., N) bool: a key point the solver reads holds a non-finite coordinate."""
-    return ~np.isfinite(pose[..., rows_read(kind, affine), :]).all(axis=(-1, -2))
-
-
-def np_compact(pose, seg, kind="seq", affine=False):
-    """The compacted and padded recording of one chain (N, 5, 3), its map and n_valid, built with numpy."""
-    miss = np_missing(pose, kind, affine)
-    keep = np.flatnonzero(~miss)
-    n = pose.shape[0]
-    if keep.size:
-        cpose = np.concatenate([pose[keep], np.repeat(pose[keep[-1]][None], n - keep.size, axis=0)])
-    else:
-        z = -np.concatenate([[0.0], np.cumsum(np.asarray(seg, dtype=np.float64))])
-        filler = np.zeros((5, 3))
-        filler[:, 2] = z
-        cpose = np.repeat(filler[None], n, axis=0)
-    mp = np.full(n, -1, np.int32)
-    mp[keep] = np.arange(keep.size, dtype=np.int32)
-    return cpose, mp, keep.size
-
-
-def np_expand(mp, compact, fill):
-    out = np.empty_like(compact)
-    out[...] = fill
-    out[mp >= 0] = compact[mp[mp >= 0]]
-    return out
-
-
-def inject_gaps(pose, rng, frac=0.05, blocks=((10, 60),), rows=(0, 1, 2, 3, 4), values=(np.nan,)):
-    """A copy of pose (N, 5, 3) with about `frac` random leg-frames and the given frame blocks made non-finite."""
-    p = np.array(pose, dtype=np.float64, copy=True)
-    n = p.shape[0]
-    hit = rng.random(n) < frac
-    for a, b in blocks:
-        hit[a:min(b, n)] = True
-    for t in np.flatnonzero(hit):
-        p[t, rng.choice(list(rows)), rng.integers(0, 3)] = values[rng.integers(0, len(values))]
-    return p
-
-
-class GapsHarness:
-    def __init__(self, so):
-        self.lib = ctypes.CDLL(so)
-        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-        self.lib.harness_gaps_compact.restype = ctypes.c_int64
-        self.lib.harness_gaps_compact.argtypes = [dp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(LegParamsC), dp, ip]
-        self.lib.harness_gaps_expand_f64.restype = None
-        self.lib.harness_gaps_expand_f64.argtypes = [ip, ctypes.c_int64, dp, ctypes.c_int32, dp]
-        self.lib.harness_gaps_expand_i32.restype = None
-        self.lib.harness_gaps_expand_i32.argtypes = [ip, ctypes.c_int64, ip, ctypes.c_int32, ctypes.c_int32, ip]
-
-    def compact(self, pose, seg, kind="seq", affine=False):
-        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-        pose = np.ascontiguousarray(pose, dtype=np.float64)
-        n = pose.shape[0]
-        cpose = np.full_like(pose, 12345.0)
-        mp = np.full(n, 777, np.int32)
-        flags = (1 if kind == "generic" else 0) | (2 if affine else 0)
-        nv = self.lib.harness_gaps_compact(pose.ctypes.data_as(dp), n, flags, ctypes.byref(_lp(seg)),
-                                           cpose.ctypes.data_as(dp), mp.ctypes.data_as(ip))
-        return cpose, mp, int(nv)
-
-    def expand(self, mp, compact, fill=None):
-        dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-        mp = np.ascontiguousarray(mp, dtype=np.int32)
-        n = mp.shape[0]
-        compact = np.ascontiguousarray(compact)
-        width = int(np.prod(compact.shape[1:])) if compact.ndim > 1 else 1
-        out = np.empty_like(compact)
-        if compact.dtype == np.float64:
-            self.lib.harness_gaps_expand_f64(mp.ctypes.data_as(ip), n, compact.ctypes.data_as(dp), width,
-                                             out.ctypes.data_as(dp))
-        else:
-            self.lib.harness_gaps_expand_i32(mp.ctypes.data_as(ip), n, compact.ctypes.data_as(ip), width, int(fill),
-                                             out.ctypes.data_as(ip))
-        return out
-
-
 @pytest.fixture(scope="module")
 def gaps_harness():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    h = load_gaps_harness()
+    if h is None:
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "gaps_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libgaps_harness.so")
-    deps = [src, os.path.join(ROOT, "include", "seqik_gaps.h")] + [
-        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_gaps.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return GapsHarness(so)
+    return h
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -509,6 +409,12 @@ def test_device_building_blocks_equal_numpy(hiplib):
                 assert np.array_equal(ang[s, l], np_expand(rm, ca[s, l], np.nan), equal_nan=True)
                 assert np.array_equal(st[s, l], np_expand(rm, cs[s, l], MISSING))
         assert np.array_equal(nv, (~np_missing(pose)).sum(axis=-1))
+        # every chain of every sequence, with the vectorised form of the same construction
+        rc, rm, rn = np_compact_batch(pose, seg)
+        assert np.array_equal(nv, rn) and np.array_equal(mp, rm)
+        assert np.array_equal(cp, rc)
+        assert np.array_equal(ang, np_expand_batch(rm, ca, np.nan), equal_nan=True)
+        assert np.array_equal(st, np_expand_batch(rm, cs, MISSING))
 
 
 @pytest.mark.gpu
