@@ -877,8 +877,10 @@ seqik_chunk_pipe_kernel(KernelArgs a, ChunkArgs ca)
                 const int64_t c = ca.serial_list[cursor];
                 leg = (int)(c % a.n_legs);
                 serial_io(a, c, io);
-                if (ca.flags && stage_wave == 0)   // (replicas write the same bytes)
-                    for (int64_t kk = lane; kk < ca.n_chunks; kk += 64) ca.flags[c * ca.n_chunks + kk] |= CHUNK_FLAG_SERIAL;
+                if (ca.flags && stage_wave == 0) {  // the chain's 64 / W replicas share its K report bytes between them
+                    const int rep = lane_replication((int)W);
+                    for (int64_t kk = lane % rep; kk < ca.n_chunks; kk += rep) ca.flags[c * ca.n_chunks + kk] |= CHUNK_FLAG_SERIAL;
+                }
             } else {
                 const int64_t vc = ca.worklist[cursor];
                 leg = (int)(vc % a.n_legs);

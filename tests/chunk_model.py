@@ -31,6 +31,61 @@ def plan(n_frames, frame_chunk=-1, frame_halo=0, frame_lead=0):
     return int(c), int(h), int(-(-n // c))
 
 
+# ---- restatement of the launch arithmetic of a chunked call (csrc/seqik_hip.hip: plan_launch, launch_chunked and the work-list
+# walks of seqik_chunk_kernel<REPAIR> / seqik_chunk_pipe_kernel<REPAIR / SERIAL>), for tests that must KNOW which branch of the
+# device-side control path an input reaches ----
+PIPE_MAX_CHUNKS = 40000      # kPipeMaxChunks: calls of at most this many chunks run on the stage pipeline by default
+REPAIR_WAVE_CAP = 4096       # lane-per-chunk REPAIR kernel: waves of the grid (the work list is walked grid-stride)
+PIPE_GROUP_CAP = 1024        # pipeline REPAIR / SERIAL kernels: workgroups of the grid
+ROOMY_WAVES = 512            # at most this many workgroups: the 256-register build of the pipeline kernels
+
+
+def pick_lanes_per_wave(n_chunks_total, lanes_per_wave=0):
+    """pick_lanes_per_wave(chunked = true): chunks a wavefront of the speculative pass carries."""
+    if 1 <= lanes_per_wave <= 64:
+        return int(lanes_per_wave)
+    return max(1, (n_chunks_total + 255) // 256) if n_chunks_total < 4096 else 64
+
+
+def wave_count(n_vseq, n_legs, w):
+    """wave_count: leg-pure wavefronts over n_vseq = n_seq * K virtual sequences, w chunks per wavefront."""
+    return -(-n_vseq // w) * n_legs
+
+
+def lane_replication(w):
+    return (64 // w) & ~7 if w <= 8 else ((64 // w) & ~1 if w <= 32 else 1)
+
+
+def items_per_wave(n_items, n_waves):
+    """W of a work-list walk: clamp(ceil(items / waves), 1, 64)."""
+    return min(max(-(-n_items // n_waves), 1), 64)
+
+
+def launch_shape(n_seq, n_legs, n_chunks, lanes_per_wave=0, pipeline=0):
+    """dict(piped, lanes, n_waves, repair_waves, roomy): `repair_waves` = the waves (lane-per-chunk kernel, block of 64) or
+    workgroups (stage pipeline) over which a round's work list is spread."""
+    total = n_seq * n_legs * n_chunks
+    piped = pipeline >= 2 or (pipeline == 0 and total <= PIPE_MAX_CHUNKS)
+    lanes = pick_lanes_per_wave(total, lanes_per_wave)
+    n_waves = wave_count(n_seq * n_chunks, n_legs, lanes)
+    return dict(piped=piped, lanes=lanes, n_waves=n_waves, repair_waves=min(n_waves, PIPE_GROUP_CAP if piped else REPAIR_WAVE_CAP),
+                roomy=n_waves <= ROOMY_WAVES and pipeline not in (4, 5))
+
+
+def repair_walk(n_listed, shape):
+    """dict(W, replication, passes): how seqik_chunk_[pipe_]kernel<REPAIR> walks a work list of n_listed chunks; passes > 1 = some
+    lane takes a second entry (on the pipeline: with its ring counters carried over, `base` of pipe_run)."""
+    w = items_per_wave(n_listed, shape["repair_waves"])
+    return dict(W=w, replication=lane_replication(w), passes=-(-n_listed // (shape["repair_waves"] * w)))
+
+
+def serial_walk(n_serial, n_chains):
+    """dict(W, passes, roomy): seqik_chunk_pipe_kernel<SERIAL> over the serial list."""
+    groups = min(n_chains, PIPE_GROUP_CAP)
+    w = items_per_wave(n_serial, groups)
+    return dict(W=w, passes=-(-n_serial // (groups * w)), roomy=n_chains <= ROOMY_WAVES)
+
+
 class ChunkedChain:
     """One chain of a chunked call.  ``speculate()`` then ``settle()`` = one library call; a later ``settle(init=...,
     resume=True)`` = a ``chunk_resume`` call."""

@@ -493,8 +493,16 @@ def test_automatic_chunks_give_way_to_the_serial_walk_per_chain_when_speculation
     hiplib.solve_seq_device(d_pose.data_ptr(), 3, 6, 256, params, d_ang.data_ptr(), frame_chunk=-1, d_chunk_stats=d_stats.data_ptr())
     torch.cuda.synchronize()
     assert np.array_equal(d_ang.cpu().numpy(), auto["angles"]) and int(d_stats[8]) == 12
-    forced = hiplib.solve_seq(rec[:1], params, frame_chunk=8)
+    forced = hiplib.solve_seq(rec[:1], params, frame_chunk=8, want_chunk_flags=True)
     assert forced["chunk_stats"]["chunks"] == 6 * 32 and forced["chunk_stats"]["chains_walked_serially"] == 0
+    ms = [chunked_oracle(oracle, rec[0, i], *[z[f"{l}_{k}"] for k in ("seg", "bounds", "seeds")], 8, 8) for i, l in enumerate(legs)]
+    assert np.array_equal(forced["angles"][0], np.stack([m["angles"] for m in ms]))    # == the model: every result bit,
+    assert np.array_equal(forced["fk"][0], np.stack([m["fk"] for m in ms]))
+    assert np.array_equal(forced["chunk_flags"][0], np.stack([m["flags"] for m in ms]))  # the report and the statistics
+    want = np.sum([m["stats"] for m in ms], 0)[:10]
+    want[1:3] = (8, 8)
+    assert np.array_equal(np.array([forced["chunk_stats"][k] for k in hiplib.CHUNK_STATS_FIELDS]), want)
+    assert want[7] > 6 * 8 and want[3] > 0 and want[6] > 0                               # (many chunks fail: rounds and the sweep)
     # and on a real recording the automatic mode keeps its chunks
     lg = [str(l) for l in z["legs"]]
     ok = hiplib.solve_seq(np.stack([z[f"{l}_pose"] for l in lg])[None], _params(hiplib, z, lg), frame_chunk=-1)
