@@ -85,11 +85,14 @@ SEQIK_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, 
 //   1  fd_step without its distance logic where the limits are wide against the step (fd_limits_wide, fd_jacobian)
 //   2  sincos_cw's quadrant signs by XOR into the sign bit
 //   4  stage 1's end-effector evaluation with the identity prefix written out (residual_sc_stage1)
-// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all three.
+// and the two of round 8, work that a pass repeated for nothing:
+//   8  stages 2-4: the translation of the frame after the active links, which no angle enters, is formed once per frame
+//      (StageProblem::t_act) and the three evaluations of a pass form only the third column of the rotation (residual_sc)
+//  16  solve_tr_2x2 keeps the Gauss-Newton step and its norm from the trust-region test for the first phi / ratio
+// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all five.
 #ifndef SEQIK_PASS_CUTS
-#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 7 : 0)
-#endif
-// "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
+#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 31 : 0)
+#endif// "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
 SEQIK_HD bool wave_any(bool c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -864,11 +867,19 @@ SEQIK_HD void tr2_phi(double aa, double b, double cc, const double *r, double De
     ratio = div_(-(phi * p_norm), acc);
 }
 
-template <bool DEFICIENT>
+// KEEP_GN (bit 16 of SEQIK_PASS_CUTS): the full-rank branch tests the Gauss-Newton step pp = tr2_apply(a + 0.0, b, c + 0.0, r)
+// against Delta and, when it lies outside, starts the root search from phi / ratio at alpha = 0 -- tr2_phi(a + 0.0, b, c +
+// 0.0, r), which forms the same pp from the same operands and takes the same norm again.  The compiler merges the two
+// divisions but not the two square roots (the early return lies between them).  With KEEP_GN pp and its norm are kept and
+// only what tr2_phi does after them remains: tr2_apply(pp -> q), the dot product, phi and the division of ratio -- the same
+// operations on the same operands in the same order, so the same bits.  pp is overwritten by every later tr2_phi /
+// tr2_apply as before.  The rank-deficient paths and the root loop are untouched.
+template <bool DEFICIENT, bool KEEP_GN = (SEQIK_PASS_CUTS & 16) != 0>
 SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const double *f, double Delta,
                            double &alpha_io, double *p)
 {
     double a = diag_h[0], b = 0.0, c = diag_h[1], r[2], pp[2];
+    double gn_norm = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         a = fma_(Jh[k][0], Jh[k][0], a);
@@ -885,7 +896,8 @@ SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const do
         full_rank = lmin > 4.437342591868191e-31 * lmax;  // (3 eps)^2: s_min > eps * m * s_max
         if (full_rank) {
             tr2_apply(a + 0.0, b, c + 0.0, r, pp);
-            if (sqrt_(fma_(pp[1], pp[1], pp[0] * pp[0])) <= Delta) { SEQIK_BLK_COUNT(CNT_GN_STEP); p[0] = -pp[0]; p[1] = -pp[1]; alpha_io = 0.0; return; }
+            gn_norm = sqrt_(fma_(pp[1], pp[1], pp[0] * pp[0]));
+            if (gn_norm <= Delta) { SEQIK_BLK_COUNT(CNT_GN_STEP); p[0] = -pp[0]; p[1] = -pp[1]; alpha_io = 0.0; return; }
         }
     }
     const double inv_Delta = div_(1.0, Delta);
@@ -893,7 +905,15 @@ SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const do
     double alpha_lower = 0.0;
     double phi = 0.0, ratio = 0.0;
     if (full_rank) {
-        tr2_phi(a + 0.0, b, c + 0.0, r, Delta, pp, phi, ratio);
+        if constexpr (KEEP_GN) {  // the rest of tr2_phi behind pp and its norm
+            double q[2];
+            tr2_apply(a + 0.0, b, c + 0.0, pp, q);
+            const double acc = fma_(pp[1], q[1], pp[0] * q[0]);
+            phi = gn_norm - Delta;
+            ratio = div_(-(phi * gn_norm), acc);
+        } else {
+            tr2_phi(a + 0.0, b, c + 0.0, r, Delta, pp, phi, ratio);
+        }
         alpha_lower = -ratio;
     }
     double alpha = alpha_io;
@@ -1260,7 +1280,26 @@ struct StageProblem {
     Frame pre;          // product of the links in front of the active ones
     double target[3];
     double tz_a, tz_b, tz_last;
+    double t_act[3];    // stages 2-4: translation of the frame after the active links (stage_translation); set with pre
 };
+
+// Translation of the frame after the active links.  frame_mul_link forms out.t[i] = in.r[3i+2] * tz + in.t[i] from the
+// INCOMING frame, the first active link of stages 2 and 3 turns about Z, which leaves column 2 of the rotation as it is,
+// and stage 4 has one active link.  So the translation after the active links is
+//   stages 2, 3:  pre.r[3i+2] * tz_b + (pre.r[3i+2] * tz_a + pre.t[i])          stage 4:  pre.r[3i+2] * tz_a + pre.t[i]
+// -- no angle enters: a constant of the frame.  Written here with frame_mul_link's own operations in its order, it is
+// formed where pre is set (run_stage, new-solve block) and read by residual_sc<STAGE, true> and at the frame's end.
+template <int STAGE>
+SEQIK_HD void stage_translation(StageProblem<STAGE> &P)
+{
+    static_assert(STAGE >= 2, "stage 1's first active link turns about X");
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double t1 = P.pre.r[3 * i + 2] * P.tz_a + P.pre.t[i];
+        if constexpr (StageTraits<STAGE>::NA == 2) P.t_act[i] = P.pre.r[3 * i + 2] * P.tz_b + t1;
+        else P.t_act[i] = t1;
+    }
+}
 
 // Frame after the active links for given sin/cos pairs.
 template <int STAGE>
@@ -1321,10 +1360,44 @@ SEQIK_HD void residual_sc_stage1(double tz_last, const double *target, double sa
     }
 }
 
+// The same for STAGES 2-4 with the frame's translation taken from P.t_act (HOISTED; stage_translation above).  Beside it
+// the end effector needs only the third column of the rotation after the active links, which frame_mul_link forms as
+//   stages 2, 3 (Z then Y):  f1.r[3i] = fma(pre.r[3i+1], sa, pre.r[3i] * ca),  f1.r[3i+2] = pre.r[3i+2],
+//                            after.r[3i+2] = fma(f1.r[3i+2], cb, f1.r[3i] * sb)
+//   stage 4 (Y):             after.r[3i+2] = fma(pre.r[3i+2], ca, pre.r[3i] * sa)
+// and e_i = after.r[3i+2] * tz_last + after.t[i].  These are the general form's operations on its operands in its order --
+// only the six other entries of the rotation and the translation's two sums are not formed -- so f and pe carry its bits
+// for every input, zeros and their signs included; no case needs an argument of its own, unlike stage 1's closed form.
+// What the caller owes: P.t_act belongs to P.pre (run_stage sets both in one place).  HOISTED is a template argument, not
+// the build flag, so that code which fills a StageProblem by hand gets the general form unless it asks.
 template <int STAGE>
+SEQIK_HD void residual_sc_hoisted(const StageProblem<STAGE> &P, double sa, double ca, double sb, double cb, double *f,
+                                  double *pe)
+{
+    static_assert(STAGE >= 2, "stage 1 has its own closed form");
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double c2;
+        if constexpr (StageTraits<STAGE>::NA == 2) {
+            const double a0 = fma_(P.pre.r[3 * i + 1], sa, P.pre.r[3 * i] * ca);
+            c2 = fma_(P.pre.r[3 * i + 2], cb, a0 * sb);
+        } else {
+            c2 = fma_(P.pre.r[3 * i + 2], ca, P.pre.r[3 * i] * sa);
+        }
+        const double e = c2 * P.tz_last + P.t_act[i];
+        if (pe) pe[i] = e;
+        f[i] = e - P.target[i];
+    }
+}
+
+template <int STAGE, bool HOISTED = false>
 SEQIK_HD void residual_sc(const StageProblem<STAGE> &P, double sa, double ca, double sb, double cb, double *f,
                           double *pe = nullptr)
 {
+    if constexpr (HOISTED && STAGE >= 2) {
+        residual_sc_hoisted<STAGE>(P, sa, ca, sb, cb, f, pe);
+        return;
+    }
 #if SEQIK_PASS_CUTS & 4
     if constexpr (STAGE == 1) {
         residual_sc_stage1(P.tz_last, P.target, sa, ca, sb, cb, f, pe);
@@ -1335,19 +1408,19 @@ SEQIK_HD void residual_sc(const StageProblem<STAGE> &P, double sa, double ca, do
 }
 
 // End-effector residual at (xa, xb); also returns the sin/cos pairs.
-template <int STAGE>
+template <int STAGE, bool HOISTED = false>
 SEQIK_HD void eval_residual(const StageProblem<STAGE> &P, double xa, double xb, double *f,
                             double &sa, double &ca, double &sb, double &cb, double *pe = nullptr)
 {
     sincos_cw(xa, sa, ca);
     if constexpr (StageTraits<STAGE>::NA == 2) sincos_cw(xb, sb, cb);
     else { sb = 0.0; cb = 1.0; }
-    residual_sc<STAGE>(P, sa, ca, sb, cb, f, pe);
+    residual_sc<STAGE, HOISTED>(P, sa, ca, sb, cb, f, pe);
 }
 
 // 2-point finite-difference Jacobian of the active columns: J[k][j].  Column a perturbs
 // link a and reuses link b's sin/cos, column b the other way round.
-template <int STAGE>
+template <int STAGE, bool HOISTED = false>
 SEQIK_HD void fd_jacobian(const StageProblem<STAGE> &P, const double *x, const double *f0, const double *lb,
                           const double *ub, double sa, double ca, double sb, double cb, bool fd_general, double J[3][2])
 {
@@ -1376,7 +1449,7 @@ SEQIK_HD void fd_jacobian(const StageProblem<STAGE> &P, const double *x, const d
         double dx = x1 - x[0];
         double s1, c1, f1[3];
         sincos_cw(x1, s1, c1);
-        residual_sc<STAGE>(P, s1, c1, sb, cb, f1);
+        residual_sc<STAGE, HOISTED>(P, s1, c1, sb, cb, f1);
         double inv_dx = div_(1.0, dx);
 #pragma unroll
         for (int i = 0; i < 3; ++i) J[i][0] = (f1[i] - f0[i]) * inv_dx;
@@ -1387,7 +1460,7 @@ SEQIK_HD void fd_jacobian(const StageProblem<STAGE> &P, const double *x, const d
         double dx = x1 - x[1];
         double s1, c1, f1[3];
         sincos_cw(x1, s1, c1);
-        residual_sc<STAGE>(P, sa, ca, s1, c1, f1);
+        residual_sc<STAGE, HOISTED>(P, sa, ca, s1, c1, f1);
         double inv_dx = div_(1.0, dx);
 #pragma unroll
         for (int i = 0; i < 3; ++i) J[i][1] = (f1[i] - f0[i]) * inv_dx;
@@ -1439,7 +1512,7 @@ SEQIK_HD bool pair_is_odd()
 }
 
 // fd_jacobian with one column per lane of a pair (stages with two active joints)
-template <int STAGE>
+template <int STAGE, bool HOISTED = false>
 SEQIK_HD void fd_jacobian_pair(const StageProblem<STAGE> &P, const double *x, const double *f0, const double *lb,
                                const double *ub, double sa, double ca, double sb, double cb, bool odd, bool fd_general,
                                double J[3][2])
@@ -1462,7 +1535,7 @@ SEQIK_HD void fd_jacobian_pair(const StageProblem<STAGE> &P, const double *x, co
     double dx = x1 - xj;
     double s1, c1, f1[3];
     sincos_cw(x1, s1, c1);
-    residual_sc<STAGE>(P, odd ? sa : s1, odd ? ca : c1, odd ? s1 : sb, odd ? c1 : cb, f1);
+    residual_sc<STAGE, HOISTED>(P, odd ? sa : s1, odd ? ca : c1, odd ? s1 : sb, odd ? c1 : cb, f1);
     double inv_dx = div_(1.0, dx);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -1474,7 +1547,7 @@ SEQIK_HD void fd_jacobian_pair(const StageProblem<STAGE> &P, const double *x, co
 }
 
 // eval_residual with one sin / cos per lane of a pair
-template <int STAGE>
+template <int STAGE, bool HOISTED = false>
 SEQIK_HD void eval_residual_pair(const StageProblem<STAGE> &P, double xa, double xb, bool odd, double *f,
                                  double &sa, double &ca, double &sb, double &cb, double *pe = nullptr)
 {
@@ -1484,7 +1557,7 @@ SEQIK_HD void eval_residual_pair(const StageProblem<STAGE> &P, double xa, double
     const double s2 = pair_swap(s1), c2 = pair_swap(c1);
     sa = odd ? s2 : s1; ca = odd ? c2 : c1;
     sb = odd ? s1 : s2; cb = odd ? c1 : c2;
-    residual_sc<STAGE>(P, sa, ca, sb, cb, f, pe);
+    residual_sc<STAGE, HOISTED>(P, sa, ca, sb, cb, f, pe);
 }
 
 // ---------------------------------------------------------------------------
@@ -1660,6 +1733,8 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
     static_assert(STAGE < 4 || !HANDOFF, "stage 4 is the last one");
     using T = StageTraits<STAGE>;
     constexpr int NA = T::NA;
+    // bit 8 of SEQIK_PASS_CUTS: P.t_act is kept next to P.pre and the evaluations read it (residual_sc_hoisted)
+    constexpr bool HOIST = (SEQIK_PASS_CUTS & 8) != 0 && STAGE >= 2;
     constexpr int DOF0 = 2 * (STAGE - 1);  // angle columns written: DOF0 (and DOF0 + 1)
     const double ftol = 1e-8, xtol = 1e-8, gtol = 1e-8;
     const StageConst &sc = lc.st[STAGE - 1];
@@ -1674,6 +1749,7 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
     P.tz_a = sc.tz_a; P.tz_b = sc.tz_b; P.tz_last = sc.tz_last;
     frame_identity(P.pre);
     P.target[0] = P.target[1] = P.target[2] = 0.0;
+    P.t_act[0] = P.t_act[1] = P.t_act[2] = 0.0;
 
     // x carries the solution from frame to frame: it is the warm start of the next solve
     double x[2] = {sc.seed[0], (NA == 2) ? sc.seed[1] : 0.0}, f[3] = {0.0, 0.0, 0.0};
@@ -1786,6 +1862,8 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
 #pragma unroll
                     for (int i = 0; i < 3; ++i) P.pre.t[i] = w[9 + i];
                 }
+                // whichever way pre came: the frame's constant beside it (the one place where pre is assigned)
+                if constexpr (HOIST) stage_translation<STAGE>(P);
             }
             if (lc.aff.enabled) {
                 // fused AlignPose.align_leg, then target = aligned key point - aligned origin
@@ -1815,7 +1893,7 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 SEQIK_BLK_COUNT(CNT_START_EVAL);
                 x[0] = strictly_feasible_thr(x[0], lb[0], ub[0], sc.thr_lb[0], sc.thr_ub[0]);
                 if constexpr (NA == 2) x[1] = strictly_feasible_thr(x[1], lb[1], ub[1], sc.thr_lb[1], sc.thr_ub[1]);
-                eval_residual<STAGE>(P, x[0], x[1], f, sa, ca, sb, cb, (STAGE == 1) ? pe : nullptr);
+                eval_residual<STAGE, HOIST>(P, x[0], x[1], f, sa, ca, sb, cb, (STAGE == 1) ? pe : nullptr);
                 have_pe = true;  // (stages 2-4 use the flag for "sa .. cb belong to x")
             } else {
                 // (x is a result of this solver here: inside its limits)
@@ -1835,13 +1913,13 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 if constexpr (STAGE == 1) {
                     if (moved0 || moved1) {
                         SEQIK_BLK_COUNT(CNT_START_EVAL);
-                        residual_sc<STAGE>(P, sa, ca, sb, cb, f, pe);
+                        residual_sc<STAGE, HOIST>(P, sa, ca, sb, cb, f, pe);
                     } else {
 #pragma unroll
                         for (int i = 0; i < 3; ++i) f[i] = pe[i] - P.target[i];
                     }
                 } else {
-                    residual_sc<STAGE>(P, sa, ca, sb, cb, f);  // the prefix frame is another one in every frame
+                    residual_sc<STAGE, HOIST>(P, sa, ca, sb, cb, f);  // the prefix frame is another one in every frame
                 }
             }
 #else
@@ -1853,12 +1931,12 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
 #pragma unroll
                         for (int i = 0; i < 3; ++i) f[i] = pe[i] - P.target[i];
                     } else {
-                        residual_sc<STAGE>(P, sa, ca, sb, cb, f);
+                        residual_sc<STAGE, HOIST>(P, sa, ca, sb, cb, f);
                     }
                 } else {
                     x[0] = xs0;
                     if constexpr (NA == 2) x[1] = xs1;
-                    eval_residual<STAGE>(P, x[0], x[1], f, sa, ca, sb, cb, (STAGE == 1) ? pe : nullptr);
+                    eval_residual<STAGE, HOIST>(P, x[0], x[1], f, sa, ca, sb, cb, (STAGE == 1) ? pe : nullptr);
                     have_pe = true;
                 }
             }
@@ -1884,8 +1962,8 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
             bool derive = true;
             if constexpr (LAT) derive = wave_any(!jac_valid);   // wave-uniform: nobody moved since the last pass
             if (derive) {
-            if constexpr (PAIRED) fd_jacobian_pair<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, odd, fd_general, J);
-            else fd_jacobian<STAGE>(P, x, f, lb, ub, sa, ca, sb, cb, fd_general, J);
+            if constexpr (PAIRED) fd_jacobian_pair<STAGE, HOIST>(P, x, f, lb, ub, sa, ca, sb, cb, odd, fd_general, J);
+            else fd_jacobian<STAGE, HOIST>(P, x, f, lb, ub, sa, ca, sb, cb, fd_general, J);
             SEQIK_BLK_END_OF(BLK_FD_JACOBIAN);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -1977,9 +2055,9 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 if constexpr (NA == 2) x_new[1] = strictly_feasible(x[1] + step[1], lb[1], ub[1], 0.0);
 #endif
                 if constexpr (PAIRED)
-                    eval_residual_pair<STAGE>(P, x_new[0], x_new[1], odd, f_new, sa_n, ca_n, sb_n, cb_n, (STAGE == 1) ? pe_n : nullptr);
+                    eval_residual_pair<STAGE, HOIST>(P, x_new[0], x_new[1], odd, f_new, sa_n, ca_n, sb_n, cb_n, (STAGE == 1) ? pe_n : nullptr);
                 else
-                    eval_residual<STAGE>(P, x_new[0], x_new[1], f_new, sa_n, ca_n, sb_n, cb_n, (STAGE == 1) ? pe_n : nullptr);
+                    eval_residual<STAGE, HOIST>(P, x_new[0], x_new[1], f_new, sa_n, ca_n, sb_n, cb_n, (STAGE == 1) ? pe_n : nullptr);
                 nfev += 1;
                 SEQIK_BLK_END_OF(BLK_TRIAL_EVAL);
                 double step_h_norm = norm2v<NA>(step_h);
@@ -2052,6 +2130,9 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
             if constexpr ((WANT_FK && STAGE >= 2) || HANDOFF) {
                 Frame after;  // frame after the active links at the solution
                 frame_after_active<STAGE>(P, sa, ca, sb, cb, after);
+                // after.t is the frame's constant (stage_translation: the same operations, the same bits); taking it from
+                // P.t_act ends the life of pre.t at the frame's start wherever FROM_ANGLES does not read it below
+                if constexpr (HOIST) { after.t[0] = P.t_act[0]; after.t[1] = P.t_act[1]; after.t[2] = P.t_act[2]; }
                 if constexpr (HANDOFF && PIPED) {
                     const int fi = io.pipe.base + (int)(t - t_first);
                     double *w = io.pipe.ring_out + (fi % PIPE_DEPTH) * 12 * io.pipe.lane_stride;
