@@ -27,7 +27,8 @@
  *   (generic): the solvers' own.
  *
  * Only runs of all four stages on the dense layout are supported; frame sharding (frame_lead, chunk_resume,
- * chunk_states) and the per-chunk report (chunk_flags) are not.  SeqikOptions.chunk_stats (HOST memory here) reports the
+ * chunk_states) and the per-chunk report (chunk_flags) are not; the slab-streaming pipeline has skip mode through the
+ * entry points of seqik_stream_gaps.h.  SeqikOptions.chunk_stats (HOST memory here) reports the
  * chunks of the compacted recording.  Return codes and seqik_last_error() as in seqik.h.  SEQIK_ERR_BAD_ARG: null
  * buffers, n_legs outside 1..8, a negative size, n_frames >= 2^31, unknown flags, a stage subset, unsupported options.
  * A call with no leg-frames returns SEQIK_OK without a launch.

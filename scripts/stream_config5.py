@@ -10,6 +10,12 @@ distinct synthetic data are generated; the stream cycles through them (the kerne
 timed region is first submit -> last result in host memory, i.e. PCIe-inclusive (H2D 120 B, D2H 56 B
 + 216 B FK per leg-frame).  One process per GPU does the same on its share of the slabs (no collective);
 prints one JSON line.
+
+    python scripts/stream_config5.py --missing skip --gap-fraction 0.05
+
+streams the same sequences in skip mode (include/seqik_stream_gaps.h; dense layout, which --dense selects for the plain
+stream too): --gap-fraction of the leg-frames, drawn from a fixed seed, get a NaN in a key point the solver reads and
+come back NaN.  The line then also holds the rate of the non-missing leg-frames and the slot memory skip mode adds.
 """
 import argparse
 import json
@@ -226,11 +232,23 @@ def main():
     ap.add_argument("--check", action="store_true", help="compare one slab with a direct solve on aligned data")
     ap.add_argument("--gpu-stats", action="store_true",
                     help="also time pass 1: AlignPose's whole-recording statistics from the RAW slabs on the GPU")
+    ap.add_argument("--missing", choices=_lib.MISSING_MODES, default="raise",
+                    help="skip: the stream runs in skip mode (dense layout); synthetic sequences only")
+    ap.add_argument("--gap-fraction", type=float, default=0.0,
+                    help="share of the leg-frames that get a NaN in a key point the solver reads (needs --missing skip)")
+    ap.add_argument("--dense", action="store_true",
+                    help="dense reference-shaped slabs instead of the planar layout (implied by --missing skip)")
     ap.add_argument("--one-recording", action="store_true",
                     help="config 5 read literally: ONE recording of --frames frames x 6 legs streamed in time slabs "
                          "(carried warm start), every slab cut into frame chunks on the device; real locomotion poses "
                          "(the df3d fixture repeated) instead of the synthetic sequences")
     args = ap.parse_args()
+    if args.gap_fraction and args.missing != "skip":
+        raise SystemExit("--gap-fraction needs --missing skip (the plain stream checks nothing per frame)")
+    if not 0.0 <= args.gap_fraction <= 1.0:
+        raise SystemExit("--gap-fraction must lie in 0..1")
+    if args.one_recording and (args.missing == "skip" or args.dense):
+        raise SystemExit("--missing skip and --dense apply to the synthetic sequences (not to --one-recording)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         if not args.one_recording:
             raise SystemExit("--gpus N > 1 needs --one-recording (independent sequences need no coordination: run one "
@@ -258,7 +276,13 @@ def synthetic_sequences(args):
     fixed = rng.normal(0.0, 2.0, (L, 3))
     affs = [_lib.make_affine(fixed[i], scales[i], data.TEMPLATE_NMF_LOCOMOTION[f"{l}_Coxa"]) for i, l in enumerate(legs)]
     want_fk = not args.no_fk
-    layout = _lib.planar_layout(T)
+    # skip mode (dense layout only): gaps are NaN in rows 1-4, the rows the solver reads under the fused alignment
+    missing = getattr(args, "missing", "raise")
+    gap_fraction = float(getattr(args, "gap_fraction", 0.0))
+    dense = bool(getattr(args, "dense", False)) or missing == "skip"
+    layout = None if dense else _lib.planar_layout(T)
+    gap_rng = np.random.default_rng(2025)
+    n_gaps = []
 
     def alloc(shape):
         return PinnedArray(shape) if not args.pageable else type("A", (), {"array": np.empty(shape), "free": lambda s: None})()
@@ -275,16 +299,23 @@ def synthetic_sequences(args):
         for i, l in enumerate(legs):
             tc = data.TEMPLATE_NMF_LOCOMOTION[f"{l}_Coxa"]
             raw[:, i] = (al[:, i] - tc) / scales[i] + fixed[i]
+        if gap_fraction > 0.0:
+            s_i, l_i, t_i = np.nonzero(gap_rng.random((S, L, T)) < gap_fraction)
+            raw[s_i, l_i, t_i, gap_rng.integers(1, 5, s_i.size), gap_rng.integers(0, 3, s_i.size)] = np.nan
+            n_gaps.append(int(s_i.size))
+        else:
+            n_gaps.append(0)
         if u == 0 and args.check:
             raw0 = raw[:256].copy()
-        p = alloc((S, L, 5, T, 3))
-        p.array[...] = raw.transpose(0, 1, 3, 2, 4)
+        p = alloc((S, L, T, 5, 3) if dense else (S, L, 5, T, 3))
+        p.array[...] = raw if dense else raw.transpose(0, 1, 3, 2, 4)
         slabs.append(p)
         del al, raw
-    outs = [(alloc((S, L, 7, T)), alloc((S, L, T, 9, 3)) if want_fk else None) for _ in range(args.slots)]
+    outs = [(alloc((S, L, T, 7) if dense else (S, L, 7, T)), alloc((S, L, T, 9, 3)) if want_fk else None)
+            for _ in range(args.slots)]
     t_gen = time.perf_counter() - t_gen
 
-    with SeqikStream(params, S, T, affine=affs, layout=layout, want_fk=want_fk, n_slots=args.slots) as st:
+    with SeqikStream(params, S, T, affine=affs, layout=layout, want_fk=want_fk, n_slots=args.slots, missing=missing) as st:
         for k in range(min(3, n_slabs)):  # warm-up: allocator pools, first-launch costs
             a, f = outs[k % args.slots]
             st.submit(slabs[k % args.unique].array, a.array, f.array if f else None)
@@ -295,20 +326,27 @@ def synthetic_sequences(args):
             st.submit(slabs[k % args.unique].array, a.array, f.array if f else None)
         st.wait()
         dt = time.perf_counter() - t0
+        # the slab that came back last: exactly its gap leg-frames are NaN
+        last_out = outs[(n_slabs - 1) % args.slots][0].array
+        nan_back = int(np.isnan(last_out[..., 0] if dense else last_out[:, :, 0]).sum())
         check = None
         if args.check:
             # the slab that ended up in outs[(n_slabs - 1) % slots] is slab (n_slabs - 1) % unique; re-run slab 0
             a, f = outs[0]
             st.submit(slabs[0].array, a.array, f.array if f else None)
             st.wait()
-            got = a.array[:256].transpose(0, 1, 3, 2)
-            direct = _lib.solve_seq(raw0, params, want_fk=want_fk, affine=affs)  # same RAW data, one blocking call
+            got = a.array[:256] if dense else a.array[:256].transpose(0, 1, 3, 2)
+            direct = _lib.solve_seq(raw0, params, want_fk=want_fk, affine=affs, missing=missing)  # same RAW data, one blocking call
             ref = _lib.solve_seq(aligned0, params, want_fk=want_fk)              # the data before the made-up camera
             # frame: (aligned - tc) / s + f followed by the fused (raw - f) * s + tc is the identity only up to
             # rounding, and on i.i.d. targets an ulp in the input can flip the reference's iteration path
+            # (with gaps a chain's frames behind a gap start elsewhere than in the gap-free solve, and i.i.d. targets have
+            # several solutions: the comparison with the pre-aligned solve is made on each chain's frames in front of its
+            # first gap alone; the bitwise check covers everything)
             err = np.abs(got - ref["angles"]).max(-1)
-            check = {"streamed_equals_direct_fused_solve_bitwise": bool(np.array_equal(got, direct["angles"])) and
-                     (not want_fk or bool(np.array_equal(f.array[:256], direct["fk"]))),
+            err = err[np.logical_and.accumulate(np.isfinite(err), axis=-1)]
+            check = {"streamed_equals_direct_fused_solve_bitwise": bool(np.array_equal(got, direct["angles"], equal_nan=True)) and
+                     (not want_fk or bool(np.array_equal(f.array[:256], direct["fk"], equal_nan=True))),
                      "median_abs_diff_vs_solve_on_prealigned": float(np.median(err)),
                      "leg_frames_gt_1e-4_vs_prealigned": int((err > 1e-4).sum()),
                      "leg_frames_checked": int(err.size)}
@@ -335,6 +373,15 @@ def synthetic_sequences(args):
 
     units = n_slabs * S * L * T
     bytes_per = 120 + 56 + (216 if want_fk else 0)
+    gaps_total = sum(n_gaps[k % args.unique] for k in range(n_slabs))
+    skip_info = {"missing": missing, "layout": "dense" if dense else "planar", "gap_fraction": gap_fraction,
+                 "missing_leg_frames": gaps_total, "non_missing_share": 1.0 - gaps_total / units,
+                 "non_missing_leg_frames_per_s": (units - gaps_total) / dt,
+                 "nan_leg_frames_in_last_slab": nan_back, "gap_leg_frames_in_last_slab": n_gaps[(n_slabs - 1) % args.unique],
+                 # per slot: compacted pose 120 B, frame map 4 B, compact angles 56 B (+ compact FK 216 B) per leg-frame,
+                 # n_valid 4 B per chain
+                 "added_slot_bytes": (args.slots * (S * L * T * (180 + (216 if want_fk else 0)) + S * L * 4)
+                                      if missing == "skip" else 0)}
     out = {"metric": "leg-IK solves/s, streamed from host memory (PCIe-inclusive)", "value": units / dt,
            "unit": "leg-frame solves/s", "n_gpus": 1, "seconds": dt, "leg_frames": units,
            "frames_total": n_slabs * S * T, "legs": L, "slabs": n_slabs, "slab_frames": S * T,
@@ -342,7 +389,7 @@ def synthetic_sequences(args):
            "fused_alignment": True, "outputs": "7 angles" + (" + 9x3 FK" if want_fk else ""),
            "pcie_GBps_total": units * bytes_per / dt / 1e9, "h2d_GBps": units * 120 / dt / 1e9,
            "d2h_GBps": units * (bytes_per - 120) / dt / 1e9, "datagen_seconds": t_gen, "check": check,
-           "alignment_statistics_pass": stats}
+           "alignment_statistics_pass": stats, "skip_mode": skip_info}
     for p in slabs:
         p.free()
     for a, f in outs:

@@ -6,8 +6,13 @@
 //   gaps_pad_value                   what a padding slot holds: the chain's last non-missing record, or the filler
 //   gaps_expand_value                what an output element of an original frame holds after the solve
 // gaps_compact_chain / gaps_expand_chain apply them to one chain frame by frame: the host restatement of the contract.
+// Streams in skip mode (include/seqik_stream_gaps.h, seqik_stream.hip) add two rules about the state a chain carries
+// from one time slab to the next:
+//   gaps_carry_slot                  which compact slot of a solved slab is the chain's new state, or none
+//   stream_seed_state                the state that stands for "no init_angles": every stage's start values
 #pragma once
 #include "seqik_core.hpp"
+#include "seqik_generic.hpp"
 #include "../../include/seqik_gaps.h"
 
 namespace seqik {
@@ -67,6 +72,33 @@ template <typename T>
 SEQIK_HD T gaps_expand_value(const T *compact, int32_t m, int width, int k, T fill)
 {
     return m >= 0 ? compact[(int64_t)m * width + k] : fill;
+}
+
+// Carried streams: the compact slot whose angles are the chain's state after a slab with n_valid non-missing frames --
+// the last non-missing frame (the slots behind it are padding, re-solves of that frame from its own solution) -- or -1:
+// the slab had no such frame and the chain keeps the state it came with.
+SEQIK_HD int64_t gaps_carry_slot(int64_t n_valid) { return n_valid > 0 ? n_valid - 1 : -1; }
+
+// One chain's carry on the host: cangles [N][7] of the solved compact slab -> state [7] (left alone without a valid frame).
+inline void gaps_carry_chain(const double *cangles, int64_t n_valid, double *state)
+{
+    const int64_t slot = gaps_carry_slot(n_valid);
+    if (slot < 0) return;
+    for (int d = 0; d < 7; ++d) state[d] = cangles[slot * 7 + d];
+}
+
+// The init_angles [7] (DOF order of the ABI) that are bit-equivalent to none.  A solver kernel reads init only where it
+// would otherwise read a seed, and reads it raw, as it reads the seed:
+//   sequential chain  stage s starts its active links from init[first DOF of the stage ..] in place of
+//                     seeds[kSeedOffset[s] + kFirstActive[s] + j] (seqik_consts.hpp): seeds 1, 2 | 7, 8 | 15, 16 | 25
+//   generic chain     link i (0..6) starts from init[generic_link_dof(i)] in place of seeds[19 + i]
+inline void stream_seed_state(const SeqikLegParams &lp, bool generic, double *state)
+{
+    static const int seq_seed[7] = {1, 2, 7, 8, 15, 16, 25};
+    for (int i = 0; i < 7; ++i) {
+        if (generic) state[generic_link_dof(i)] = lp.seeds[19 + i];
+        else state[i] = lp.seeds[seq_seed[i]];
+    }
 }
 
 // One chain on the host: pose [N][15] -> cpose [N][15], map [N]; returns n_valid.

@@ -238,6 +238,15 @@ EXTENSION_SIGNATURES = {
         ("seqik_resample_der_device", _int, _vp, _i64, _i64, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp)),
 }
 
+# The same for skip mode on streams (include/seqik_stream_gaps.h): a third table, so that the two above stay the sets
+# their tests pin.
+STREAM_GAPS_SIGNATURES = {
+    "seqik_stream_gaps.h": (
+        ("seqik_stream_open_skip", _int, _vpp, _i32, _legs, _aff, _i64, _i64, _lay, _i32, _i32, _i32, _i32, _opt),
+        ("seqik_stream_seed_state", _int, _legs, _i32, _i32, _dp),
+        ("seqik_stream_get_carry", _int, _vp, _dp, _i64)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -340,7 +349,8 @@ def load():
         if L.seqik_abi_version() != ABI_VERSION:
             raise SeqikLibraryError(f"{LIB_PATH} has ABI {L.seqik_abi_version()}, this package needs {ABI_VERSION}: "
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
-        for signatures in list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()):
+        for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
+                           list(STREAM_GAPS_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -585,6 +595,20 @@ def solve_seq_gaps_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_cpo
                      affine=affine, d_init=c_ptrs[5], **solve_options)
     gaps_expand_device(d_map, n_seq, n_legs, n_frames, d_cangles, d_angles, d_cfk, d_fk, d_cstatus, d_status, d_cnfev,
                        d_nfev, kind="seq", stream=s)
+
+
+#: entry points of include/seqik_stream_gaps.h (skip mode on streams), additive to ABI 7
+STREAM_GAPS_EXPORTED_SYMBOLS = [sig[0] for sig in STREAM_GAPS_SIGNATURES["seqik_stream_gaps.h"]]
+
+
+def stream_seed_state(legs, generic=False) -> np.ndarray:
+    """``seqik_stream_seed_state``: (L, 7) joint angles in ``DOFS`` order, the ``init_angles`` that are bit-equivalent to
+    none -- the start values of every stage's active joints (``seeds[[1, 2, 7, 8, 15, 16, 25]]``), for the generic chain
+    those of its seven joints.  What a carried skip stream starts from (``SeqikStream.get_carry``).  No GPU needed."""
+    n = len(legs)
+    state = np.zeros((n, 7))
+    _call("seqik_stream_seed_state", (SeqikLegParams * n)(*legs), n, 1 if generic else 0, _data(state))
+    return state
 
 
 #: entry points of include/seqik_resample.h (PCHIP resampling of joint angles), kept apart from the ABI-7 set of seqik.h

@@ -9,6 +9,11 @@ streams.  With ``carry=True`` consecutive slabs are consecutive pieces in time o
 recordings (frame 0 of a slab is warm-started from the last frame of the slab before, on the
 device), so the result equals one call over the concatenated recording bit for bit.
 
+``missing="skip"`` (include/seqik_stream_gaps.h) is skip mode for streams: every slab is compacted, solved and expanded
+on the device, leg-frames with a non-finite key point the solver reads come back NaN, and a carried stream hands on each
+chain's state from its last non-missing frame -- the result equals ``_lib.solve_seq(..., missing="skip")`` of the
+unsplit recording bit for bit.
+
 All work is done by ``libseqik_hip.so``; this module only owns buffers and the handle.
 """
 import ctypes
@@ -54,16 +59,21 @@ class SeqikStream:
     legs: list of ``SeqikLegParams``; affine: optional list of ``SeqikAffine`` (pose slabs are then RAW
     key points, ``AlignPose.align_leg`` runs in the kernel prologue); layout: optional ``SeqikLayout`` of
     the pose / angle slabs (``_lib.planar_layout(n_frames)``), default dense reference-shaped arrays.
+    missing: ``"raise"`` (default; nothing is checked per frame, see ``solve_streamed``) or ``"skip"`` -- skip mode
+    (``seqik_stream_open_skip``; dense layout only): missing leg-frames come back as NaN angles and NaN FK.
     """
 
     def __init__(self, legs: List[_lib.SeqikLegParams], slab_seq: int, n_frames: int, affine=None, layout=None,
                  want_fk: bool = True, n_slots: int = 3, carry: bool = False, generic: bool = False,
                  device: int = -1, block_size: int = 0, frame_chunk: int = 0, frame_halo: int = 0,
-                 chunk_tol: float = 0.0):
+                 chunk_tol: float = 0.0, missing: str = "raise"):
+        self.skip = _lib.check_missing_mode(missing)
+        if self.skip and layout is not None:
+            raise ValueError("missing='skip' supports the dense layout only (layout must be None)")
         self._lib = _lib.load()   # held for close(), which may run while the interpreter shuts down
         self.n_legs = len(legs)
         self.slab_seq, self.n_frames = int(slab_seq), int(n_frames)
-        self.want_fk, self.layout = bool(want_fk), layout
+        self.want_fk, self.layout, self.carry = bool(want_fk), layout, bool(carry)
         self._handle = ctypes.c_void_p()
         # frame chunks inside every slab (SeqikOptions.frame_chunk): with carry=True and ONE long recording per slab
         # (slab_seq = 1) this is BASELINE config 5 read literally -- a 10 M-frame recording streamed in time slabs, each
@@ -71,7 +81,7 @@ class SeqikStream:
         opt = _lib.SeqikOptions(device=device, block_size=block_size, frame_chunk=int(frame_chunk),
                                 frame_halo=int(frame_halo), chunk_tol=float(chunk_tol))
         try:
-            _lib._call("seqik_stream_open", ctypes.byref(self._handle), self.n_legs,
+            _lib._call("seqik_stream_open_skip" if self.skip else "seqik_stream_open", ctypes.byref(self._handle), self.n_legs,
                        (_lib.SeqikLegParams * self.n_legs)(*legs), _lib._affine_array(affine, self.n_legs), self.slab_seq,
                        self.n_frames, ctypes.byref(layout) if layout is not None else None, 1 if want_fk else 0,
                        int(n_slots), 1 if carry else 0, 1 if generic else 0, ctypes.byref(opt))
@@ -135,6 +145,15 @@ class SeqikStream:
                 raise ValueError(f"state must have shape (n_seq, {self.n_legs}, 7)")
             _lib._call("seqik_stream_set_carry", self._handle, arr.ctypes.data, arr.shape[0], 0)
 
+    def get_carry(self, n_seq=None) -> np.ndarray:
+        """Carried streams: waits for the slabs submitted so far and returns the state (n_seq, n_legs, 7) the next slab
+        would start from (``n_seq`` defaults to the slab size).  In skip mode that is every chain's angles at its last
+        non-missing frame so far, or the seed state (``_lib.stream_seed_state``) when it has had none."""
+        n_seq = self.slab_seq if n_seq is None else int(n_seq)
+        state = np.zeros((max(n_seq, 0), self.n_legs, 7))
+        _lib._call("seqik_stream_get_carry", self._handle, _lib._data(state), n_seq)
+        return state
+
     def close(self):
         if self._handle:
             self._lib.seqik_stream_close(self._handle)
@@ -155,16 +174,18 @@ class SeqikStream:
 
 
 def solve_streamed(pose: np.ndarray, legs, slab_seq: int, affine=None, want_fk: bool = True, n_slots: int = 3,
-                   device: int = -1):
+                   device: int = -1, missing: str = "raise"):
     """Convenience: ``pose (S, L, N, 5, 3)`` pushed through a stream in slabs of ``slab_seq`` sequences.
-    Returns ``dict(angles (S, L, N, 7), fk (S, L, N, 9, 3) or None)`` -- equal to ``_lib.solve_seq`` bit for bit."""
+    Returns ``dict(angles (S, L, N, 7), fk (S, L, N, 9, 3) or None)`` -- equal to ``_lib.solve_seq`` bit for bit
+    (``missing="skip"``: to ``_lib.solve_seq(..., missing="skip")``; the default refuses non-finite key points)."""
     pose = np.ascontiguousarray(pose, dtype=np.float64)
-    _lib._check_finite(pose)
+    if not _lib.check_missing_mode(missing):
+        _lib._check_finite(pose)
     S, L, N = pose.shape[:3]
     angles = np.zeros((S, L, N, 7))
     fk = np.full((S, L, N, 9, 3), np.nan) if want_fk else None
     with SeqikStream(legs, min(slab_seq, max(S, 1)), N, affine=affine, want_fk=want_fk, n_slots=n_slots,
-                     device=device) as st:
+                     device=device, missing=missing) as st:
         for s0 in range(0, S, slab_seq):
             s1 = min(S, s0 + slab_seq)
             st.submit(pose[s0:s1], angles[s0:s1], fk[s0:s1] if want_fk else None)
@@ -173,21 +194,26 @@ def solve_streamed(pose: np.ndarray, legs, slab_seq: int, affine=None, want_fk: 
 
 
 def solve_streamed_in_time(pose: np.ndarray, legs, slab_frames: int, affine=None, want_fk: bool = True,
-                           n_slots: int = 3, device: int = -1, frame_chunk: int = 0):
+                           n_slots: int = 3, device: int = -1, frame_chunk: int = 0, missing: str = "raise"):
     """``pose (S, L, N, 5, 3)`` pushed through a carried stream in slabs of ``slab_frames`` frames (the S
     recordings advance in lock step).  Equal to ``_lib.solve_seq(pose, ...)`` bit for bit with ``frame_chunk = 0``;
     with frame chunks (-1 = automatic) every slab is cut into concurrently solved chunks on the device (a few long
-    recordings then fill the GPU) and the result equals the serial walk to about the chunk tolerance."""
+    recordings then fill the GPU) and the result equals the serial walk to about the chunk tolerance.
+    ``missing="skip"``: skip mode, equal to ``_lib.solve_seq(pose, ..., missing="skip")`` in the same way (every chain
+    continues from its last non-missing frame, across slabs as well); the default refuses non-finite key points."""
     pose = np.ascontiguousarray(pose, dtype=np.float64)
-    _lib._check_finite(pose)
+    skip = _lib.check_missing_mode(missing)
+    if not skip:
+        _lib._check_finite(pose)
     S, L, N = pose.shape[:3]
     angles = np.zeros((S, L, N, 7))
     fk = np.full((S, L, N, 9, 3), np.nan) if want_fk else None
     T = min(slab_frames, N)
     n_full = N // T if T else 0
+    state = None   # skip mode: what the shorter last piece continues from
     if n_full:
         with SeqikStream(legs, S, T, affine=affine, want_fk=want_fk, n_slots=n_slots, carry=True, device=device,
-                         frame_chunk=frame_chunk) as st:
+                         frame_chunk=frame_chunk, missing=missing) as st:
             bufs = []
             for k in range(n_full):
                 sl = slice(k * T, (k + 1) * T)
@@ -196,15 +222,18 @@ def solve_streamed_in_time(pose: np.ndarray, legs, slab_frames: int, affine=None
                 st.submit(np.ascontiguousarray(pose[:, :, sl]), a, f)
                 bufs.append((sl, a, f))
             st.wait()
+            if skip and n_full * T < N:
+                state = st.get_carry()   # (the last streamed frame may be missing: the angles do not show the state)
         for sl, a, f in bufs:
             angles[:, :, sl] = a
             if want_fk:
                 fk[:, :, sl] = f
     t0 = n_full * T
     if t0 < N:  # a shorter last piece: one direct call, continued from the last streamed frame
-        rest = _lib.solve_seq(pose[:, :, t0:], legs, want_fk=want_fk, affine=affine, device=device,
-                              init_angles=np.ascontiguousarray(angles[:, :, t0 - 1]) if t0 else None,
-                              frame_chunk=frame_chunk)
+        if not skip:
+            state = np.ascontiguousarray(angles[:, :, t0 - 1]) if t0 else None
+        rest = _lib.solve_seq(pose[:, :, t0:], legs, want_fk=want_fk, affine=affine, device=device, init_angles=state,
+                              frame_chunk=frame_chunk, missing=missing)
         angles[:, :, t0:] = rest["angles"]
         if want_fk:
             fk[:, :, t0:] = rest["fk"]
