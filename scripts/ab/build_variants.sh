@@ -1,14 +1,30 @@
 #!/bin/bash
 # Builds library variants for A/B measurements into build_ab/ (git-ignored; they travel to the GPU box with the snapshot):
 #   usage: bash scripts/ab/build_variants.sh name1:"-DFLAG=1 ..." name2:"..."      -> build_ab/libseqik_<name>.so
+# The flags reach the solver unit (seqik_hip.hip), the one the A/B switches of seqik_core.hpp act on; the other units of the
+# library are compiled once, with the library's own flags, and linked into every variant.  The solver unit's assembly with
+# the compiler's per-kernel metadata (registers, scratch, occupancy) is kept as build_ab/<name>.s.
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
-mkdir -p $ROOT/build_ab
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+FLAGS="--offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17"
+mkdir -p $ROOT/build_ab/obj
 cd $ROOT/sequential-inverse-kinematics_amd/csrc
+others=()
+for src in seqik_*.hip; do
+  [ $src == seqik_hip.hip ] && continue
+  others+=($ROOT/build_ab/obj/${src%.hip}.o)
+  $HIPCC $FLAGS -c -o $ROOT/build_ab/obj/${src%.hip}.o $src &
+done
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off $flags -fPIC -shared -std=c++17 -o $ROOT/build_ab/libseqik_$name.so \
-      seqik_hip.hip seqik_head.hip seqik_stream.hip seqik_align.hip seqik_peer.hip &
+  mkdir -p $ROOT/build_ab/obj/$name
+  $HIPCC $FLAGS $flags -c -save-temps=obj -o $ROOT/build_ab/obj/$name/seqik_hip.o seqik_hip.hip &
 done
 wait
+for spec in "$@"; do
+  name=${spec%%:*}
+  $HIPCC --offload-arch=gfx950 -fPIC -shared -o $ROOT/build_ab/libseqik_$name.so $ROOT/build_ab/obj/$name/seqik_hip.o "${others[@]}"
+  cp $ROOT/build_ab/obj/$name/seqik_hip-hip-amdgcn-amd-amdhsa-gfx950.s $ROOT/build_ab/$name.s
+done
 ls -la $ROOT/build_ab

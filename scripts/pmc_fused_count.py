@@ -2,11 +2,15 @@
 """Wave-level VALU instructions of ONE launch of seqik_fused_kernel<true> on the benchmark batch (15 625 sequences x 6 legs x
 64 frames, the seeds of bench.py), iid and smooth -- the deterministic count of EXPERIMENTS.md 16.1.
 
-    rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d OUT -- python scripts/pmc_fused_count.py run [CACHE_DIR]
+    rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_TRANS_F64 --output-format csv -d OUT -- python scripts/pmc_fused_count.py run [CACHE_DIR]
     python scripts/pmc_fused_count.py read OUT [OUT2 ...]        # -> one JSON line per directory
 
 `run` makes one launch per variant, iid first (counters-only profiler run of its own: no tracing beside it); `read` takes
-the fused kernel's dispatches of such a run in dispatch order.  CACHE_DIR keeps the generated key points (0.75 GB per
+the fused kernel's dispatches of such a run in dispatch order.  Where the run also collected SQ_INSTS_VALU_TRANS_F64 (the
+v_rcp_f64 / v_rsq_f64 / v_sqrt_f64 seeds of every division and square root), `read` adds the WEIGHTED count
+W = VALU + 2.8 x TRANS_F64: a transcendental issues in 16.2 cycles where every other FP64 instruction takes 4.2-4.3
+(profiles/r03_valu_issue_costs.json, 3 waves per SIMD), so it stands for 16.2 / 4.25 = 3.8 ordinary instructions, 2.8 more
+than the plain count gives it.  CACHE_DIR keeps the generated key points (0.75 GB per
 variant) for the next build's run.  SEQIK_LIB selects the library (A/B builds).  The count is a
 property of the code and the data: it does not vary from run to run, unlike a time."""
 import csv
@@ -19,6 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "sequential-inverse-kinematics_amd"))
 sys.path.insert(0, ROOT)
 VARIANTS = ("iid", "smooth")
+COUNTERS = ("SQ_INSTS_VALU", "SQ_INSTS_VALU_TRANS_F64")
+TRANS_EXTRA = 2.8   # 16.2 / 4.25 - 1: issue cycles of v_rcp_f64 / v_rsq_f64 over those of an FP64 add / multiply / FMA, less the one counted
 
 
 def run(cache=None):
@@ -50,13 +56,17 @@ def read(dirs):
     for d in dirs:
         rows = []
         for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
-            rows += [r for r in csv.DictReader(open(f)) if "seqik_fused_kernel" in r["Kernel_Name"] and r["Counter_Name"] == "SQ_INSTS_VALU"]
-        per_dispatch = {}
+            rows += [r for r in csv.DictReader(open(f)) if "seqik_fused_kernel" in r["Kernel_Name"] and r["Counter_Name"] in COUNTERS]
+        per_dispatch, trans = {}, {}
         for r in rows:
-            per_dispatch[int(r["Dispatch_Id"])] = per_dispatch.get(int(r["Dispatch_Id"]), 0.0) + float(r["Counter_Value"])
+            acc = per_dispatch if r["Counter_Name"] == "SQ_INSTS_VALU" else trans
+            acc[int(r["Dispatch_Id"])] = acc.get(int(r["Dispatch_Id"]), 0.0) + float(r["Counter_Value"])
         out = {"dir": os.path.basename(os.path.normpath(d)), "launches": len(per_dispatch)}
         for variant, k in zip(VARIANTS, sorted(per_dispatch)):
             out[f"{variant}_valu_insts_per_launch"] = per_dispatch[k]
+            if k in trans:
+                out[f"{variant}_f64_trans_insts_per_launch"] = trans[k]
+                out[f"{variant}_weighted_insts_per_launch"] = per_dispatch[k] + TRANS_EXTRA * trans[k]
         print(json.dumps(out))
 
 

@@ -89,10 +89,19 @@ SEQIK_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, 
 //   8  stages 2-4: the translation of the frame after the active links, which no angle enters, is formed once per frame
 //      (StageProblem::t_act) and the three evaluations of a pass form only the third column of the rotation (residual_sc)
 //  16  solve_tr_2x2 keeps the Gauss-Newton step and its norm from the trust-region test for the first phi / ratio
-// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all five.
+// and the four of round 9, divisions and square roots (16-cycle v_rcp_f64 / v_rsq_f64 plus 8 / 12 Newton instructions
+// each) whose value nothing reads as a value:
+//  32  solve_tr_2x2<false>: the rank test without its eigenvalues where the determinant clears it by far (tr2_rank_sure)
+//  64  stages 1-3: ||step|| < xtol (xtol + ||x||) decided on the squares (step_below)
+// 128  stage 4: sqrt(a0 * a0) is |a0| (norm2v<1>)
+// 256  (not assigned: handing the reciprocals of select_step_reflective's first distance to the bounds on to its second
+//      cost registers and scratch in 17 kernels and was taken out, EXPERIMENTS.md 21.4)
+// 512  stage 1: the first multiplier of a solve without sqrt(0 * alpha_upper) (tr_first_alpha)
+// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all nine.
 #ifndef SEQIK_PASS_CUTS
-#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 31 : 0)
-#endif// "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
+#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 1023 : 0)
+#endif
+// "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
 SEQIK_HD bool wave_any(bool c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -548,12 +557,53 @@ SEQIK_HD double strictly_feasible_pinned(double x, double lb, double ub, double 
 // ---------------------------------------------------------------------------
 // Small fixed-size linear algebra.  Vectors have 2 slots; slot 1 is unused when NA == 1.
 // ---------------------------------------------------------------------------
-template <int NA>
-SEQIK_HD double norm2v(const double *a)
+// ABS1 (bit 128 of SEQIK_PASS_CUTS; one unknown, stage 4): the norm is sqrt(fl(a0 * a0)).  In binary arithmetic with
+// correct rounding sqrt(fl(x * x)) == |x| whenever x * x neither underflows nor overflows: fl(x * x) = x^2 (1 + e), |e| <=
+// 2^-53, so its root is |x| (1 + e / 2 - ...), less than half an ulp of |x| away from |x| wherever |x| sits in its binade
+// (at the bottom of a binade the spacing below |x| halves, and there e / 2 <= 2^-54 is still short of half of it) -- and
+// |x| is a double.  x == +-0 gives +0 on both sides.  So where acc = fl(a0 * a0) is a normal number (2^-1021 leaves a
+// binade to spare) or a0 is a zero, fabs(a0) IS the oracle's IEEE result; the parent reached it through sqrt_, here no
+// property of sqrt_ is used.  Anything else -- subnormal or zero acc of a non-zero a0, inf, NaN -- on any active lane sends
+// the wavefront through the plain form.  `short_form` (nullable) tells the host harness which branch ran.
+template <int NA, bool ABS1 = (SEQIK_PASS_CUTS & 128) != 0>
+SEQIK_HD double norm2v(const double *a, bool *short_form = nullptr)
 {
     double acc = a[0] * a[0];
     if constexpr (NA == 2) acc = fma_(a[1], a[1], acc);
+    if constexpr (NA == 1 && ABS1) {
+        const bool sure = (acc >= 0x1p-1021 && acc < __builtin_huge_val()) || a[0] == 0.0;
+        const bool plain = wave_any(!sure);
+        if (short_form) *short_form = !plain;
+        if (!plain) return fabs(a[0]);
+    } else if (short_form) *short_form = false;
     return sqrt_(acc);
+}
+
+// sqrt(S) < T, the only reader of ||step|| in stages 1-3 (xtol test: S = the sum of squares norm2v forms, T = xtol (xtol +
+// ||x||)), decided on the squares (SQUARES: bit 64 of SEQIK_PASS_CUTS).  With u = 2^-53, T2 = fl(T * T) = T^2 (1 + e1) and
+// the band edges fl(T2 (1 -+ 2^-49)) carry two roundings, so
+//   S < lo  =>  S < T^2 (1 - 2^-49)(1 + u)^2  =>  sqrt(S) < T (1 - 2^-50 + 2 u) = T (1 - 6 u)
+//   S > hi  =>  sqrt(S) > T (1 + 2^-50 - 2 u - 2^-100) > T (1 + 5 u).
+// A square root that is off by up to 2 ulp (4 u relative; the oracle's IEEE one is within u) of such an S still lies
+// below / above the double T, so the comparison has the oracle's outcome and the root is not taken.  That holds for any S >=
+// 0, zero and underflowed sums included: S is the same double in both forms, the real square root is monotone, and T >=
+// xtol^2 = 1e-16 keeps T2 and both edges normal (>= 1e-32).  T2 = inf (T >= 2^512, or T = inf) makes both edges inf: a
+// finite S is then `below`, which is right since sqrt(S) < 2^512 <= T; S = inf lands in the band.  Inside the band, or with
+// a NaN on either side (both comparisons false), on any active lane the wavefront takes the plain form.  The band is 4e-15
+// wide relative to T^2.  branch (nullable, host harness): 1 decided true, 0 decided false, 2 plain form.
+template <bool SQUARES = (SEQIK_PASS_CUTS & 64) != 0>
+SEQIK_HD bool step_below(double S, double T, int *branch = nullptr)
+{
+    if constexpr (SQUARES) {
+        const double T2 = T * T;
+        const bool below = S < T2 * (1.0 - 0x1p-49), above = S > T2 * (1.0 + 0x1p-49);
+        if (!wave_any(!(below || above))) {
+            if (branch) *branch = below ? 1 : 0;
+            return below;
+        }
+    }
+    if (branch) *branch = 2;
+    return sqrt_(S) < T;
 }
 
 template <int NA>
@@ -786,6 +836,21 @@ SEQIK_HD void apply_V_neg(const double V[2][2], const double *tmp, double *p)
     }
 }
 
+// The first multiplier of a solve that is not full rank and starts from alpha == 0: scipy's max(0.001 alpha_upper,
+// sqrt(alpha_lower alpha_upper)) with alpha_lower still the literal 0.0 it was initialised to.  z = 0.0 * alpha_upper is a
+// zero with alpha_upper's sign for a finite alpha_upper and a NaN for an infinite or NaN one, and IEEE sqrt returns +-0 and
+// NaN as they are (so does sqrt_: its zero select, and a NaN through the iteration) -- so sqrt(z) == z and the root is not
+// taken (NO_ROOT: bit 512 of SEQIK_PASS_CUTS).  The product stays: it is what makes inf and NaN come out as before (fmax
+// returns its other operand for a NaN, and NaN for two).  The callers ask for it in the DEFICIENT instantiation only -- stage
+// 1, which takes this line in the first pass of every solve; a full-rank stage reaches it on a singular Jacobian alone, where
+// the short form saved nothing and cost stage 3's kernels registers.
+template <bool NO_ROOT = (SEQIK_PASS_CUTS & 512) != 0>
+SEQIK_HD double tr_first_alpha(double alpha_upper)
+{
+    if constexpr (NO_ROOT) return fmax(0.001 * alpha_upper, 0.0 * alpha_upper);
+    else return fmax(0.001 * alpha_upper, sqrt_(0.0 * alpha_upper));
+}
+
 // _lsq/common.py:solve_lsq_trust_region on the active set (m = 3 residuals >= NA)
 template <int NA, bool DEFICIENT>
 SEQIK_HD void solve_lsq_trust_region(const double *uf, const double *s, const double V[2][2], double Delta,
@@ -815,7 +880,7 @@ SEQIK_HD void solve_lsq_trust_region(const double *uf, const double *s, const do
         alpha_lower = -ratio;
     }
     double alpha = alpha_io;
-    if (!full_rank && alpha == 0.0) alpha = fmax(0.001 * alpha_upper, sqrt_(alpha_lower * alpha_upper));
+    if (!full_rank && alpha == 0.0) alpha = tr_first_alpha<DEFICIENT && (SEQIK_PASS_CUTS & 512) != 0>(alpha_upper);   // (alpha_lower is 0.0 here)
     for (int it = 0; it < 10; ++it) {
         if (alpha < alpha_lower || alpha > alpha_upper)
             alpha = fmax(0.001 * alpha_upper, sqrt_(alpha_lower * alpha_upper));
@@ -874,7 +939,41 @@ SEQIK_HD void tr2_phi(double aa, double b, double cc, const double *r, double De
 // only what tr2_phi does after them remains: tr2_apply(pp -> q), the dot product, phi and the division of ratio -- the same
 // operations on the same operands in the same order, so the same bits.  pp is overwritten by every later tr2_phi /
 // tr2_apply as before.  The rank-deficient paths and the root loop are untouched.
-template <bool DEFICIENT, bool KEEP_GN = (SEQIK_PASS_CUTS & 16) != 0>
+//
+// RANK_GUARD (bit 32): the rank test reads its two eigenvalues -- a square root and a division -- through one comparison,
+// lmin > C lmax with C = (3 eps)^2 = 2^-100.8.  tr2_rank_sure decides it from det = fma(a, c, -(b b)) (the numerator the
+// plain form divides; tr2_apply forms it again) and s = a + c:  sure = det > K s^2 with K = 2^-97 = 14 C, and 2^-401 < s <
+// 2^498 (which implies the K s^2 > 2^-900 that keeps the guard's own arithmetic away from underflow, keeps s^2, a c and
+// ((a - c) / 2)^2 away from overflow, and makes s positive).  Then, with u = 2^-53 and EVERY quantity the one the plain form
+// computes (the same doubles, not their real counterparts):
+//   * det > 0 means a c > fl(b b) >= 0, so a and c have one sign, s's: both are positive, and b^2 <= fl(b b)(1 + u) < a c
+//     (1 + u) <= (s / 2)^2 (1 + 3 u)  (a + c rounds once);
+//   * ((a - c) / 2)^2 + b^2 = ((a + c)^2 - 4 a c) / 4 + b^2 < (s / 2)^2 (1 + 6 u), so the plain form's sqrt_(fma(h, h, b b))
+//     is at most (s / 2)(1 + 9 u) even with a 2 ulp error of sqrt_, and 0 < s / 2 <= lmax <= s (1 + 6 u);
+//   * lmin = div_(det, lmax) >= det / lmax (1 - 4 u) (2 ulp allowed) > K s^2 (1 - 5 u) / lmax >= K lmax (1 - 18 u) > C lmax
+//     (1 + u) >= fl(C lmax): the comparison is true, with a factor 14 to spare.  lmin > K s / 2 > 2^-500 and C lmax > 2^-503:
+//     nothing underflows on the way.
+// A NaN among a, b, c makes det or s a NaN and the guard false; s^2 or a product beyond the range is excluded by the bounds
+// on s, and b b = inf gives det = -inf or NaN.  Where every active lane is sure the wavefront skips the eigenvalues; one
+// lane that is not sends it through the plain form, which gives the sure lanes `true` as well.  (solve_tr_2x2 hands the
+// guard a + 0.0 and c + 0.0, the operands tr2_apply takes, so that the two determinants are one: they differ from a and c
+// only where one is -0, and a zero a or c makes det <= 0 either way.)
+SEQIK_HD bool tr2_rank_sure(double a, double b, double c)
+{
+    const double det = fma_(a, c, -(b * b));
+    const double s = a + c;
+    return det > 0x1p-97 * s * s && s > 0x1p-401 && s < 0x1p+498;
+}
+
+SEQIK_HD bool tr2_rank_plain(double a, double b, double c)
+{
+    double h = 0.5 * (a - c);
+    double lmax = fma_(0.5, a + c, sqrt_(fma_(h, h, b * b)));
+    double lmin = div_(fma_(a, c, -(b * b)), lmax);
+    return lmin > 4.437342591868191e-31 * lmax;  // (3 eps)^2: s_min > eps * m * s_max
+}
+
+template <bool DEFICIENT, bool KEEP_GN = (SEQIK_PASS_CUTS & 16) != 0, bool RANK_GUARD = (SEQIK_PASS_CUTS & 32) != 0>
 SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const double *f, double Delta,
                            double &alpha_io, double *p)
 {
@@ -890,10 +989,9 @@ SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const do
     r[1] = fma_(Jh[2][1], f[2], fma_(Jh[1][1], f[1], Jh[0][1] * f[0]));
     bool full_rank = false;
     if constexpr (!DEFICIENT) {
-        double h = 0.5 * (a - c);
-        double lmax = fma_(0.5, a + c, sqrt_(fma_(h, h, b * b)));
-        double lmin = div_(fma_(a, c, -(b * b)), lmax);
-        full_rank = lmin > 4.437342591868191e-31 * lmax;  // (3 eps)^2: s_min > eps * m * s_max
+        bool plain = true;
+        if constexpr (RANK_GUARD) plain = wave_any(!tr2_rank_sure(a + 0.0, b, c + 0.0));
+        full_rank = plain ? tr2_rank_plain(a, b, c) : true;
         if (full_rank) {
             tr2_apply(a + 0.0, b, c + 0.0, r, pp);
             gn_norm = sqrt_(fma_(pp[1], pp[1], pp[0] * pp[0]));
@@ -917,7 +1015,7 @@ SEQIK_HD void solve_tr_2x2(const double Jh[3][2], const double *diag_h, const do
         alpha_lower = -ratio;
     }
     double alpha = alpha_io;
-    if (!full_rank && alpha == 0.0) alpha = fmax(0.001 * alpha_upper, sqrt_(alpha_lower * alpha_upper));
+    if (!full_rank && alpha == 0.0) alpha = tr_first_alpha<DEFICIENT && (SEQIK_PASS_CUTS & 512) != 0>(alpha_upper);   // (alpha_lower is 0.0 here)
     // SHORTCUT of the m < n root search (mirrors oracle solve_tr_2x2, where it is derived): when the Gauss-Newton
     // step lies well inside the trust region scipy's ten iterations are ten resets alpha <- 0.001 alpha_upper plus
     // one Newton step from the last alpha, so only that alpha is evaluated; otherwise the verbatim loop runs.
@@ -2021,7 +2119,9 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 double p_h[2], p[2], step[2], step_h[2];
                 SEQIK_BLK_END_OF(BLK_SCALING);
                 if constexpr (NA == 2) {
-                    solve_tr_2x2<T::DEFICIENT>(Jh, diag_h, f, Delta, alpha, p_h);
+                    // (bit 32 everywhere but in the 168-register stage pipeline, whose two kernels it cost 8 B of scratch)
+                    solve_tr_2x2<T::DEFICIENT, (SEQIK_PASS_CUTS & 16) != 0, (SEQIK_PASS_CUTS & 32) != 0 && (!PIPED || LAT)>(
+                        Jh, diag_h, f, Delta, alpha, p_h);
                 } else {  // one unknown: the "SVD" is a column norm
                     double q[2] = {sqrt_(diag_h[0]), 0.0}, s[2], V[2][2], uf[2];
                     svd_active<1>(Jh, q, f, s, V, uf);
@@ -2075,7 +2175,6 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 double Delta_new = Delta;
                 if (ratio < 0.25) Delta_new = 0.25 * step_h_norm;
                 else if (ratio > 0.75 && step_h_norm > 0.95 * Delta) Delta_new = Delta * 2.0;
-                double step_norm = norm2v<NA>(step);
                 // ||x|| over all links: inert prefix, active, inert last link
                 double xn = sc.x_pre_sq;
                 xn = fma_(x[0], x[0], xn);
@@ -2083,7 +2182,11 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 xn = fma_(sc.x_suf, sc.x_suf, xn);
                 xn = sqrt_(xn);
                 bool ftol_ok = (actual_reduction < ftol * cost) && (ratio > 0.25);
-                bool xtol_ok = step_norm < xtol * (xtol + xn);
+                // ||step|| is read by this one comparison: two unknowns decide it on the squares (step_below), one unknown
+                // has its norm as |step[0]| (norm2v<1>)
+                bool xtol_ok;
+                if constexpr (NA == 2) xtol_ok = step_below(fma_(step[1], step[1], step[0] * step[0]), xtol * (xtol + xn));
+                else xtol_ok = norm2v<NA>(step) < xtol * (xtol + xn);
                 if (ftol_ok && xtol_ok) status = 4;
                 else if (ftol_ok) status = 2;
                 else if (xtol_ok) status = 3;
