@@ -3,12 +3,11 @@ its kernels, named gap patterns and poisoned inputs for the geometry
 tests/harness/gaps_harness.hip.  Shared by tests/test_missing_key_points.py and tests/test_gaps_geometry.py."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
-from conftest import PKG_PARENT, ROOT, LegParamsC
+from conftest import ROOT, LegParamsC
+from harness_build import build_harness, find_hipcc
 
 MISSING = -100
 
@@ -261,17 +260,6 @@ class GapsHarness:
 
 def load_gaps_harness():
     """Builds tests/harness/gaps_harness.hip for the host if stale; None when there is no hipcc."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    if find_hipcc() is None:
         return None
-    src = os.path.join(ROOT, "tests", "harness", "gaps_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libgaps_harness.so")
-    deps = [src, os.path.join(ROOT, "include", "seqik_gaps.h")] + [
-        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_gaps.hpp",
-                                                      "seqik_runtime.hpp", "seqik_device_scope.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return GapsHarness(so)
+    return GapsHarness(build_harness(os.path.join(ROOT, "tests", "harness", "gaps_harness.hip")))

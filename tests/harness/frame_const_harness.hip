@@ -5,11 +5,11 @@
 //   bit 8   residual_sc<STAGE, true> (translation of the frame after the active links kept in StageProblem::t_act) against
 //           residual_sc_general<STAGE>, and frame_after_active with t replaced by t_act against the plain call;
 //   bit 16  solve_tr_2x2<false, true> (Gauss-Newton step and norm kept) against solve_tr_2x2<false, false>.
-// Built by that test with `hipcc --offload-host-only`, like pass_path_harness.hip.
+// Built by that test through tests/harness_build.py.  The operands of solve_tr_2x2 recorded from host runs of run_stage come
+// from first_pass_harness.hip (stages 2 and 3, columns 0..12).
 #include "../../sequential-inverse-kinematics_amd/csrc/seqik_core.hpp"
 #include "../../sequential-inverse-kinematics_amd/csrc/seqik_consts.hpp"
 #include <string.h>
-#include <vector>
 
 static uint64_t bits_of(double v)
 {
@@ -142,65 +142,4 @@ extern "C" int64_t fc_tr2_compare(const double *ops, int64_t n, int64_t *counts,
         }
     }
     return bad;
-}
-
-// Operands of solve_tr_2x2 from a host run of run_stage over one chain (stages 2 and 3, the full-rank two-unknown
-// stages): the chain is solved by run_stage<1..4> as the staged launch does it, then for every frame and stage the operands
-// of the FIRST pass of that solve are formed from the run's angles with run_stage's own helpers in its order -- prefix
-// (build_prefix), warm start = the previous frame's solution made strictly feasible, residual, finite-difference Jacobian,
-// Coleman-Li scaling, Delta_0.  ops [cap][13] as above; returns the number of rows written (2 per frame), < 0 on error.
-template <int STAGE>
-static void fc_first_pass(const seqik::LegConst &lc, const double *pose, const double *ang, const double *warm, double *o)
-{
-    using namespace seqik;
-    const StageConst &sc = lc.st[STAGE - 1];
-    StageProblem<STAGE> P;
-    P.tz_a = sc.tz_a; P.tz_b = sc.tz_b; P.tz_last = sc.tz_last;
-    build_prefix<STAGE>(P.pre, lc, ang, 1, nullptr);
-    for (int i = 0; i < 3; ++i) P.target[i] = pose[3 * STAGE + i] - pose[i];
-    double x[2], f[3], sa, ca, sb, cb, J[3][2], g[2], v[2], dv[2], d[2];
-    for (int j = 0; j < 2; ++j) x[j] = strictly_feasible(warm[j], sc.lb[j], sc.ub[j], 1e-10);
-    eval_residual<STAGE>(P, x[0], x[1], f, sa, ca, sb, cb);
-    fd_jacobian<STAGE>(P, x, f, sc.lb, sc.ub, sa, ca, sb, cb, true, J);
-    for (int j = 0; j < 2; ++j) {
-        g[j] = fma_(J[2][j], f[2], fma_(J[1][j], f[1], J[0][j] * f[0]));
-        cl_scaling(x[j], g[j], sc.lb[j], sc.ub[j], v[j], dv[j]);
-        d[j] = sqrt_pos_(v[j]);
-    }
-    double acc = sc.x_pre_sq;
-    for (int j = 0; j < 2; ++j) { const double t = div_(x[j], d[j]); acc = fma_(t, t, acc); }
-    acc = fma_(sc.x_suf, sc.x_suf, acc);
-    double Delta = sqrt_(acc);
-    if (Delta == 0) Delta = 1.0;
-    for (int k = 0; k < 3; ++k) { o[2 * k] = J[k][0] * d[0]; o[2 * k + 1] = J[k][1] * d[1]; }
-    for (int j = 0; j < 2; ++j) o[6 + j] = g[j] * dv[j] * 1.0;
-    for (int k = 0; k < 3; ++k) o[8 + k] = f[k];
-    o[11] = Delta;
-    o[12] = 0.0;
-}
-
-extern "C" int64_t fc_record_tr2(const double *pose, int64_t n_frames, const SeqikLegParams *leg, double *ops, int64_t cap)
-{
-    if (seqik::validate_leg(*leg, 1, 4) != SEQIK_OK) return -1;
-    seqik::LegConst lc;
-    seqik::make_leg_consts(*leg, nullptr, lc);
-    std::vector<double> ang((size_t)n_frames * 7, 0.0), ws((size_t)n_frames * 12 + 1);
-    seqik::ChainIO io;
-    io.pose = pose; io.pose_row = 3; io.pose_frame = 15;
-    io.angles = ang.data(); io.ang_dof = 1; io.ang_frame = 7;
-    io.fk = nullptr; io.status = nullptr; io.nfev = nullptr; io.init = nullptr;
-    io.frames = ws.data(); io.n_frames = n_frames;
-    seqik::run_stage<1, false, false, false, true>(lc, io);
-    seqik::run_stage<2, false, false, false, true>(lc, io);
-    seqik::run_stage<3, false, false, false, true>(lc, io);
-    seqik::run_stage<4, false, false, false, false>(lc, io);
-    int64_t rows = 0;
-    for (int64_t t = 0; t < n_frames && rows + 2 <= cap; ++t) {
-        const double *a = ang.data() + 7 * t;
-        const double *w2 = t ? ang.data() + 7 * (t - 1) + 2 : lc.st[1].seed;
-        const double *w3 = t ? ang.data() + 7 * (t - 1) + 4 : lc.st[2].seed;
-        fc_first_pass<2>(lc, pose + 15 * t, a, w2, ops + 13 * rows++);
-        fc_first_pass<3>(lc, pose + 15 * t, a, w3, ops + 13 * rows++);
-    }
-    return rows;
 }

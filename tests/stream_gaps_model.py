@@ -3,12 +3,11 @@ library with -- the seed state, the state a chain carries out of a slab, named g
 of tests/harness/stream_gaps_harness.hip."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
-from conftest import PKG_PARENT, ROOT, LegParamsC
+from conftest import ROOT, LegParamsC
+from harness_build import build_harness, find_hipcc
 
 SEQ_SEED_INDEX = [1, 2, 7, 8, 15, 16, 25]     # kSeedOffset[s] + kFirstActive[s] + j: every stage's active links
 GENERIC_LINK_DOF = [2, 0, 1, 3, 4, 5, 6]      # kGenericLinkDof: link i of the generic chain carries this DOF
@@ -94,16 +93,6 @@ class StreamGapsHarness:
 
 def load_stream_gaps_harness():
     """Builds tests/harness/stream_gaps_harness.hip for the host if stale; None when there is no hipcc."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
+    if find_hipcc() is None:
         return None
-    src = os.path.join(ROOT, "tests", "harness", "stream_gaps_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libstream_gaps_harness.so")
-    deps = [src, os.path.join(ROOT, "include", "seqik_gaps.h")] + [
-        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_generic.hpp", "seqik_gaps.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return StreamGapsHarness(so)
+    return StreamGapsHarness(build_harness(os.path.join(ROOT, "tests", "harness", "stream_gaps_harness.hip")))

@@ -8,13 +8,12 @@ import ctypes
 import os
 import pickle
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import DOFS, PKG_PARENT, ROOT, LegParamsC, leg_arrays, load_golden
+from conftest import DOFS, ROOT, LegParamsC, leg_arrays, load_golden
+from harness_build import build_harness
 
 FK_SYMBOLS = ["seqik_forward_kinematics", "seqik_forward_kinematics_device"]
 
@@ -61,19 +60,7 @@ class FkHarness:
 
 @pytest.fixture(scope="module")
 def fk_harness():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "fk_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libfk_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp",
-                                                                 "seqik_generic.hpp", "seqik_fk.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return FkHarness(so)
+    return FkHarness(build_harness(os.path.join(ROOT, "tests", "harness", "fk_harness.hip")))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -10,14 +10,16 @@ GPU tier: HIP == C oracle bit for bit on 70 sequences x 6 legs x 6 frames of iid
 one of six lanes; lanes start their frames in different passes, so a translation left over from another frame on any launch
 path shows), through every launch path, with shipped limits and with a limit range of 1e-8 on one joint of every stage."""
 import ctypes
+import functools
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, SEED_LINK_DOF, LegParamsC, load_golden
+from conftest import ROOT, LegParamsC
+from harness_build import build_harness
+from pass_cut_support import (LAUNCH_PATHS, assert_equal_reference, first_pass_rows, leg_struct, narrow_limits,
+                              oracle_reference, shipped_legs, solve_on_path)
 
 dp = ctypes.POINTER(ctypes.c_double)
 i64p = ctypes.POINTER(ctypes.c_int64)
@@ -25,18 +27,7 @@ i64p = ctypes.POINTER(ctypes.c_int64)
 
 @pytest.fixture(scope="module")
 def fc():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "frame_const_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libframe_const_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_generic.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_harness(os.path.join(ROOT, "tests", "harness", "frame_const_harness.hip")))
     lib.fc_prefixes.restype = ctypes.c_int
     lib.fc_prefixes.argtypes = [ctypes.c_int32, ctypes.POINTER(LegParamsC), dp, ctypes.c_int64, dp, dp]
     lib.fc_compare.restype = ctypes.c_int
@@ -44,30 +35,7 @@ def fc():
     lib.fc_sincos.argtypes = [dp, ctypes.c_int64, dp]
     lib.fc_tr2_compare.restype = ctypes.c_int64
     lib.fc_tr2_compare.argtypes = [dp, ctypes.c_int64, i64p, ctypes.POINTER(ctypes.c_int32), dp, dp, i64p]
-    lib.fc_record_tr2.restype = ctypes.c_int64
-    lib.fc_record_tr2.argtypes = [dp, ctypes.c_int64, ctypes.POINTER(LegParamsC), dp, ctypes.c_int64]
     return lib
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _leg_struct(seg, bounds, seeds):
-    lp = LegParamsC()
-    for i in range(4):
-        lp.seg[i] = seg[i]
-    for i in range(7):
-        lp.bounds[i][0], lp.bounds[i][1] = bounds[i][0], bounds[i][1]
-    for i in range(27):
-        lp.seeds[i] = seeds[i]
-    return lp
-
-
-def _shipped_legs(oracle):
-    from seqikpy_amd import data, utils
-    body = utils.calculate_body_size(data.TEMPLATE_NMF_LOCOMOTION, data.LEGS)
-    return [oracle.leg_params(l, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION) for l in data.LEGS]
 
 
 # ---- bit 8: hoisted residual == general residual; frame at the frame's end ---------------------------------------------------
@@ -89,7 +57,7 @@ def _sincos_pool(fc, rng):
 
 
 def _operand_sets(fc, oracle, stage, rng):
-    legs = _shipped_legs(oracle)
+    legs = shipped_legs(oracle)
     pres, tzs = [], []
     per_leg = 300
     for seg, b, seeds in legs:
@@ -98,7 +66,7 @@ def _operand_sets(fc, oracle, stage, rng):
         ang[:8, :] = np.where(rng.random((8, 7)) < 0.5, 0.0, -0.0)                 # ... and angles of +-0 where they are allowed
         ang[:8] = np.clip(ang[:8], lb, ub)
         pre, tz = np.zeros((per_leg, 12)), np.zeros(3)
-        assert fc.fc_prefixes(stage, ctypes.byref(_leg_struct(seg, b, seeds)), ang.ctypes.data_as(dp), per_leg,
+        assert fc.fc_prefixes(stage, ctypes.byref(leg_struct(seg, b, seeds)), ang.ctypes.data_as(dp), per_leg,
                               pre.ctypes.data_as(dp), tz.ctypes.data_as(dp)) == 0
         pres.append(pre)
         tzs.append(np.broadcast_to(tz, (per_leg, 3)))
@@ -165,19 +133,11 @@ def _tr2(fc, ops):
 
 @pytest.fixture(scope="module")
 def recorded_ops(fc):
-    """First-pass operands of solve_tr_2x2 from host runs of run_stage on the shipped recording, all six legs."""
-    z = load_golden("df3d_100")
-    rows = []
-    for leg in [str(l) for l in z["legs"]]:
-        pose = np.ascontiguousarray(z[f"{leg}_pose"], dtype=np.float64)
-        ops = np.zeros((2 * len(pose), 13))
-        n = fc.fc_record_tr2(pose.ctypes.data_as(dp), len(pose), ctypes.byref(_leg_struct(z[f"{leg}_seg"], z[f"{leg}_bounds"],
-                                                                                             z[f"{leg}_seeds"])),
-                             ops.ctypes.data_as(dp), len(ops))
-        assert n == len(ops)
-        rows.append(ops)
-    ops = np.concatenate(rows)
-    assert np.all(np.isfinite(ops))
+    """First-pass operands of solve_tr_2x2 (stages 2 and 3, the full-rank two-unknown stages) from host runs of run_stage on
+    the shipped recording, all six legs."""
+    rows = first_pass_rows()
+    ops = np.ascontiguousarray(rows[(rows[:, 27] == 2) | (rows[:, 27] == 3)][:, :13])
+    assert len(ops) == 1200 and np.all(np.isfinite(ops))
     ops.setflags(write=False)
     return ops
 
@@ -271,73 +231,25 @@ def _gpu_case(kind):
         seg, b, seeds = c_oracle.leg_params(leg, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION)
         b, seeds = b.copy(), seeds.copy()
         if kind == "narrow":
-            for dof in (1, 2, 5, 6):   # ThC_pitch (stage 1), ThC_roll (2), FTi_pitch (3), TiTa_pitch (4)
-                c = float(seeds[SEED_LINK_DOF.index(dof)])
-                if dof == 6:
-                    c = -0.6           # (the shipped seed 0 sits on the shipped upper limit)
-                b[dof] = (c - 0.5e-8, c + 0.5e-8)
-                for i, d in enumerate(SEED_LINK_DOF):
-                    if d == dof:
-                        seeds[i] = c
+            narrow_limits(b, seeds)
         cases.append((seg, b, seeds))
     return pose, cases
 
 
-_CASES = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _gpu_case_with_reference(kind):
     """pose, per-leg parameters and the C oracle's results for `kind`, computed once and shared read-only"""
-    if kind in _CASES:
-        return _CASES[kind]
-    from oracle import c_oracle
-    c_oracle.build()
     pose, cases = _gpu_case(kind)
-    ref = dict(angles=np.zeros((S_GPU, 6, N_GPU, 7)), fk=np.zeros((S_GPU, 6, N_GPU, 9, 3)),
-               status=np.zeros((S_GPU, 6, N_GPU, 4), np.int32), nfev=np.zeros((S_GPU, 6, N_GPU, 4), np.int32))
-    for li, (seg, b, seeds) in enumerate(cases):
-        for s in range(S_GPU):
-            r = c_oracle.seq_leg(pose[s, li], seg, b, seeds)
-            for k in ref:
-                ref[k][s, li] = r[k]
-    for v in ref.values():
-        v.setflags(write=False)
-    _CASES[kind] = (pose, cases, ref)
-    return _CASES[kind]
-
-
-PATHS = dict(fused=dict(pipeline=1, lanes_per_wave=64), queue128=dict(pipeline=1, lanes_per_wave=128),
-             staged=dict(staged=1, lanes_per_wave=64), staged_diag=dict(want_diag=True), pipeline=dict(pipeline=2),
-             chunked=dict(frame_chunk=3, frame_halo=2, chunk_tol=-1.0, chunk_rounds=2),   # exact mode: == the serial walk
-             subset=None)
+    return pose, cases, oracle_reference(pose, cases)
 
 
 # shipped limits through every launch path; the narrow limits (general fd_step, joints pinned between limits 1e-8 apart)
 # once per kernel family
-GPU_RUNS = [("base", p) for p in PATHS] + [("narrow", p) for p in ("fused", "staged_diag", "pipeline")]
+GPU_RUNS = [("base", p) for p in LAUNCH_PATHS] + [("narrow", p) for p in ("fused", "staged_diag", "pipeline")]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,path", GPU_RUNS)
 def test_launch_paths_equal_the_oracle_bit_for_bit(hiplib, kind, path):
     pose, cases, ref = _gpu_case_with_reference(kind)
-    params = [hiplib.leg_params_from_arrays(*c) for c in cases]
-    if path == "subset":
-        # stages k .. 4 from the stored angles of the earlier stages: the FROM_ANGLES instantiations, which rebuild the
-        # prefix (and read its translation for the FK rows of the stages that are not run)
-        outs = []
-        for first in (2, 3, 4):
-            prior = ref["angles"].copy()
-            prior[..., 2 * (first - 1):] = 0.0
-            outs.append(hiplib.solve_seq(pose, params, first_stage=first, last_stage=4, angles=prior, want_fk=True))
-    else:
-        outs = [hiplib.solve_seq(pose, params, want_fk=True, **PATHS[path])]
-    hiplib.check_faults()
-    for out in outs:
-        assert np.array_equal(_bits(out["angles"]), _bits(ref["angles"]))
-        assert np.array_equal(_bits(out["fk"]), _bits(ref["fk"]))
-    if path == "staged_diag":
-        assert np.array_equal(outs[0]["status"], ref["status"])
-        assert np.array_equal(outs[0]["nfev"], ref["nfev"])
-    if path == "chunked":
-        assert outs[0]["chunk_stats"]["chunks"] == 2 * S_GPU * 6   # every chain was cut into two chunks
+    assert_equal_reference(solve_on_path(hiplib, pose, cases, ref, path), ref, path, n_chains=S_GPU * 6)

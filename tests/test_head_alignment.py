@@ -13,14 +13,13 @@ import importlib.util
 import os
 import pickle
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, load_golden
+from conftest import ROOT, load_golden
+from harness_build import build_harness
 
 HEAD_ALIGN_SYMBOLS = ["seqik_head_align_stats_open", "seqik_head_align_stats_select", "seqik_head_align_stats_pick",
                       "seqik_head_align_stats_close", "seqik_head_angles_raw", "seqik_head_angles_raw_device"]
@@ -94,19 +93,7 @@ class HeadAlignHarness:
 
 @pytest.fixture(scope="module")
 def head_align_harness():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "head_align_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libhead_align_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_head.hpp", "seqik_head_align.hpp")]
-    deps.append(os.path.join(ROOT, "include", "seqik_head_align.h"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return HeadAlignHarness(so)
+    return HeadAlignHarness(build_harness(os.path.join(ROOT, "tests", "harness", "head_align_harness.hip")))
 
 
 # -- numpy restatement of what AlignPose.align_head reduces (the yardstick) ---------------------------------------------

@@ -14,14 +14,13 @@ import ctypes
 import os
 import pickle
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import DOFS, PKG_PARENT, ROOT, LegParamsC, load_golden
+from conftest import DOFS, ROOT, LegParamsC, load_golden
+from harness_build import build_harness
 from test_forward_kinematics import fk_harness, _lp  # noqa: F401  (fixture: the FK rule run on the host)
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -59,19 +58,7 @@ class FramesHarness:
 
 @pytest.fixture(scope="module")
 def frames_harness():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "frames_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libframes_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_generic.hpp",
-                                                                 "seqik_fk.hpp", "seqik_frames.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return FramesHarness(so)
+    return FramesHarness(build_harness(os.path.join(ROOT, "tests", "harness", "frames_harness.hip")))
 
 
 # -- the IKPy stand-in (oracle/shim/ikpy/link.py; its chain.py:25-35 is the product below) -----------------------------

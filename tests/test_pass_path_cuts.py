@@ -11,13 +11,14 @@ the chain queue, the staged launch and the stage pipeline, with shipped limits, 
 and with limits / seeds of exactly 0 and open bounds."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, SEED_LINK_DOF, LegParamsC
+from conftest import ROOT, LegParamsC
+from harness_build import build_harness
+from pass_cut_support import (assert_equal_reference, bits, leg_struct, narrow_limits,
+                              oracle_reference, pin_seed, shipped_legs, solve_on_path)
 
 dp = ctypes.POINTER(ctypes.c_double)
 RSTEP = 2.0 ** -26
@@ -25,18 +26,7 @@ RSTEP = 2.0 ** -26
 
 @pytest.fixture(scope="module")
 def pp():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "pass_path_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libpass_path_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_generic.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_harness(os.path.join(ROOT, "tests", "harness", "pass_path_harness.hip")))
     lib.pp_sincos_mismatches.restype = ctypes.c_int64
     lib.pp_sincos_mismatches.argtypes = [ctypes.c_void_p, dp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     lib.pp_leg_consts.argtypes = [ctypes.POINTER(LegParamsC), dp, ctypes.POINTER(ctypes.c_int32)]
@@ -48,30 +38,9 @@ def pp():
     return lib
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _leg_struct(seg, bounds, seeds):
-    lp = LegParamsC()
-    for i in range(4):
-        lp.seg[i] = seg[i]
-    for i in range(7):
-        lp.bounds[i][0], lp.bounds[i][1] = bounds[i][0], bounds[i][1]
-    for i in range(27):
-        lp.seeds[i] = seeds[i]
-    return lp
-
-
-def _shipped_legs(oracle):
-    from seqikpy_amd import data, utils
-    body = utils.calculate_body_size(data.TEMPLATE_NMF_LOCOMOTION, data.LEGS)
-    return [oracle.leg_params(l, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION) for l in data.LEGS]
-
-
 def _leg_consts(pp, seg, bounds, seeds):
     out, flags = np.zeros((4, 2, 6)), np.zeros(4, np.int32)
-    pp.pp_leg_consts(ctypes.byref(_leg_struct(seg, bounds, seeds)), out.ctypes.data_as(dp),
+    pp.pp_leg_consts(ctypes.byref(leg_struct(seg, bounds, seeds)), out.ctypes.data_as(dp),
                      flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
     return out, flags
 
@@ -93,7 +62,7 @@ def test_sincos_sign_bits_equal_the_oracle(oracle, pp):
                 near.append(lo)
             xs.append(np.array(near))
     # the host constants of the six shipped legs: the points themselves ...
-    consts = [_leg_consts(pp, *leg)[0] for leg in _shipped_legs(oracle)]
+    consts = [_leg_consts(pp, *leg)[0] for leg in shipped_legs(oracle)]
     for c in consts:
         xs.append(c[:, :, [0, 3]].ravel())
     x = np.ascontiguousarray(np.concatenate(xs))
@@ -107,7 +76,7 @@ def test_sincos_sign_bits_equal_the_oracle(oracle, pp):
             for j in range(2):
                 for o in (0, 3):
                     s, co = oracle.sincos(c[st, j, o])
-                    assert _bits([s, co]).tolist() == _bits(c[st, j, o + 1:o + 3]).tolist()
+                    assert bits([s, co]).tolist() == bits(c[st, j, o + 1:o + 3]).tolist()
 
 
 # ---- A: fd_step_wide == fd_step wherever the flag is set ---------------------------------------------------------------------
@@ -133,7 +102,7 @@ def _fd_both(pp, x, lb, ub):
 
 def test_fd_step_wide_equals_fd_step_on_shipped_and_mirrored_limits(oracle, pp):
     pairs = set()
-    for seg, b, seeds in _shipped_legs(oracle):
+    for seg, b, seeds in shipped_legs(oracle):
         for lb, ub in b:
             pairs.add((float(lb), float(ub)))
             pairs.add((float(-ub), float(-lb)))   # the mirrored leg's limits
@@ -146,7 +115,7 @@ def test_fd_step_wide_equals_fd_step_on_shipped_and_mirrored_limits(oracle, pp):
         assert pp.pp_fd_limits_wide(lb, ub) == 1
         x = _fd_points(lb, ub)
         g, w = _fd_both(pp, x, lb, ub)
-        assert np.array_equal(_bits(g), _bits(w)), (lb, ub)
+        assert np.array_equal(bits(g), bits(w)), (lb, ub)
         flipped += int(np.sum(np.signbit(g) != np.signbit(np.where(x >= 0, 1.0, -1.0))))
     assert flipped > 100   # the sign flip next to a limit was exercised
 
@@ -162,16 +131,16 @@ def test_fd_step_flag_threshold_and_infinite_bounds(pp):
             x = _fd_points(lb, ub)
             g, w = _fd_both(pp, x, lb, ub)
             if want:
-                assert np.array_equal(_bits(g), _bits(w)), (lb, ub)
+                assert np.array_equal(bits(g), bits(w)), (lb, ub)
             elif width <= RSTEP * m:
                 # narrower than one step: the general routine's `!fitting` replacement fires and the short form would be
                 # wrong -- which is why the flag must be clear here
-                assert not np.array_equal(_bits(g), _bits(w)), (lb, ub)
+                assert not np.array_equal(bits(g), bits(w)), (lb, ub)
     for lb, ub in ((-np.inf, 0.7), (-0.7, np.inf), (-np.inf, np.inf), (-np.inf, 0.0), (0.0, np.inf)):
         assert pp.pp_fd_limits_wide(lb, ub) == 1
         x = _fd_points(lb, ub)
         g, w = _fd_both(pp, x, lb, ub)
-        assert np.array_equal(_bits(g), _bits(w)), (lb, ub)
+        assert np.array_equal(bits(g), bits(w)), (lb, ub)
 
 
 def test_fd_jacobian_takes_the_general_routine_when_the_flag_is_clear(pp):
@@ -191,7 +160,7 @@ def test_fd_jacobian_takes_the_general_routine_when_the_flag_is_clear(pp):
             J = np.zeros(6)
             pp.pp_fd_jacobian(x.ctypes.data_as(dp), lb.ctypes.data_as(dp), ub.ctypes.data_as(dp), general, J.ctypes.data_as(dp))
             outs.append(J)
-        assert np.array_equal(_bits(outs[0]), _bits(outs[1])), (case, lb, ub, x)
+        assert np.array_equal(bits(outs[0]), bits(outs[1])), (case, lb, ub, x)
 
 
 # ---- C: stage 1's evaluation, closed form == general form, zero signs included ----------------------------------------------
@@ -213,7 +182,7 @@ def test_stage1_closed_form_equals_the_chain_product(pp):
                     g, c = np.zeros(6), np.zeros(6)
                     pp.pp_stage1_eval(sa, ca, sb, cb, tz, np.ascontiguousarray(tg).ctypes.data_as(dp), g.ctypes.data_as(dp),
                                       c.ctypes.data_as(dp))
-                    assert _bits(g).tolist() == _bits(c).tolist(), (xa, xb, tz, tg, g, c)
+                    assert bits(g).tolist() == bits(c).tolist(), (xa, xb, tz, tg, g, c)
                     n += 1
     assert len(seen) == 16 and n > 20000
 
@@ -236,49 +205,27 @@ def _gpu_case(kind):
     for li, leg in enumerate(legs):
         seg, b, seeds = c_oracle.leg_params(leg, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION)
         b, seeds = b.copy(), seeds.copy()
-
-        def pin(dof, value):
-            for i, d in enumerate(SEED_LINK_DOF):
-                if d == dof:
-                    seeds[i] = value
-
         if kind == "narrow":
-            for dof in (1, 2, 5, 6):   # ThC_pitch (stage 1), ThC_roll (2), FTi_pitch (3), TiTa_pitch (4)
-                c = float(seeds[SEED_LINK_DOF.index(dof)])
-                if dof == 6:
-                    c = -0.6           # (the shipped seed 0 sits on the shipped upper limit)
-                b[dof] = (c - 0.5e-8, c + 0.5e-8)
-                pin(dof, c)
+            narrow_limits(b, seeds)
         elif kind == "edge":
             if li % 2 == 0:
                 b[0] = (-np.pi, 0.0)   # ThC_yaw: upper limit exactly 0, seed 0 on it
             else:
                 b[0] = (0.0, np.pi)    # ... lower limit exactly 0
-            pin(0, 0.0)
+            pin_seed(seeds, 0, 0.0)
             b[1] = (0.0, b[1][1]) if li < 3 else (b[1][0], 0.0)   # ThC_pitch: a limit of exactly 0, seed exactly 0
-            pin(1, 0.0)
+            pin_seed(seeds, 1, 0.0)
             b[2] = (-np.inf, b[2][1])                             # ThC_roll: one open bound
             b[4] = (b[4][0], np.inf) if li % 3 else (-np.inf, np.inf)
-            pin(3, 0.0)                                           # CTr_pitch seed exactly 0 (inside its limits)
+            pin_seed(seeds, 3, 0.0)                               # CTr_pitch seed exactly 0 (inside its limits)
         cases.append((seg, b, seeds))
     return pose, cases
 
 
 @pytest.fixture(scope="module", params=["base", "narrow", "edge"])
 def gpu_case(request):
-    from oracle import c_oracle
-    c_oracle.build()
     pose, cases = _gpu_case(request.param)
-    ref = dict(angles=np.zeros((S_GPU, 6, N_GPU, 7)), fk=np.zeros((S_GPU, 6, N_GPU, 9, 3)),
-               status=np.zeros((S_GPU, 6, N_GPU, 4), np.int32), nfev=np.zeros((S_GPU, 6, N_GPU, 4), np.int32))
-    for li, (seg, b, seeds) in enumerate(cases):
-        for s in range(S_GPU):
-            r = c_oracle.seq_leg(pose[s, li], seg, b, seeds)
-            for k in ref:
-                ref[k][s, li] = r[k]
-    for v in ref.values():
-        v.setflags(write=False)
-    return request.param, pose, cases, ref
+    return request.param, pose, cases, oracle_reference(pose, cases)
 
 
 @pytest.mark.gpu
@@ -290,15 +237,7 @@ def test_launch_paths_equal_the_oracle_bit_for_bit(hiplib, pp, gpu_case, path):
         assert all(f != 3 for fl in flags for f in fl)      # the general fd_step runs in every stage
     else:
         assert all(fl == [3, 3, 3, 3] for fl in flags)
-    params = [hiplib.leg_params_from_arrays(*c) for c in cases]
-    kw = dict(fused=dict(pipeline=1, lanes_per_wave=64), queue128=dict(pipeline=1, lanes_per_wave=128),
-              staged=dict(staged=1, lanes_per_wave=64), staged_diag=dict(want_diag=True), pipeline=dict(pipeline=2))[path]
-    out = hiplib.solve_seq(pose, params, want_fk=True, **kw)
-    assert np.array_equal(_bits(out["angles"]), _bits(ref["angles"]))
-    assert np.array_equal(_bits(out["fk"]), _bits(ref["fk"]))
-    if path == "staged_diag":
-        assert np.array_equal(out["status"], ref["status"])
-        assert np.array_equal(out["nfev"], ref["nfev"])
+    assert_equal_reference(solve_on_path(hiplib, pose, cases, ref, path), ref, path)
     if kind == "edge":
         # the zero-operand cases were reached: stage-1 angles that ended exactly on a limit of 0 were moved to +-2^-1074
         # or stayed 0, whose sine is a (signed) zero or the smallest subnormal

@@ -11,13 +11,12 @@ profiles/resample_parity_r09.json)."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, load_golden
+from conftest import ROOT, load_golden
+from harness_build import build_harness
 
 RESAMPLE_SYMBOLS = ["seqik_resample_count", "seqik_resample_workspace_bytes", "seqik_resample_pchip",
                     "seqik_resample_pchip_device"]
@@ -95,19 +94,7 @@ class ResampleHarness:
 def rs_harness(hiplib):
     # the product library first: it lets torch's HIP runtime load before anything else that links one (_lib.load)
     hiplib.load()
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "resample_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libresample_harness.so")
-    deps = [src, os.path.join(ROOT, "include", "seqik_resample.h")] + [
-        os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_resample.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC",
-                               "-shared", "-o", so, src])
-    return ResampleHarness(so)
+    return ResampleHarness(build_harness(os.path.join(ROOT, "tests", "harness", "resample_harness.hip")))
 
 
 def shipped_angles():

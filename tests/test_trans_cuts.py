@@ -11,35 +11,26 @@ CPU tier: each short form against its plain form on the host, compared as intege
 full wavefront and one of six lanes) through every launch path, on three inputs whose branch coverage is asserted first, from
 the oracle alone."""
 import ctypes
+import functools
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PKG_PARENT, ROOT, SEED_LINK_DOF, LegParamsC, load_golden
+from conftest import ROOT
+from harness_build import build_harness
+from pass_cut_support import (LAUNCH_PATHS, assert_equal_reference, bits, first_pass_rows, narrow_limits, oracle_reference,
+                              same_bits, solve_on_path)
 
 dp = ctypes.POINTER(ctypes.c_double)
 ip = ctypes.POINTER(ctypes.c_int32)
 i64p = ctypes.POINTER(ctypes.c_int64)
-ROW = 28   # doubles per recorded row (trans_cuts_harness.hip)
 
 
 @pytest.fixture(scope="module")
 def tc():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "tests", "harness", "trans_cuts_harness.hip")
-    out_dir = os.path.join(ROOT, "tests", "harness", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libtrans_cuts_harness.so")
-    deps = [src] + [os.path.join(PKG_PARENT, "csrc", f) for f in ("seqik_core.hpp", "seqik_consts.hpp", "seqik_generic.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call([hipcc, "--offload-host-only", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-o", so, src])
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(build_harness(os.path.join(ROOT, "tests", "harness", "trans_cuts_harness.hip")))
     lib.tc_rank.argtypes = [dp, ctypes.c_int64, ip, ip]
     lib.tc_abc.argtypes = [dp, ctypes.c_int64, dp]
     lib.tc_tr2_compare.restype = ctypes.c_int64
@@ -47,50 +38,14 @@ def tc():
     lib.tc_step_below.argtypes = [dp, dp, ctypes.c_int64, ip, ip, ip]
     lib.tc_norm1.argtypes = [dp, ctypes.c_int64, dp, dp, ip]
     lib.tc_first_alpha.argtypes = [dp, ctypes.c_int64, dp, dp]
-    lib.tc_record.restype = ctypes.c_int64
-    lib.tc_record.argtypes = [dp, ctypes.c_int64, ctypes.POINTER(LegParamsC), dp, ctypes.c_int64]
     return lib
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    """bit for bit, a NaN on both sides counting as equal (NaN stays NaN)"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return (_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))
-
-
-def _leg_struct(seg, bounds, seeds):
-    lp = LegParamsC()
-    for i in range(4):
-        lp.seg[i] = seg[i]
-    for i in range(7):
-        lp.bounds[i][0], lp.bounds[i][1] = bounds[i][0], bounds[i][1]
-    for i in range(27):
-        lp.seeds[i] = seeds[i]
-    return lp
 
 
 @pytest.fixture(scope="module")
 def recorded(tc):
     """First-pass operands of every solve of host runs of run_stage over the shipped recording, all six legs: rows [n][ROW],
     column 27 = stage."""
-    z = load_golden("df3d_100")
-    rows = []
-    for leg in [str(l) for l in z["legs"]]:
-        pose = np.ascontiguousarray(z[f"{leg}_pose"], dtype=np.float64)
-        r = np.zeros((4 * len(pose), ROW))
-        n = tc.tc_record(pose.ctypes.data_as(dp), len(pose), ctypes.byref(_leg_struct(z[f"{leg}_seg"], z[f"{leg}_bounds"],
-                                                                                       z[f"{leg}_seeds"])),
-                         r.ctypes.data_as(dp), len(r))
-        assert n == len(r)
-        rows.append(r)
-    rows = np.concatenate(rows)
-    assert rows.shape == (2400, ROW) and np.all(np.isfinite(rows))
-    rows.setflags(write=False)
-    return rows
+    return first_pass_rows()
 
 
 # ---- A: the rank test -------------------------------------------------------------------------------------------------------
@@ -214,7 +169,7 @@ def test_step_below_on_the_squares_equals_the_square_root(tc, recorded):
     assert len(T) > 1000 and np.all((T > 1e-16) & (T < 1e-6))
     T = np.concatenate([T, [1e-16, 1e-8 * (1e-8 + 1e-300)]])
     # S within +-64 ulp of fl(T T) ...
-    base = _bits(T * T).astype(np.int64)
+    base = bits(T * T).astype(np.int64)
     S = np.concatenate([(base + k).view(np.float64) for k in range(-64, 65)])
     TT = np.tile(T, 129)
     plain, cut, br = _step_below(tc, S, TT)
@@ -233,7 +188,7 @@ def test_step_below_on_the_squares_equals_the_square_root(tc, recorded):
     assert np.all(plain2[br2 == 1] == 1) and np.all(plain2[br2 == 0] == 0)
     # the edges of the band themselves, +- 3 ulp
     for f in (1.0 - 2.0 ** -49, 1.0 + 2.0 ** -49):
-        e = _bits((T * T) * f).astype(np.int64)
+        e = bits((T * T) * f).astype(np.int64)
         Se = np.concatenate([(e + k).view(np.float64) for k in range(-3, 4)])
         pe, ce, _ = _step_below(tc, Se, np.tile(T, 7))
         assert np.array_equal(pe, ce)
@@ -254,7 +209,7 @@ def test_step_below_on_the_squares_equals_the_square_root(tc, recorded):
 def test_norm_of_one_unknown_is_the_absolute_value(tc):
     rng = np.random.default_rng(12800)
     m = 1.0 + rng.random(4000)
-    near = np.concatenate([(_bits(np.array([1.0, 2.0])).astype(np.int64)[:, None] + np.arange(-40, 41)[None, :]).ravel()
+    near = np.concatenate([(bits(np.array([1.0, 2.0])).astype(np.int64)[:, None] + np.arange(-40, 41)[None, :]).ravel()
                            .view(np.float64), np.sqrt(2.0) + np.arange(-40, 41) * 2.0 ** -52, m])
     xs = [np.ldexp(near, e) for e in range(-1074, 1024, 7)]          # every seventh binade, subnormals to the top
     xs += [np.ldexp(m[:64], e) for e in range(-1080, 1024)]          # all binades
@@ -266,12 +221,12 @@ def test_norm_of_one_unknown_is_the_absolute_value(tc):
     with np.errstate(all="ignore"):
         tc.tc_norm1(x.ctypes.data_as(dp), len(x), plain.ctypes.data_as(dp), cut.ctypes.data_as(dp), sf.ctypes.data_as(ip))
         sq = x * x
-    assert np.all(_same(plain, cut)), x[np.flatnonzero(~_same(plain, cut))[:5]]
-    assert np.all(_same(plain, np.sqrt(sq)))
+    assert np.all(same_bits(plain, cut)), x[np.flatnonzero(~same_bits(plain, cut))[:5]]
+    assert np.all(same_bits(plain, np.sqrt(sq)))
     sf = sf.astype(bool)
     assert np.array_equal(sf, ((sq >= 2.0 ** -1021) & np.isfinite(sq)) | (x == 0.0))
     assert sf.sum() > 100_000 and (~sf).sum() > 50_000
-    assert np.all(_bits(cut[sf]) == _bits(np.abs(x[sf])))
+    assert np.all(bits(cut[sf]) == bits(np.abs(x[sf])))
     # squares that underflow to a subnormal or to zero, and squares that overflow: the plain form ran
     assert not np.any(sf[(np.abs(x) > 0) & (np.abs(x) < 2.0 ** -511)]) and not np.any(sf[np.abs(x) >= 2.0 ** 512])
     assert not np.any(sf[np.isnan(x)])
@@ -286,11 +241,11 @@ def test_first_multiplier_without_its_square_root(tc):
     plain, cut = np.zeros_like(au), np.zeros_like(au)
     with np.errstate(all="ignore"):
         tc.tc_first_alpha(au.ctypes.data_as(dp), len(au), plain.ctypes.data_as(dp), cut.ctypes.data_as(dp))
-    assert np.all(_same(plain, cut)), au[np.flatnonzero(~_same(plain, cut))[:5]]
+    assert np.all(same_bits(plain, cut)), au[np.flatnonzero(~same_bits(plain, cut))[:5]]
     fin = np.isfinite(au) & (au > 0)
-    assert np.all(_bits(cut[fin]) == _bits(0.001 * au[fin]))
+    assert np.all(bits(cut[fin]) == bits(0.001 * au[fin]))
     assert cut[au == np.inf][0] == np.inf and np.isnan(cut[np.isnan(au)][0])
-    assert _bits(cut[:2]).tolist() == _bits(plain[:2]).tolist()   # the zero keeps alpha_upper's sign in both forms
+    assert bits(cut[:2]).tolist() == bits(plain[:2]).tolist()   # the zero keeps alpha_upper's sign in both forms
 
 
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
@@ -312,14 +267,7 @@ def _gpu_case(kind):
         seg, b, seeds = c_oracle.leg_params(leg, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION)
         b, seeds = b.copy(), seeds.copy()
         if kind == "narrow":  # limits 1e-8 apart on one joint of every stage: steps around the xtol threshold
-            for dof in (1, 2, 5, 6):   # ThC_pitch (stage 1), ThC_roll (2), FTi_pitch (3), TiTa_pitch (4)
-                c = float(seeds[SEED_LINK_DOF.index(dof)])
-                if dof == 6:
-                    c = -0.6           # (the shipped seed 0 sits on the shipped upper limit)
-                b[dof] = (c - 0.5e-8, c + 0.5e-8)
-                for i, d in enumerate(SEED_LINK_DOF):
-                    if d == dof:
-                        seeds[i] = c
+            narrow_limits(b, seeds)
         cases.append((seg, b, seeds))
     return pose, cases
 
@@ -351,26 +299,12 @@ def _oracle_branch_stats(pose, cases):
     return np.array(list(out)).reshape(2, 24)
 
 
-_CASES = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _gpu_case_with_reference(kind):
     """pose, per-leg parameters and the C oracle's results for `kind`, computed once and shared read-only.  Before anything
     runs on the GPU the case shows, from the oracle alone, that its chains reach the branches the cuts changed."""
-    if kind in _CASES:
-        return _CASES[kind]
-    from oracle import c_oracle
-    c_oracle.build()
     pose, cases = _gpu_case(kind)
-    ref = dict(angles=np.zeros((S_GPU, 6, N_GPU, 7)), fk=np.zeros((S_GPU, 6, N_GPU, 9, 3)),
-               status=np.zeros((S_GPU, 6, N_GPU, 4), np.int32), nfev=np.zeros((S_GPU, 6, N_GPU, 4), np.int32))
-    for li, (seg, b, seeds) in enumerate(cases):
-        for s in range(S_GPU):
-            r = c_oracle.seq_leg(pose[s, li], seg, b, seeds)
-            for k in ref:
-                ref[k][s, li] = r[k]
-    for v in ref.values():
-        v.setflags(write=False)
+    ref = oracle_reference(pose, cases)
     st = _oracle_branch_stats(pose, cases)
     assert st[0, 6] > 0 and st[1, 6] > 0, st[:, 6]     # reflective calls, stage 1 and stages 2 / 3
     assert st[0, 3] + st[1, 3] > 0, st[:, 3]           # root loops entered (A's full-rank branch outside the region, E)
@@ -380,37 +314,12 @@ def _gpu_case_with_reference(kind):
         assert np.any((status == 3) | (status == 4)) and np.any(status == 2)   # both outcomes of the xtol test (B, C)
     if kind == "still":
         assert np.any((status == 1) & (nfev == 1))     # solves that end on their start point
-    _CASES[kind] = (pose, cases, ref)
-    return _CASES[kind]
-
-
-PATHS = dict(fused=dict(pipeline=1, lanes_per_wave=64), queue128=dict(pipeline=1, lanes_per_wave=128),
-             staged=dict(staged=1, lanes_per_wave=64), staged_diag=dict(want_diag=True), pipeline=dict(pipeline=2),
-             chunked=dict(frame_chunk=3, frame_halo=2, chunk_tol=-1.0, chunk_rounds=2),   # exact mode: == the serial walk
-             subset=None)
+    return pose, cases, ref
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("path", list(PATHS))
+@pytest.mark.parametrize("path", list(LAUNCH_PATHS))
 @pytest.mark.parametrize("kind", ["iid", "still", "narrow"])
 def test_launch_paths_equal_the_oracle_bit_for_bit(hiplib, kind, path):
     pose, cases, ref = _gpu_case_with_reference(kind)
-    params = [hiplib.leg_params_from_arrays(*c) for c in cases]
-    if path == "subset":
-        # stages k .. 4 from the stored angles of the earlier stages (the FROM_ANGLES instantiations)
-        outs = []
-        for first in (2, 3, 4):
-            prior = ref["angles"].copy()
-            prior[..., 2 * (first - 1):] = 0.0
-            outs.append(hiplib.solve_seq(pose, params, first_stage=first, last_stage=4, angles=prior, want_fk=True))
-    else:
-        outs = [hiplib.solve_seq(pose, params, want_fk=True, **PATHS[path])]
-    hiplib.check_faults()
-    for out in outs:
-        assert np.array_equal(_bits(out["angles"]), _bits(ref["angles"]))
-        assert np.array_equal(_bits(out["fk"]), _bits(ref["fk"]))
-    if path == "staged_diag":
-        assert np.array_equal(outs[0]["status"], ref["status"])
-        assert np.array_equal(outs[0]["nfev"], ref["nfev"])
-    if path == "chunked":
-        assert outs[0]["chunk_stats"]["chunks"] == 2 * S_GPU * 6   # every chain was cut into two chunks
+    assert_equal_reference(solve_on_path(hiplib, pose, cases, ref, path), ref, path, n_chains=S_GPU * 6)
