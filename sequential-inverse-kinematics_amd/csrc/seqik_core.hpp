@@ -97,9 +97,11 @@ SEQIK_HD double fma_(double a, double b, double c) { return __builtin_fma(a, b, 
 // 256  (not assigned: handing the reciprocals of select_step_reflective's first distance to the bounds on to its second
 //      cost registers and scratch in 17 kernels and was taken out, EXPERIMENTS.md 21.4)
 // 512  stage 1: the first multiplier of a solve without sqrt(0 * alpha_upper) (tr_first_alpha)
-// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all nine.
+// and the one of round 10, a square root per pass in all four stages:
+// 1024 ||step|| < xtol (xtol + ||x||) decided from the two sums of squares, without the root under ||x|| (xtol_test)
+// Same bits with and without each; SEQIK_FAST_PATHS=0 builds the plain forms of all ten.
 #ifndef SEQIK_PASS_CUTS
-#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 1023 : 0)
+#define SEQIK_PASS_CUTS (SEQIK_FAST_PATHS ? 2047 : 0)
 #endif
 // "does any active lane of this wavefront ...?" (one ballot; on the host: this lane)
 SEQIK_HD bool wave_any(bool c)
@@ -604,6 +606,59 @@ SEQIK_HD bool step_below(double S, double T, int *branch = nullptr)
     }
     if (branch) *branch = 2;
     return sqrt_(S) < T;
+}
+
+// The whole xtol test ||step|| < xtol (xtol + ||x||) of a pass, from X = the sum of squares under ||x|| and the step.  The
+// plain form takes sqrt_(X) for T = fl(xtol fl(xtol + sqrt_(X))), which nothing else reads, and hands T to step_below (two
+// unknowns) or compares it with norm2v<1> (one unknown).  XSQ (bit 1024 of SEQIK_PASS_CUTS) decides it from X and S = the
+// sum of squares under ||step|| -- fl(fma(s1, s1, fl(s0 s0))) or fl(s0 s0), the double whose IEEE root the oracle compares
+// with T -- without the root of X and without T:
+//   sure_true  = S < fl(XTOL_SQ_LO X),  sure_false = S > fl(XTOL_SQ_HI X),  in_range = 2^-20 <= X < 2^100.
+// The constants belong to xt = fl(1e-8) = 0x1.5798ee2308c3ap-27, the double the plain form multiplies by (|xt / 1e-8 - 1|
+// < 2^-54, which the margins below swallow, but the derivation is from xt): xt^2 = 0x1.cd2b297d889bc82...p-54, and the
+// literals are the doubles next to xt^2 (1 - 2^-40) and xt^2 (1 + 2^-14); in exact arithmetic
+//   XTOL_SQ_LO < xt^2 (1 - 2^-41)  and  XTOL_SQ_HI > xt^2 (1 + 2^-14.1)      (tests/test_xtol_squares.py checks both).
+// With u = 2^-53, r = sqrt X, s = sqrt S (real numbers), and a computed root allowed 2 ulp (4 u relative; the oracle's is
+// within u) on either side of the comparison, every T the plain form can compute lies in
+//   T_min = xt (xt + r (1 - 4 u)) (1 - u)^2  <=  T  <=  xt (xt + r (1 + 4 u)) (1 + u)^2 = T_max        (sum and product round
+// once each; in_range keeps both normal: 1e-16 <= T < 2^25).  In range the two products are normal as well (>= 2^-74), so
+// they carry one rounding:
+//   * sure_true:  S < XTOL_SQ_LO X (1 + u)  =>  s < xt r (1 - 2^-42)(1 + u)  =>  s (1 + 4 u) < xt r (1 - 2^-42 + 6 u) < xt r
+//     (1 - 7 u) < T_min: the computed root of S is below the computed T, with 2^-42 = 2048 u against the 13 u needed.
+//   * sure_false: r >= 2^-10 makes xt / r <= 1024 xt < 2^-16.5, so T_max < xt r (1 + 2^-16.5 + 4 u)(1 + 3 u) < xt r (1 +
+//     2^-16.4).  S > XTOL_SQ_HI X (1 - u)  =>  s > xt r (1 + 2^-15.2)  =>  s (1 - 4 u) > xt r (1 + 2^-15.3) > T_max: the
+//     computed root is not below T.  (The band between the two constants is 6e-5 of T^2 wide: a step that shrinks by a
+//     constant factor per pass crosses it in almost no pass.)
+//   * S = 0 or subnormal (an underflowed square, stage 4's fl(s0 s0) of a tiny non-zero s0 included): sure_true, and the
+//     oracle's root of that same S is at most 2^-511 < 1e-16 <= T.  S = inf (an overflowed square): sure_false, and the
+//     oracle's root is inf, not below a finite T.  In stage 4 the parent forms the root as |s0| where the square is normal
+//     (norm2v<1>), which IS the oracle's root of S, so S stands for it there too.
+//   * a NaN in S fails both comparisons, a NaN in X fails in_range (and makes both products NaN); X = +inf, X < 2^-20 (zero
+//     and the range where xtol^2 counts against xtol ||x||) and X >= 2^100 fail in_range.
+// One active lane that is not in range or not sure sends the wavefront through the plain form, sure lanes included.
+// xtol is run_stage's 1e-8, the only value the two constants are good for.  branch (nullable, host harness): 1 sure true, 0
+// sure false, 2 plain form.
+constexpr double XTOL_SQ_LO = 0x1.cd2b297d86ceap-54;   // xtol^2 (1 - 2^-40)
+constexpr double XTOL_SQ_HI = 0x1.cd325e2a2e91fp-54;   // xtol^2 (1 + 2^-14)
+template <int NA, bool XSQ = (SEQIK_PASS_CUTS & 1024) != 0>
+SEQIK_HD bool xtol_test(double X, const double *step, double xtol, int *branch = nullptr)
+{
+    if constexpr (XSQ) {
+        double S = step[0] * step[0];
+        if constexpr (NA == 2) S = fma_(step[1], step[1], S);
+        const bool sure_true = S < XTOL_SQ_LO * X, sure_false = S > XTOL_SQ_HI * X;
+        const bool in_range = X >= 0x1p-20 && X < 0x1p+100;
+        if (!wave_any(!(in_range && (sure_true || sure_false)))) {
+            if (branch) *branch = sure_true ? 1 : 0;
+            return sure_true;
+        }
+    }
+    if (branch) *branch = 2;
+    const double T = xtol * (xtol + sqrt_(X));
+    // ||step|| is read by this one comparison: two unknowns decide it on the squares (step_below), one unknown has its norm
+    // as |step[0]| (norm2v<1>)
+    if constexpr (NA == 2) return step_below(fma_(step[1], step[1], step[0] * step[0]), T);
+    else return norm2v<NA>(step) < T;
 }
 
 template <int NA>
@@ -1833,6 +1888,9 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
     constexpr int NA = T::NA;
     // bit 8 of SEQIK_PASS_CUTS: P.t_act is kept next to P.pre and the evaluations read it (residual_sc_hoisted)
     constexpr bool HOIST = (SEQIK_PASS_CUTS & 8) != 0 && STAGE >= 2;
+    // bit 1024: the xtol test of a pass without the root under ||x|| (xtol_test); everywhere but in the 168-register stage
+    // pipeline over frame chunks, whose kernel with forward kinematics it cost 4 B of scratch
+    constexpr bool XSQ = (SEQIK_PASS_CUTS & 1024) != 0 && !(CHUNKED && PIPED && !LAT);
     constexpr int DOF0 = 2 * (STAGE - 1);  // angle columns written: DOF0 (and DOF0 + 1)
     const double ftol = 1e-8, xtol = 1e-8, gtol = 1e-8;
     const StageConst &sc = lc.st[STAGE - 1];
@@ -2175,18 +2233,14 @@ SEQIK_HD void run_stage(const LegConst &lc, const ChainIO &io_arg)
                 double Delta_new = Delta;
                 if (ratio < 0.25) Delta_new = 0.25 * step_h_norm;
                 else if (ratio > 0.75 && step_h_norm > 0.95 * Delta) Delta_new = Delta * 2.0;
-                // ||x|| over all links: inert prefix, active, inert last link
+                // ||x||^2 over all links: inert prefix, active, inert last link
                 double xn = sc.x_pre_sq;
                 xn = fma_(x[0], x[0], xn);
                 if constexpr (NA == 2) xn = fma_(x[1], x[1], xn);
                 xn = fma_(sc.x_suf, sc.x_suf, xn);
-                xn = sqrt_(xn);
                 bool ftol_ok = (actual_reduction < ftol * cost) && (ratio > 0.25);
-                // ||step|| is read by this one comparison: two unknowns decide it on the squares (step_below), one unknown
-                // has its norm as |step[0]| (norm2v<1>)
-                bool xtol_ok;
-                if constexpr (NA == 2) xtol_ok = step_below(fma_(step[1], step[1], step[0] * step[0]), xtol * (xtol + xn));
-                else xtol_ok = norm2v<NA>(step) < xtol * (xtol + xn);
+                // the root of xn is read by the xtol test alone, which decides on the squares where it can (xtol_test)
+                const bool xtol_ok = xtol_test<NA, XSQ>(xn, step, xtol);
                 if (ftol_ok && xtol_ok) status = 4;
                 else if (ftol_ok) status = 2;
                 else if (xtol_ok) status = 3;
