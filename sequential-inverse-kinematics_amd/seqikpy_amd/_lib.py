@@ -24,10 +24,10 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip"]
+                 "seqik_head_align.hip", "seqik_jacobian.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
-                "seqik_head_align.hpp"]
+                "seqik_head_align.hpp", "seqik_jacobian.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -247,6 +247,13 @@ STREAM_GAPS_SIGNATURES = {
         ("seqik_stream_get_carry", _int, _vp, _dp, _i64)),
 }
 
+# The same for the leg Jacobians (include/seqik_jacobian.h): a fourth table.
+JACOBIAN_SIGNATURES = {
+    "seqik_jacobian.h": (
+        ("seqik_leg_jacobians", _int, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _dp, _dp, _dp, _i32),
+        ("seqik_leg_jacobians_device", _int, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _vp, _vp, _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -350,7 +357,7 @@ def load():
             raise SeqikLibraryError(f"{LIB_PATH} has ABI {L.seqik_abi_version()}, this package needs {ABI_VERSION}: "
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
-                           list(STREAM_GAPS_SIGNATURES.values())):
+                           list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -514,6 +521,55 @@ def link_frames_device(d_angles, n_seq, n_legs, n_frames, legs, d_frames, kind="
     _call("seqik_link_frames_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
           (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_origin, "origin", lf + (3,)),
           _ptr(d_frames, "frames", lf + (9, 3, 4)), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_jacobian.h (leg Jacobians, conditioning, key-point velocities), additive to ABI 7
+JACOBIAN_EXPORTED_SYMBOLS = [sig[0] for sig in JACOBIAN_SIGNATURES["seqik_jacobian.h"]]
+
+
+def _sigma_view(sigma, kind):
+    """The library's (..., 8) conditioning record as documented: (..., 4, 2) for the sequential chain, (..., 3) for the
+    generic chain (its other five values are NaN and carry no meaning)."""
+    if sigma is None:
+        return None
+    return sigma.reshape(sigma.shape[:-1] + (4, 2)) if kind == 0 else np.ascontiguousarray(sigma[..., :3])
+
+
+def leg_jacobians(angles, legs, kind="seq", qdot=None, want_jac=True, want_sigma=True, device=-1):
+    """``seqik_leg_jacobians`` on host arrays: joint angles (S, L, N, 7) in ``DOFS`` order -> dict(jac (S, L, N, 4, 3, 7) or
+    None, sigma or None, vel (S, L, N, 4, 3) or None).
+
+    ``jac[..., k, :, d]`` is the derivative of key point k + 1 (FK rows 4, 6, 7, 8: coxa, femur and tibia end, claw) with
+    respect to the angle of DOF d -- ``DOFS`` order for both kinds -- in the leg's own frame (it does not depend on the
+    origin).  ``sigma`` (``want_sigma``): for ``kind="seq"`` (S, L, N, 4, 2), per stage (sigma_max, sigma_min) of the
+    block that stage's solve sees (key point s by the stage's own DOFs); for ``"generic"`` (S, L, N, 3), the singular
+    values of the claw's 3 x 7 block, descending.  ``vel`` (when ``qdot`` (S, L, N, 7), joint rates, is given): ``jac @
+    qdot``, the key-point velocities.  At least one of the three must be asked for.  An angle that is not finite or lies
+    beyond ``SEQIK_ANGLE_MAX`` makes that leg-frame's values NaN; a non-finite rate its velocities only."""
+    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    if qdot is not None:
+        qdot = np.ascontiguousarray(qdot, dtype=np.float64)
+        if qdot.shape != angles.shape:
+            raise ValueError(f"qdot must have the shape of angles {angles.shape}, got {qdot.shape}")
+    jac = np.full((S, L, N, 4, 3, 7), np.nan) if want_jac else None
+    sigma = np.full((S, L, N, 8), np.nan) if want_sigma else None
+    vel = np.full((S, L, N, 4, 3), np.nan) if qdot is not None else None
+    _call("seqik_leg_jacobians", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(qdot), _data(jac),
+          _data(sigma), _data(vel), int(device))
+    return dict(jac=jac, sigma=_sigma_view(sigma, k), vel=vel)
+
+
+def leg_jacobians_device(d_angles, n_seq, n_legs, n_frames, legs, kind="seq", d_qdot=0, d_jac=0, d_sigma=0, d_vel=0,
+                         stream=None):
+    """``seqik_leg_jacobians_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_jacobian.h`` (``d_jac`` (S, L, N, 4, 3, 7), ``d_sigma`` (S, L, N, 8), ``d_vel`` (S, L, N, 4, 3)
+    doubles; 0 / None: not computed, not written; at least one), asynchronous on ``stream`` (a hipStream_t as int, or a
+    torch stream; None / 0 = the default stream) of the current device."""
+    lf = (n_seq, n_legs, n_frames)
+    _call("seqik_leg_jacobians_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
+          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_qdot, "qdot", lf + (7,)),
+          _ptr(d_jac, "jac", lf + (4, 3, 7)), _ptr(d_sigma, "sigma", lf + (8,)), _ptr(d_vel, "vel", lf + (4, 3)),
+          _stream_ptr(stream))
 
 
 #: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h

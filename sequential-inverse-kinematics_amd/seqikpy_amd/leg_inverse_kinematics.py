@@ -294,6 +294,103 @@ class LegInvKinBase(ABC):
                 save_file(Path(export_path) / "leg_joint_accelerations.pkl", acc)
         return (vel, acc) if acceleration else vel
 
+    # -- key-point Jacobians, conditioning and velocities (include/seqik_jacobian.h) --------
+    def _jacobian_outputs(self, joint_angles, want_jac, want_sigma):
+        """``_lib.leg_jacobians`` per group of legs with the same frame count -> ({segment_name: jac}, {...: sigma})."""
+        jac, sigma = {}, {}
+        for items, angles, _ in self._fk_batches(joint_angles, origin=np.zeros(3)):
+            legs = [self._fk_leg_params(leg_name) for _, leg_name, _, _ in items]
+            out = _lib.leg_jacobians(angles, legs, kind=self._fk_kind, want_jac=want_jac, want_sigma=want_sigma,
+                                     device=self.device)
+            for li, (segment_name, *_) in enumerate(items):
+                if want_jac:
+                    jac[segment_name] = out["jac"][0, li].copy()
+                if want_sigma:
+                    sigma[segment_name] = out["sigma"][0, li].copy()
+        order = [name for name, _, _ in self._leg_segments()]
+        return {n: jac[n] for n in order if n in jac}, {n: sigma[n] for n in order if n in sigma}
+
+    def run_jacobians(self, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                      export_path: Union[Path, str] = None) -> Dict[str, np.ndarray]:
+        """How the fitted key points move when the angles move, for every leg, on the GPU (``seqik_leg_jacobians``):
+        ``{segment_name: (N, 4, 3, 7)}`` in the order of ``aligned_pos``; ``[t, k, :, d]`` is the derivative of key point
+        k + 1 of frame t (forward-kinematics rows 4, 6, 7, 8: coxa, femur and tibia end, claw) with respect to the angle
+        of ``DOFS[d]``, length per radian, in the leg's own frame (it does not depend on the origin).  The chain kind
+        follows the class; ``joint_angles`` defaults as in ``run_fk``.  Noise propagation is a numpy step on top: with
+        the pseudo-inverse ``P`` of a frame's stacked ``(12, 7)`` Jacobian, key-point covariance ``C`` gives angle
+        covariance ``P @ C @ P.T``.  ``export_path``: writes ``leg_jacobians.pkl`` there."""
+        out, _ = self._jacobian_outputs(joint_angles, True, False)
+        if export_path is not None:
+            save_file(Path(export_path) / "leg_jacobians.pkl", out)
+            self.logger.info("Leg Jacobians are saved at %s", export_path)
+        return out
+
+    def conditioning(self, joint_angles: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+        """How well the angles are determined by the key points they were fitted to, per frame, on the GPU
+        (``seqik_leg_jacobians``, ``sigma``): the singular values of the Jacobian each least-squares solve works with.
+
+        ``LegInvKinSeq``: ``{segment_name: (N, 4, 2)}``, per stage ``(sigma_max, sigma_min)`` of that stage's block.
+        Stage 1 reads key point 1 (coxa end) and solves ThC_yaw, ThC_pitch; stage 2 reads key point 2 (femur end) and
+        solves ThC_roll, CTr_pitch; stage 3 reads key point 3 (tibia end) and solves CTr_roll, FTi_pitch; stage 4 reads
+        key point 4 (claw) and solves TiTa_pitch (one column: both entries are its norm).  A ``sigma_min`` that is small
+        next to ``sigma_max`` -- or to the recording's median -- means that the stage's two angles are not both
+        determined by its key point: some combination of them leaves the key point where it is (a kinematic
+        singularity, e.g. a stretched joint and the roll about it), and the solved angles there are arbitrary along that
+        combination.  ``LegInvKinGeneric``: ``{segment_name: (N, 3)}``, the singular values of the claw's 3 x 7 block,
+        descending (seven angles from three coordinates: the problem is rank-deficient by construction; a small third
+        value marks postures where the claw loses a direction of motion)."""
+        return self._jacobian_outputs(joint_angles, False, True)[1]
+
+    def run_key_point_velocities(self, original_ts, new_ts=None, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                                 missing: str = "error", max_gap: Optional[int] = None,
+                                 export_path: Union[Path, str] = None) -> Dict[str, np.ndarray]:
+        """The velocities of the four fitted key points of every leg, on the GPU: ``{segment_name: (n_out, 4, 3)}``, the
+        Jacobian at the resampled angles times the joint rates, in length per unit of ``original_ts``.
+
+        The angles are resampled and differentiated on the device as in ``run_resample`` / ``run_joint_velocities``
+        (``seqik_resample_der_device``: value and first derivative), and the Jacobian kernel runs on those device buffers
+        (``seqik_leg_jacobians_device``) with no host round trip.  ``new_ts=None`` means ``original_ts``.  ``missing``
+        and ``max_gap``: ``run_resample``'s; a velocity is NaN exactly where the resampled angle or rate is.
+        ``export_path``: writes ``key_point_velocities.pkl`` there."""
+        import torch
+        ja = self.joint_angles_dict if joint_angles is None else joint_angles
+        new_ts = original_ts if new_ts is None else new_ts
+        flags, _ = _lib._resample_flags(missing, max_gap)
+        groups = {}
+        for segment_name, leg_name, arr in self._leg_segments():
+            ang = self._fk_angles(ja, leg_name)
+            groups.setdefault(ang.shape[0], []).append((segment_name, leg_name, ang))
+        out = {}
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device < 0 else self.device)
+        for N, items in groups.items():
+            y = np.ascontiguousarray(np.stack([a for *_, a in items]), dtype=np.float64)
+            L = y.shape[0]
+            if N < 2:
+                raise ValueError("The number of knots must be at least 2")
+            if not flags and not np.isfinite(y).all():
+                raise ValueError("`y` must contain only finite values (missing='bridge' resamples over the finite records)")
+            n_out = _lib.resample_count(N, original_ts, new_ts)
+            legs = [self._fk_leg_params(leg_name) for _, leg_name, _ in items]
+            with torch.cuda.device(dev):
+                d_y = torch.from_numpy(y).to(dev)
+                d_val = torch.empty((L, n_out, 7), dtype=torch.float64, device=dev)
+                d_d1 = torch.empty((L, n_out, 7), dtype=torch.float64, device=dev)
+                d_ws = torch.empty((2, L, N), dtype=torch.int32, device=dev) if flags else 0
+                d_vel = torch.empty((L, n_out, 4, 3), dtype=torch.float64, device=dev)
+                stream = torch.cuda.current_stream().cuda_stream
+                _lib.resample_der_device(d_y, L, N, 7, original_ts, new_ts, d_value=d_val, d_d1=d_d1, missing=missing,
+                                         max_gap=max_gap, d_workspace=d_ws, stream=stream)
+                _lib.leg_jacobians_device(d_val, 1, L, n_out, legs, kind=self._fk_kind, d_qdot=d_d1, d_vel=d_vel,
+                                          stream=stream)
+                torch.cuda.synchronize(dev)
+                vel = d_vel.cpu().numpy()
+            for li, (segment_name, *_) in enumerate(items):
+                out[segment_name] = vel[li].copy()
+        out = {name: out[name] for name, _, _ in self._leg_segments()}
+        if export_path is not None:
+            save_file(Path(export_path) / "key_point_velocities.pkl", out)
+        return out
+
     def _resample_origin(self, origin, segment_name, leg_name, segment_array):
         if origin is not None:
             o = np.asarray(origin, dtype=np.float64)
