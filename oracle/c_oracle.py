@@ -177,7 +177,8 @@ def set_variant(tr2_shortcut=None, closed_form_2x2=None, generic_svd=None, analy
     3 x 3 push-through form); analytic_jacobian [False]: geometric Jacobian instead of scipy's 2-point differences
     (rejected, see the C file); generic_rtl [True]: the generic chain's claw position as a vector pushed through the
     links right to left (False = last column of the left-to-right matrix product, as the sequential stages);
-    woodbury_form [1]: 0 = the round-3 form of the 3 x 3 step (two general solves per evaluation)."""
+    woodbury_form [0]: two general solves per evaluation of the 3 x 3 step; 1 = the push-through identity applied once more
+    (shorter, the default until it was measured against real scipy on made-up legs: EXPERIMENTS.md)."""
     L = lib()
     if tr2_shortcut is not None:
         L.oracle_set_tr2_shortcut(1 if tr2_shortcut else 0)
@@ -195,4 +196,4 @@ def set_variant(tr2_shortcut=None, closed_form_2x2=None, generic_svd=None, analy
 
 def reset_variants():
     set_variant(tr2_shortcut=True, closed_form_2x2=True, generic_svd=False, analytic_jacobian=False, generic_rtl=True,
-                woodbury_form=1)
+                woodbury_form=0)

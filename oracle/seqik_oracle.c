@@ -644,9 +644,12 @@ static void woodbury_solve(int n, double Jh[NRES][MAXN], const double *W, const 
  *     pp = W J_h^T y,  y = (I + J_h W J_h^T)^-1 f            (the right-hand side IS J_h^T f: no 7-vector product in front)
  *     pp^T (B + J_h^T J_h)^-1 pp = pp^T W pp - u^T (I + J_h W J_h^T)^-1 u,  u = J_h W pp
  * -- 37 + 54 multiply-adds instead of 65 + 72 per evaluation.  The angles of the generic chain are not pinned by the reference
- * (see chain_end_effector_rtl), so the form is this restatement's to choose; the kernel mirrors form 1 operation for
- * operation.  oracle_set_woodbury_form(0) restores form 0 (test hook). */
-static int g_woodbury_form = 1;
+ * (see chain_end_effector_rtl), so the form is this restatement's to choose.  Form 1 was the default until the answers were
+ * measured against real scipy on made-up legs (tests/test_generic_answers.py, EXPERIMENTS.md): with open limits
+ * (diag_h = 0, W = 1 / alpha) it ends in a worse minimum than scipy three times as often as form 0, which stays within
+ * scipy's own spread.  The kernel mirrors form 0 operation for operation; oracle_set_woodbury_form(1) selects form 1
+ * (test hook). */
+static int g_woodbury_form = 0;
 void oracle_set_woodbury_form(int form) { g_woodbury_form = form; }
 static void woodbury_phi(int n, double Jh[NRES][MAXN], const double *diag_h, const double *rhs /* J_h^T f */, const double *f,
                          double alpha, double Delta, double *pp, double *phi, double *ratio)

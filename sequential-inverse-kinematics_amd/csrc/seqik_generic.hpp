@@ -17,8 +17,8 @@
 // Since the angles are not pinned, the association order of the forward kinematics is the restatement's to choose
 // (round-3 review): the claw position is evaluated RIGHT TO LEFT as a 3-vector pushed through the seven links
 // (generic_claw: 30 instructions) instead of as the last column of the left-to-right product of 3 x 4 frames
-// (generic_chain: 150, now only used once per frame for the stored joint positions), and the trust-region step uses
-// the push-through identity twice (woodbury_phi).  A pass is ~30 % shorter; oracle_generic_leg makes the same choices.
+// (generic_chain: 150, now only used once per frame for the stored joint positions); oracle_generic_leg makes the same
+// choice.
 #pragma once
 #include "seqik_core.hpp"
 
@@ -245,12 +245,32 @@ SEQIK_HD void sym3_inverse(const double *m /* 00 01 02 11 12 22 */, double *inv)
     inv[0] = c00 * r; inv[1] = c01 * r; inv[2] = c02 * r; inv[3] = c11 * r; inv[4] = c12 * r; inv[5] = c22 * r;
 }
 
-// pp = (B + J_h^T J_h)^-1 J_h^T f (the un-negated step), and -- when WANT_PHI -- phi and the Newton ratio phi / phi'.
-// Push-through twice (oracle woodbury_phi, form 1):  pp = W J_h^T y  with  y = (I + J_h W J_h^T)^-1 f,  and
-//     pp^T (B + J_h^T J_h)^-1 pp = pp^T W pp - u^T (I + J_h W J_h^T)^-1 u,   u = J_h W pp.
+// q = (B + J_h^T J_h)^-1 r  given W = 1 / (diag_h + alpha) and Minv = (I + J_h W J_h^T)^-1
+SEQIK_HD void woodbury_solve(const double Jh[3][GN], const double *W, const double *Minv, const double *r, double *q)
+{
+    double wr[GN], t[3], y[3];
+#pragma unroll
+    for (int c = 0; c < GN; ++c) wr[c] = W[c] * r[c];
+    matvec37(Jh, wr, t);
+    y[0] = fma_(Minv[2], t[2], fma_(Minv[1], t[1], Minv[0] * t[0]));
+    y[1] = fma_(Minv[4], t[2], fma_(Minv[3], t[1], Minv[1] * t[0]));
+    y[2] = fma_(Minv[5], t[2], fma_(Minv[4], t[1], Minv[2] * t[0]));
+#pragma unroll
+    for (int c = 0; c < GN; ++c) {
+        double jy = fma_(Jh[2][c], y[2], fma_(Jh[1][c], y[1], Jh[0][c] * y[0]));
+        q[c] = fma_(-W[c], jy, wr[c]);
+    }
+}
+
+// pp = (B + J_h^T J_h)^-1 J_h^T f (the un-negated step), and -- when WANT_PHI -- phi and the Newton ratio phi / phi':
+// two general solves with woodbury_solve, one for rhs = J_h^T f and one for pp (oracle woodbury_phi, form 0).  The shorter
+// form that applies the push-through identity once more (pp = W J_h^T (I + J_h W J_h^T)^-1 f, oracle form 1: 91 instead of
+// 137 multiply-adds) was the default until tests/test_generic_answers.py measured it against real scipy on made-up legs: with
+// open limits (diag_h = 0, W = 1 / alpha) it ended in a worse minimum than scipy on 16-37 % of the frames, form 0 on 3-15 %,
+// scipy's own 1-ulp twin on 5-17 % (EXPERIMENTS.md, "Generic chain: answers against real scipy").
 // jm >= 0: lane group, this lane divides for joint jm only (the seven quotients are the same code on different data)
 template <bool WANT_PHI>
-SEQIK_HD void woodbury_phi(const double Jh[3][GN], const double *diag_h, const double *f, double alpha, double Delta,
+SEQIK_HD void woodbury_phi(const double Jh[3][GN], const double *diag_h, const double *rhs, double alpha, double Delta,
                            double *pp, double &phi, double &ratio, int jm = -1)
 {
     double W[GN], M[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 1.0}, Minv[6];
@@ -267,27 +287,12 @@ SEQIK_HD void woodbury_phi(const double Jh[3][GN], const double *diag_h, const d
         M[3] = fma_(w1, Jh[1][c], M[3]); M[4] = fma_(w1, Jh[2][c], M[4]); M[5] = fma_(w2, Jh[2][c], M[5]);
     }
     sym3_inverse(M, Minv);
-    double y[3];
-    y[0] = fma_(Minv[2], f[2], fma_(Minv[1], f[1], Minv[0] * f[0]));
-    y[1] = fma_(Minv[4], f[2], fma_(Minv[3], f[1], Minv[1] * f[0]));
-    y[2] = fma_(Minv[5], f[2], fma_(Minv[4], f[1], Minv[2] * f[0]));
-#pragma unroll
-    for (int c = 0; c < GN; ++c) {
-        double z = fma_(Jh[2][c], y[2], fma_(Jh[1][c], y[1], Jh[0][c] * y[0]));
-        pp[c] = W[c] * z;
-    }
+    woodbury_solve(Jh, W, Minv, rhs, pp);
     if constexpr (WANT_PHI) {
+        double q[GN];
         double p_norm = vnorm7(pp);
-        double wa[GN], u[3], t[3];
-#pragma unroll
-        for (int c = 0; c < GN; ++c) wa[c] = W[c] * pp[c];
-        double s1 = vdot7(wa, pp);
-        matvec37(Jh, wa, u);
-        t[0] = fma_(Minv[2], u[2], fma_(Minv[1], u[1], Minv[0] * u[0]));
-        t[1] = fma_(Minv[4], u[2], fma_(Minv[3], u[1], Minv[1] * u[0]));
-        t[2] = fma_(Minv[5], u[2], fma_(Minv[4], u[1], Minv[2] * u[0]));
-        double s2 = fma_(u[2], t[2], fma_(u[1], t[1], u[0] * t[0]));
-        double acc = s1 - s2;
+        woodbury_solve(Jh, W, Minv, pp, q);
+        double acc = vdot7(pp, q);
         phi = p_norm - Delta;
         ratio = div_(-(phi * p_norm), acc);
     }
@@ -317,7 +322,7 @@ SEQIK_HD void solve_tr_woodbury(const double Jh[3][GN], const double *diag_h, co
             if (it < 9) a_k = -1.0;
         }
         double phi, ratio;
-        woodbury_phi<true>(Jh, diag_h, f, a_k, Delta, pp, phi, ratio, jm);
+        woodbury_phi<true>(Jh, diag_h, rhs, a_k, Delta, pp, phi, ratio, jm);
         if (phi < 0 && !(fabs(phi) < 0.01 * Delta)) {
             alpha = a_k - (phi + Delta) * ratio * inv_Delta;
             shortcut = true;
@@ -327,14 +332,14 @@ SEQIK_HD void solve_tr_woodbury(const double Jh[3][GN], const double *diag_h, co
         if (alpha < alpha_lower || alpha > alpha_upper)
             alpha = fmax(0.001 * alpha_upper, sqrt_(alpha_lower * alpha_upper));
         double phi, ratio;
-        woodbury_phi<true>(Jh, diag_h, f, alpha, Delta, pp, phi, ratio, jm);
+        woodbury_phi<true>(Jh, diag_h, rhs, alpha, Delta, pp, phi, ratio, jm);
         if (phi < 0) alpha_upper = alpha;
         alpha_lower = fmax(alpha_lower, alpha - ratio);
         alpha -= (phi + Delta) * ratio * inv_Delta;
         if (fabs(phi) < 0.01 * Delta) break;
     }
     double unused_phi, unused_ratio;
-    woodbury_phi<false>(Jh, diag_h, f, alpha, Delta, pp, unused_phi, unused_ratio, jm);
+    woodbury_phi<false>(Jh, diag_h, rhs, alpha, Delta, pp, unused_phi, unused_ratio, jm);
     double scale = div_(Delta, vnorm7(pp));
 #pragma unroll
     for (int c = 0; c < GN; ++c) p[c] = -(pp[c] * scale);
