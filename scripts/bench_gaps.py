@@ -8,11 +8,9 @@ each against a device-to-device copy of the same algorithmic bytes timed in the 
 config-3 size with nothing missing: solve_seq_device against compact -> solve_seq_device -> expand (dense layout, serial
 walk, FK on), the cost of skip mode when the data has no gaps.
 Usage: python scripts/bench_gaps.py [launches]"""
-import os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "sequential-inverse-kinematics_amd"))
-import json
-import numpy as np, torch
+import json, sys
+import torch
+import bench_common
 from seqikpy_amd import _lib
 from bench_support import make_workload
 
@@ -24,23 +22,13 @@ st = torch.cuda.current_stream().cuda_stream
 
 
 def timed(fn, k=K):
-    for _ in range(3):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(k + 1)]
-    ev[0].record()
-    for i in range(k):
-        fn(); ev[i + 1].record()
-    torch.cuda.synchronize()
-    each = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(k)])
-    return {"ms": float(each.mean()), "ms_min": float(each.min()), "ms_median": float(np.median(each))}
+    return bench_common.timed(fn, k, 3)
 
 
 def copy_bar(nbytes):
-    src = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
-    dst = torch.empty_like(src)
-    t = timed(lambda: dst.copy_(src))
-    del src, dst
-    return dict(t, bytes=2 * (nbytes // 8) * 8, GBps=2 * (nbytes // 8) * 8 / t["ms"] / 1e6)
+    bar = bench_common.copy_bar(nbytes, K, 3)
+    del bar["GBps_median"]
+    return bar
 
 
 def rate(t, nbytes, bar):

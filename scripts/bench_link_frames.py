@@ -6,66 +6,32 @@ workgroup, SEQIK_FRAMES_BLOCK), and as the bar a device-to-device copy with the 
 bytes = the call's) timed in the same process.  Then Chain.forward_kinematics_many of the generic chain on the shipped
 6000-frame recording through the GPU against the host loop, both timed here.
 Usage: python scripts/bench_link_frames.py [n_seq] [launches]"""
-import os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "sequential-inverse-kinematics_amd"))
-import json
+import json, os, sys, time
 import numpy as np, torch
-from seqikpy_amd import _lib, data, utils
+from bench_common import ROOT, config3_input, copy_bar, timed
+from seqikpy_amd import _lib, data
 from seqikpy_amd.kinematic_chain import KinematicChainGeneric
 
-S = int(sys.argv[1]) if len(sys.argv) > 1 else 15625
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 40
-L, N = 6, 64
+(S, L, N), params, ang, g, st = config3_input(int(sys.argv[1]) if len(sys.argv) > 1 else 15625)
 n = S * L * N
-legs = data.LEGS
-body = utils.calculate_body_size(data.TEMPLATE_NMF_LOCOMOTION, legs)
-params = [_lib.make_leg_params(l, data.BOUNDS_LOCOMOTION, body, data.INITIAL_ANGLES_LOCOMOTION) for l in legs]
-lb = torch.tensor([[data.BOUNDS_LOCOMOTION[f"{l}_{d}"][0] for d in data.DOFS] for l in legs], dtype=torch.float64).cuda()
-ub = torch.tensor([[data.BOUNDS_LOCOMOTION[f"{l}_{d}"][1] for d in data.DOFS] for l in legs], dtype=torch.float64).cuda()
-g = torch.Generator(device="cuda").manual_seed(3)
-ang = (lb[None, :, None] + torch.rand((S, L, N, 7), dtype=torch.float64, device="cuda", generator=g) *
-       (ub - lb)[None, :, None]).contiguous()
 org = torch.randn((S, L, N, 3), dtype=torch.float64, device="cuda", generator=g)
 frames = torch.empty((S, L, N, 9, 3, 4), dtype=torch.float64, device="cuda")
-st = torch.cuda.current_stream().cuda_stream
-
-
-def timed(fn):
-    for _ in range(10):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)]
-    ev[0].record()
-    for i in range(K):
-        fn(); ev[i + 1].record()
-    torch.cuda.synchronize()
-    each = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(K)])
-    return {"ms": float(each.mean()), "ms_min": float(each.min()), "ms_median": float(np.median(each))}
-
-
-def copy_bar(nbytes):
-    src = torch.empty(nbytes // 8, dtype=torch.float64, device="cuda")
-    dst = torch.empty_like(src)
-    t = timed(lambda: dst.copy_(src))
-    del src, dst
-    total = 2 * (nbytes // 8) * 8
-    return dict(t, bytes=total, GBps=total / t["ms"] / 1e6, GBps_median=total / t["ms_median"] / 1e6)
-
 
 nbytes = n * (80 + 864)
-bar = copy_bar(nbytes // 2)
+bar = copy_bar(nbytes // 2, K, 10)
 out = {"kernel": "seqik_frames_kernel", "leg_frames": n, "n_seq": S, "n_legs": L, "n_frames": N, "launches": K, "kind": "seq",
        "algorithmic_bytes": nbytes, "copy_bar": bar}
 for variant, staged, block in (("per_lane", "0", "256"), ("lds_staged_64", "1", "64"), ("lds_staged_128", "1", "128"),
                                ("lds_staged_256", "1", "256")):
     os.environ["SEQIK_FRAMES_STAGED"], os.environ["SEQIK_FRAMES_BLOCK"] = staged, block
     t = timed(lambda: _lib.link_frames_device(ang.data_ptr(), S, L, N, params, frames.data_ptr(), kind="seq",
-                                              d_origin=org.data_ptr(), stream=st))
+                                              d_origin=org.data_ptr(), stream=st), K, 10)
     out[variant] = dict(t, leg_frames_per_s=n / t["ms_median"] * 1e3, GBps=nbytes / t["ms"] / 1e6,
                         GBps_median=nbytes / t["ms_median"] / 1e6, rate_vs_copy=bar["ms_median"] / t["ms_median"])
 os.environ.pop("SEQIK_FRAMES_STAGED", None); os.environ.pop("SEQIK_FRAMES_BLOCK", None)
 t = timed(lambda: _lib.link_frames_device(ang.data_ptr(), S, L, N, params, frames.data_ptr(), kind="seq",
-                                          d_origin=org.data_ptr(), stream=st))
+                                          d_origin=org.data_ptr(), stream=st), K, 10)
 out["default"] = dict(t, rate_vs_copy=bar["ms_median"] / t["ms_median"])
 del frames, ang, org
 

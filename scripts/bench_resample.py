@@ -7,39 +7,15 @@ moves the same bytes, timed in the same process.  Then what a user sees: utils.i
 6000-frame, 14-series recording at 1e-2 -> 1e-4 s with on_gpu=False (scipy on the host) and on_gpu=True (both copies
 included), wall clock.
 Usage: python scripts/bench_resample.py [n_frames] [launches]"""
-import os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "sequential-inverse-kinematics_amd"))
-import json
+import json, os, sys, time
 import numpy as np, torch
+from bench_common import ROOT, copy_bar, timed
 from seqikpy_amd import _lib, utils
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 C, W = 6, 7
 st = torch.cuda.current_stream().cuda_stream
-
-
-def timed(fn, launches=K, warm=5):
-    for _ in range(warm):
-        fn()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(launches + 1)]
-    ev[0].record()
-    for i in range(launches):
-        fn(); ev[i + 1].record()
-    torch.cuda.synchronize()
-    each = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(launches)])
-    return {"ms": float(each.mean()), "ms_min": float(each.min()), "ms_median": float(np.median(each))}
-
-
-def copy_bar(nbytes, launches):
-    src = torch.empty(nbytes // 16, dtype=torch.float64, device="cuda")
-    dst = torch.empty_like(src)
-    t = timed(lambda: dst.copy_(src), launches)
-    moved = 2 * src.numel() * 8
-    del src, dst
-    torch.cuda.empty_cache()
-    return dict(t, bytes=moved, GBps=moved / t["ms"] / 1e6)
 
 
 g = torch.Generator(device="cuda").manual_seed(5)
@@ -53,11 +29,12 @@ for name, ots, nts, bridge in (("ratio_10", 1e-2, 1e-3, False), ("ratio_100", 1e
     n_out = _lib.resample_count(N, ots, nts)
     launches = max(5, K // 4) if n_out > 20 * N else K
     nbytes = C * (8 * W * (N + n_out) + (8 * N if bridge else 0))
-    bar = copy_bar(nbytes, launches)
+    bar = copy_bar(nbytes // 2, launches, 5)
+    del bar["GBps_median"]
     d_out = torch.empty((C, n_out, W), dtype=torch.float64, device="cuda")
     src = y_gaps if bridge else y
     t = timed(lambda: _lib.resample_pchip_device(src, C, N, W, ots, nts, d_out, missing="bridge" if bridge else "error",
-                                                 d_workspace=ws if bridge else 0, stream=st), launches)
+                                                 d_workspace=ws if bridge else 0, stream=st), launches, 5)
     gbps = nbytes / t["ms"] / 1e6
     out[name] = dict(t, n_out=n_out, algorithmic_bytes=nbytes, GBps=gbps, GBps_best_launch=nbytes / t["ms_min"] / 1e6,
                      samples_per_s=C * n_out / t["ms"] * 1e3, copy_bar=bar, rate_vs_copy=gbps / bar["GBps"])

@@ -2,10 +2,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#include "seqik_fk.hpp"
-#include "seqik_runtime.hpp"
+#include "seqik_leg_map.hpp"
 #include "../../include/seqik_fk.h"
 
 namespace {
@@ -20,11 +18,7 @@ struct FkArgs {
     const double *origin;  // nullable, [n_total][3]
     double *fk;            // [n_total][9][3]
     double *dist;          // nullable, [n_total][4]
-    int64_t n_frames;      // leg-frame i belongs to leg (i / n_frames) % n_legs
-    int64_t n_total;       // n_seq * n_legs * n_frames
-    int32_t n_legs;
-    int32_t pad_;
-    seqik::FkLeg legs[seqik::kFkMaxLegs];
+    seqik::LegFrameIndex ix;
 };
 
 constexpr int kFkWaveLds = 64 * kFkRow;  // doubles of LDS per wavefront (STAGED)
@@ -57,7 +51,7 @@ template <int KIND, bool STAGED>
 __global__ void __launch_bounds__(1024) seqik_fk_kernel(FkArgs a)
 {
     extern __shared__ double s_fk[];  // STAGED: kFkWaveLds doubles per wavefront
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = a.n_total;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = a.ix.n_total;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x; t0 < n; t0 += stride) {
         const int64_t i = t0 + threadIdx.x;
@@ -72,9 +66,9 @@ __global__ void __launch_bounds__(1024) seqik_fk_kernel(FkArgs a)
 #pragma unroll
             for (int d = 0; d < 7; ++d) x[d] = st[lane * 7 + d];
             wave_lds_fence();  // every lane has its angles before any lane overwrites them with FK rows
-            const int leg = (int)((i / a.n_frames) % a.n_legs);
+            const int leg = a.ix.leg_of(i);
             double *row = st + lane * kFkRow;
-            seqik::fk_leg_frame<KIND>(a.legs[leg], x, fk_origin(a, i), row);
+            seqik::fk_leg_frame<KIND>(a.ix.legs[leg], x, fk_origin(a, i), row);
             fk_store_dist(a, i, row);
             wave_lds_fence();
             double *gf = a.fk + w0 * kFkRow;
@@ -82,9 +76,9 @@ __global__ void __launch_bounds__(1024) seqik_fk_kernel(FkArgs a)
             for (int k = 0; k < kFkRow; ++k) __builtin_nontemporal_store(st[k * 64 + lane], gf + k * 64 + lane);
             wave_lds_fence();  // the next iteration's LDS writes stay behind these reads
         } else if (i < n) {
-            const int leg = (int)((i / a.n_frames) % a.n_legs);
+            const int leg = a.ix.leg_of(i);
             double row[kFkRow];
-            seqik::fk_leg_frame<KIND>(a.legs[leg], a.angles + i * 7, fk_origin(a, i), row);
+            seqik::fk_leg_frame<KIND>(a.ix.legs[leg], a.angles + i * 7, fk_origin(a, i), row);
             fk_store_dist(a, i, row);
             double *gf = a.fk + i * kFkRow;
 #pragma unroll
@@ -100,17 +94,11 @@ int fk_validate(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_f
                 int32_t kind, const double *pose, const double *origin, const double *fk, const double *dist,
                 int64_t *n_total)
 {
-    if (n_legs < 1 || n_legs > seqik::kFkMaxLegs)
-        return bad_arg(kWho, "n_legs must lie in 1..8");
-    if (n_seq < 0 || n_frames < 0) return bad_arg(kWho, "negative n_seq or n_frames");
+    if (int rc = seqik::check_leg_map(kWho, n_seq, n_legs, n_frames, legs, kind, kFkRow, n_total)) return rc;
     if (!angles || !fk) return bad_arg(kWho, "angles and fk must not be null");
-    if (!legs) return bad_arg(kWho, "legs must not be null");
-    if (kind != SEQIK_FK_KIND_SEQ && kind != SEQIK_FK_KIND_GENERIC)
-        return bad_arg(kWho, "kind must be 0 (sequential chain) or 1 (generic chain)");
     if (pose && origin) return bad_arg(kWho, "pass pose or origin, not both");
     if (dist && !pose) return bad_arg(kWho, "dist needs pose (the key points to measure against)");
-    if (int rc = seqik::check_segments(kWho, legs, n_legs)) return rc;
-    return seqik::leg_frames_fit(kWho, n_seq, n_legs, n_frames, n_total);
+    return SEQIK_OK;
 }
 
 }  // namespace
@@ -127,25 +115,14 @@ int seqik_forward_kinematics_device(const double *d_angles, int64_t n_seq, int32
     if (n == 0) return SEQIK_OK;
     FkArgs a;
     a.angles = d_angles; a.pose = d_pose; a.origin = d_origin; a.fk = d_fk; a.dist = d_dist;
-    a.n_frames = n_frames; a.n_total = n; a.n_legs = n_legs; a.pad_ = 0;
-    for (int l = 0; l < seqik::kFkMaxLegs; ++l) seqik::make_fk_leg(legs[l < n_legs ? l : 0], a.legs[l]);
+    a.ix.fill(n, n_legs, n_frames, legs);
     // LDS-staged by default: 6 M leg-frames in 0.296 ms = 1.00 x a copy of the same traffic, the per-lane kernel 0.508 ms =
-    // 0.58 x (profiles/fk_bench_r07.json, EXPERIMENTS.md 7.1).  SEQIK_FK_STAGED = 0 / 1 and SEQIK_FK_BLOCK (threads per
-    // workgroup, 64..1024) select variants for measurements and tests; read per call so that one process can run both.
-    const char *env_staged = getenv("SEQIK_FK_STAGED"), *env_block = getenv("SEQIK_FK_BLOCK");
-    const bool staged = env_staged ? atoi(env_staged) != 0 : true;
-    int block = env_block ? atoi(env_block) : 256;
-    if (block < 64 || block > 1024 || block % 64) block = 256;
-    if (staged && block > 256) block = 256;  // 13.5 KiB of LDS per wavefront: at most 54 KiB per workgroup
-    int64_t blocks = (n + block - 1) / block;
-    if (blocks > 256 * 64) blocks = 256 * 64;  // grid-stride beyond 64 workgroups per CU (as seqik_head.hip)
-    const size_t lds = staged ? sizeof(double) * kFkWaveLds * (block / 64) : 0;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-#define FK_LAUNCH(K, ST) hipLaunchKernelGGL((seqik_fk_kernel<K, ST>), dim3((unsigned)blocks), dim3(block), lds, s, a)
-    if (kind == SEQIK_FK_KIND_SEQ) { if (staged) FK_LAUNCH(0, true); else FK_LAUNCH(0, false); }
-    else { if (staged) FK_LAUNCH(1, true); else FK_LAUNCH(1, false); }
-#undef FK_LAUNCH
-    return seqik::launched();
+    // 0.58 x (profiles/fk_bench_r07.json, EXPERIMENTS.md 7.1).  Per lane up to 1024 threads per workgroup; staged at most
+    // 256: 13.5 KiB of LDS per wavefront, 54 KiB per workgroup.
+    const seqik::LegMapPlan p = seqik::plan_leg_map("SEQIK_FK", n, true, 1024, 256, kFkWaveLds);
+    auto *kernel = kind == SEQIK_FK_KIND_SEQ ? (p.staged ? seqik_fk_kernel<0, true> : seqik_fk_kernel<0, false>)
+                                             : (p.staged ? seqik_fk_kernel<1, true> : seqik_fk_kernel<1, false>);
+    return seqik::launch_leg_map(kernel, p, a, hip_stream);
 }
 
 int seqik_forward_kinematics(const double *angles, int64_t n_seq, int32_t n_legs, int64_t n_frames,

@@ -37,10 +37,11 @@ constexpr int kFkRow = 27;  // doubles of FK per leg-frame: the largest per-leg-
 // workgroups of `waves_per_block` wavefronts that hold `waves` wavefronts
 inline int64_t blocks_for(int64_t waves, int waves_per_block) { return (waves + waves_per_block - 1) / waves_per_block; }
 
-// n_seq * n_legs * n_frames into *n_total; the byte count of 27 doubles per leg-frame must fit in 63 bits
-inline int leg_frames_fit(const char *who, int64_t n_seq, int32_t n_legs, int64_t n_frames, int64_t *n_total)
+// n_seq * n_legs * n_frames into *n_total; the byte count of `row` doubles per leg-frame must fit in 63 bits
+inline int leg_frames_fit(const char *who, int64_t n_seq, int32_t n_legs, int64_t n_frames, int64_t *n_total,
+                          int row = kFkRow)
 {
-    const int64_t lim = INT64_MAX / (8 * kFkRow);
+    const int64_t lim = INT64_MAX / (8 * row);
     if (n_seq != 0 && n_frames != 0 && (n_seq > lim / n_legs || n_seq * n_legs > lim / n_frames))
         return bad_arg(who, "too many leg-frames");
     *n_total = n_seq * n_legs * n_frames;

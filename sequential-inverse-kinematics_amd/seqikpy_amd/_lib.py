@@ -27,7 +27,7 @@ COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_
                  "seqik_head_align.hip", "seqik_jacobian.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
-                "seqik_head_align.hpp", "seqik_jacobian.hpp"]
+                "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -430,13 +430,20 @@ def _fk_kind(kind) -> int:
 
 
 def _angles_batch(angles, legs, kind):
-    """The checks ``forward_kinematics`` and ``link_frames`` share -> (angles, (S, L, N), kind as int)."""
+    """The checks the host wrappers of the angle maps share -> (angles, (S, L, N), kind as int, the leading arguments)."""
     angles = np.ascontiguousarray(angles, dtype=np.float64)
     if angles.ndim != 4 or angles.shape[3] != 7:
         raise ValueError(f"angles must have shape (S, L, N, 7), got {angles.shape}")
     if len(legs) != angles.shape[1]:
         raise ValueError("one SeqikLegParams per leg expected")
-    return angles, angles.shape[:3], _fk_kind(kind)
+    k = _fk_kind(kind)
+    return angles, angles.shape[:3], k, (_data(angles), *angles.shape[:3], (SeqikLegParams * len(legs))(*legs), k)
+
+
+def _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, kind):
+    """The leading arguments of the angle maps' ``*_device`` wrappers -> ((S, L, N), (angles, S, L, N, legs, kind))."""
+    lf = (n_seq, n_legs, n_frames)
+    return lf, (_ptr(d_angles, "angles", lf + (7,)), *map(int, lf), (SeqikLegParams * n_legs)(*legs), _fk_kind(kind))
 
 
 def _origin_batch(origin, slf):
@@ -455,7 +462,7 @@ def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_di
     (S, L, N, 3); the fused alignment's origin is ``template_coxa``), or 0 when neither is given (leg-local positions).
     ``want_dist`` (needs ``pose``): distances of FK rows 4, 6, 7, 8 from key points 1..4.  An angle that is not finite or lies beyond
     ``SEQIK_ANGLE_MAX`` (2^30 rad, include/seqik_fk.h) makes that leg-frame's rows (and distances) NaN.  Fed a solver's angles and origin, the result equals the solver's FK bit for bit."""
-    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    angles, (S, L, N), k, head = _angles_batch(angles, legs, kind)
     if pose is not None and origin is not None:
         raise ValueError("pass pose or origin, not both")
     if want_dist and pose is None:
@@ -467,8 +474,7 @@ def forward_kinematics(angles, legs, kind="seq", pose=None, origin=None, want_di
     origin = _origin_batch(origin, (S, L, N))
     fk = np.full((S, L, N, 9, 3), np.nan)
     dist = np.full((S, L, N, 4), np.nan) if want_dist else None
-    _call("seqik_forward_kinematics", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(pose), _data(origin),
-          _data(fk), _data(dist), int(device))
+    _call("seqik_forward_kinematics", *head, _data(pose), _data(origin), _data(fk), _data(dist), int(device))
     return dict(fk=fk, dist=dist)
 
 
@@ -477,11 +483,9 @@ def forward_kinematics_device(d_angles, n_seq, n_legs, n_frames, legs, d_fk, kin
     """``seqik_forward_kinematics_device``: raw device pointers (ints) or torch tensors in the dense layouts of
     ``forward_kinematics``, asynchronous on ``stream`` (a hipStream_t as int, or a torch stream; 0 = the default stream)
     of the current device."""
-    lf = (n_seq, n_legs, n_frames)
-    _call("seqik_forward_kinematics_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
-          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_pose, "pose", lf + (5, 3)),
-          _ptr(d_origin, "origin", lf + (3,)), _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_dist, "dist", lf + (4,)),
-          _stream_ptr(stream))
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, kind)
+    _call("seqik_forward_kinematics_device", *head, _ptr(d_pose, "pose", lf + (5, 3)), _ptr(d_origin, "origin", lf + (3,)),
+          _ptr(d_fk, "fk", lf + (9, 3)), _ptr(d_dist, "dist", lf + (4,)), _stream_ptr(stream))
 
 
 #: entry points of include/seqik_frames.h (link frames from joint angles), kept apart from the ABI-7 set of seqik.h
@@ -499,11 +503,10 @@ def link_frames(angles, legs, kind="seq", origin=None, device=-1, rows3=False):
     for the same angles, kind and origin bit for bit.  ``rows3=True`` returns the (S, L, N, 9, 3, 4) array as the library
     wrote it (the fourth row, 0 0 0 1, is filled in on the host otherwise).  An angle that is not finite or lies beyond
     ``SEQIK_ANGLE_MAX`` (2^30 rad) makes that leg-frame's frames NaN (with ``rows3=False`` the fourth row too)."""
-    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    angles, (S, L, N), k, head = _angles_batch(angles, legs, kind)
     origin = _origin_batch(origin, (S, L, N))
     rows = np.full((S, L, N, 9, 3, 4), np.nan)
-    _call("seqik_link_frames", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(origin), _data(rows),
-          int(device))
+    _call("seqik_link_frames", *head, _data(origin), _data(rows), int(device))
     if rows3:
         return dict(frames=rows)
     frames = np.empty((S, L, N, 9, 4, 4))
@@ -517,10 +520,9 @@ def link_frames_device(d_angles, n_seq, n_legs, n_frames, legs, d_frames, kind="
     """``seqik_link_frames_device``: raw device pointers (ints) or torch tensors in the dense layouts of
     ``include/seqik_frames.h`` (``d_frames``: (S, L, N, 9, 3, 4) doubles), asynchronous on ``stream`` (a hipStream_t as
     int, or a torch stream; None / 0 = the default stream) of the current device."""
-    lf = (n_seq, n_legs, n_frames)
-    _call("seqik_link_frames_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
-          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_origin, "origin", lf + (3,)),
-          _ptr(d_frames, "frames", lf + (9, 3, 4)), _stream_ptr(stream))
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, kind)
+    _call("seqik_link_frames_device", *head, _ptr(d_origin, "origin", lf + (3,)), _ptr(d_frames, "frames", lf + (9, 3, 4)),
+          _stream_ptr(stream))
 
 
 #: entry points of include/seqik_jacobian.h (leg Jacobians, conditioning, key-point velocities), additive to ABI 7
@@ -546,7 +548,7 @@ def leg_jacobians(angles, legs, kind="seq", qdot=None, want_jac=True, want_sigma
     values of the claw's 3 x 7 block, descending.  ``vel`` (when ``qdot`` (S, L, N, 7), joint rates, is given): ``jac @
     qdot``, the key-point velocities.  At least one of the three must be asked for.  An angle that is not finite or lies
     beyond ``SEQIK_ANGLE_MAX`` makes that leg-frame's values NaN; a non-finite rate its velocities only."""
-    angles, (S, L, N), k = _angles_batch(angles, legs, kind)
+    angles, (S, L, N), k, head = _angles_batch(angles, legs, kind)
     if qdot is not None:
         qdot = np.ascontiguousarray(qdot, dtype=np.float64)
         if qdot.shape != angles.shape:
@@ -554,8 +556,7 @@ def leg_jacobians(angles, legs, kind="seq", qdot=None, want_jac=True, want_sigma
     jac = np.full((S, L, N, 4, 3, 7), np.nan) if want_jac else None
     sigma = np.full((S, L, N, 8), np.nan) if want_sigma else None
     vel = np.full((S, L, N, 4, 3), np.nan) if qdot is not None else None
-    _call("seqik_leg_jacobians", _data(angles), S, L, N, (SeqikLegParams * L)(*legs), k, _data(qdot), _data(jac),
-          _data(sigma), _data(vel), int(device))
+    _call("seqik_leg_jacobians", *head, _data(qdot), _data(jac), _data(sigma), _data(vel), int(device))
     return dict(jac=jac, sigma=_sigma_view(sigma, k), vel=vel)
 
 
@@ -565,11 +566,9 @@ def leg_jacobians_device(d_angles, n_seq, n_legs, n_frames, legs, kind="seq", d_
     ``include/seqik_jacobian.h`` (``d_jac`` (S, L, N, 4, 3, 7), ``d_sigma`` (S, L, N, 8), ``d_vel`` (S, L, N, 4, 3)
     doubles; 0 / None: not computed, not written; at least one), asynchronous on ``stream`` (a hipStream_t as int, or a
     torch stream; None / 0 = the default stream) of the current device."""
-    lf = (n_seq, n_legs, n_frames)
-    _call("seqik_leg_jacobians_device", _ptr(d_angles, "angles", lf + (7,)), int(n_seq), int(n_legs), int(n_frames),
-          (SeqikLegParams * n_legs)(*legs), _fk_kind(kind), _ptr(d_qdot, "qdot", lf + (7,)),
-          _ptr(d_jac, "jac", lf + (4, 3, 7)), _ptr(d_sigma, "sigma", lf + (8,)), _ptr(d_vel, "vel", lf + (4, 3)),
-          _stream_ptr(stream))
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, kind)
+    _call("seqik_leg_jacobians_device", *head, _ptr(d_qdot, "qdot", lf + (7,)), _ptr(d_jac, "jac", lf + (4, 3, 7)),
+          _ptr(d_sigma, "sigma", lf + (8,)), _ptr(d_vel, "vel", lf + (4, 3)), _stream_ptr(stream))
 
 
 #: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h

@@ -58,6 +58,7 @@ import mpmath
 import numpy as np
 import pytest
 
+from angle_map_support import gpu_lib, same_bits, switches
 from conftest import ROOT, host_harness  # noqa: F401  (fixture: sincos_cw run on the host)
 from test_forward_kinematics import fk_harness  # noqa: F401  (fixture: the FK rule run on the host)
 from test_link_frames import frames_harness  # noqa: F401  (fixture: the frames rule run on the host)
@@ -343,11 +344,6 @@ def run(be, fam, kind):
     return fk[0], dist[0], fr[0]
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
 # -------------------------------------------------------- K_ref --------------------------------------------------------
 
 def _shim():
@@ -560,9 +556,7 @@ def test_host_edge_of_the_domain_is_inside(host, fams):
 
 @pytest.fixture(scope="module")
 def lib(hiplib):
-    if hiplib.load().seqik_device_count() < 1:
-        pytest.fail("GPU tier needs a GPU: the HIP path must not be skipped silently")
-    return hiplib
+    return gpu_lib(hiplib)
 
 
 @pytest.fixture(scope="module", params=["host", "device"])
@@ -604,12 +598,9 @@ def test_gpu_sizes_around_the_tile_equal_the_host_rule(dev, host, fams, n_legs, 
         ref_fk, ref_dist = host.fk(ang, seg, kind, pose)
         ref_fr = host.frames(ang, seg, kind, pose[:, :, :, 0])
         for staged in ("1", "0"):
-            os.environ["SEQIK_FK_STAGED"] = os.environ["SEQIK_FRAMES_STAGED"] = staged
-            try:
+            with switches(SEQIK_FK_STAGED=staged, SEQIK_FRAMES_STAGED=staged):
                 fk, dist = dev.fk(ang, seg, kind, pose)
                 fr = dev.frames(ang, seg, kind, pose[:, :, :, 0])
-            finally:
-                os.environ.pop("SEQIK_FK_STAGED"), os.environ.pop("SEQIK_FRAMES_STAGED")
             assert same_bits(fk, ref_fk) and same_bits(dist, ref_dist) and same_bits(fr, ref_fr), (dev.name, kind, staged)
 
 

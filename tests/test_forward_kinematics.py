@@ -12,6 +12,8 @@ import re
 import numpy as np
 import pytest
 
+from angle_map_support import (_generic_params, _params, _stack, SENTINEL, gpu_lib, guarded, made_up_batch, same_bits,
+                               switches, unguarded)
 from conftest import DOFS, ROOT, LegParamsC, leg_arrays, load_golden
 from harness_build import build_harness
 
@@ -38,6 +40,16 @@ class FkHarness:
         self.lib.harness_fk.restype = ctypes.c_int
         self.lib.harness_fk.argtypes = [dp, ctypes.c_int64, ctypes.POINTER(LegParamsC), ctypes.c_int32, dp,
                                         ctypes.c_int64, dp, dp]
+        self.lib.harness_leg_map_plan.restype = None
+        self.lib.harness_leg_map_plan.argtypes = [ctypes.c_char_p, ctypes.c_int64] + [ctypes.c_int32] * 4 + [
+            ctypes.POINTER(ctypes.c_int64)]
+
+    def plan(self, prefix, n_total, unit, **env):
+        """plan_leg_map under the switches `env` (without the prefix) -> (staged, block, workgroups, LDS bytes)."""
+        out = (ctypes.c_int64 * 4)()
+        with switches(**{f"{prefix}_{k}": str(v) for k, v in env.items()}):
+            self.lib.harness_leg_map_plan(prefix.encode(), n_total, *unit, out)
+        return tuple(out)
 
     def fk(self, angles, seg, kind, pose=None, origin=None, want_dist=False):
         dp = ctypes.POINTER(ctypes.c_double)
@@ -133,6 +145,39 @@ def test_host_fk_nan_angle_and_leg_local_origin(fk_harness):
     assert np.abs(local + pose[:, :1] - fk_harness.fk(z["RF_angles"], seg, 0, pose=pose)[0])[ok].max() < 1e-15
 
 
+# what each unit hands to plan_leg_map: staging allowed, largest block per lane and staged, doubles of LDS per wavefront
+PLAN_UNITS = {"SEQIK_FK": (1, 1024, 256, 64 * 27), "SEQIK_FRAMES": (1, 256, 256, 64 * 27), "SEQIK_JAC": (1, 256, 256, 64 * 21)}
+
+
+@pytest.mark.parametrize("prefix", sorted(PLAN_UNITS))
+def test_launch_plan_defaults_clamps_and_caps(fk_harness, prefix):
+    """The launch plan the three angle-map units share, with the numbers each unit's own launch code gave before the plan
+    was shared: 256 threads and the staged kernel by default; a block that is no multiple of 64 in 64..max means 256;
+    a staged FK launch takes at most 256; at most 256 * 64 workgroups; <prefix>_GRID caps them further."""
+    unit = PLAN_UNITS[prefix]
+    w, fk = 8 * unit[3], prefix == "SEQIK_FK"
+    plan = lambda n, **env: fk_harness.plan(prefix, n, unit, **env)  # noqa: E731
+    assert not [k for k in os.environ if k.startswith(prefix + "_")]
+    assert plan(1000) == (1, 256, 4, 4 * w) and plan(1) == (1, 256, 1, 4 * w) and plan(1025) == (1, 256, 5, 4 * w)
+    assert plan(1000, STAGED=0) == (0, 256, 4, 0) and plan(1000, STAGED=7) == (1, 256, 4, 4 * w)
+    assert fk_harness.plan(prefix, 1000, (0,) + unit[1:], STAGED=1) == (0, 256, 4, 0)   # a request without a record
+    for staged in (0, 1):
+        lds = lambda block: staged * w * (block // 64)  # noqa: E731
+        for bad in (63, 65, 2048, 0, -64, 1088):
+            assert plan(1000, STAGED=staged, BLOCK=bad) == (staged, 256, 4, lds(256)), (staged, bad)
+        assert plan(1000, STAGED=staged, BLOCK=64) == (staged, 64, 16, lds(64))
+        assert plan(1000, STAGED=staged, BLOCK=128) == (staged, 128, 8, lds(128))
+        big = 512 if fk and not staged else 256   # per lane FK goes up to 1024; everything else stops at 256
+        assert plan(1000, STAGED=staged, BLOCK=512) == (staged, big, -(-1000 // big), lds(big))
+        assert plan(5000, STAGED=staged, BLOCK=1024) == ((0, 1024, 5, 0) if fk and not staged else (staged, 256, 20, lds(256)))
+    full = 256 * 64 * 256
+    assert plan(full)[2] == 256 * 64 == plan(full + 1)[2] == plan(6_000_000_000)[2] and plan(full - 256)[2] == 256 * 64 - 1
+    assert plan(full + 1, BLOCK=64)[2] == 256 * 64
+    assert plan(1573, GRID=3) == (1, 256, 3, 4 * w) and plan(421, GRID=3, BLOCK=64, STAGED=0) == (0, 64, 3, 0)
+    assert plan(1000, GRID=4)[2] == 4 == plan(1000, GRID=9)[2] == plan(1000, GRID=0)[2] == plan(1000, GRID=-2)[2]
+    assert plan(1000, GRID=1)[2] == 1
+
+
 def _call(lib, fn, angles, n_seq, n_legs, n_frames, legs, kind, pose, origin, fk, dist):
     dp = ctypes.POINTER(ctypes.c_double)
     p = lambda a: a.ctypes.data_as(dp) if a is not None else None  # noqa: E731
@@ -202,28 +247,7 @@ def test_fk_python_argument_errors(hiplib):
 
 @pytest.fixture(scope="module")
 def lib(hiplib):
-    if hiplib.load().seqik_device_count() < 1:
-        pytest.fail("GPU tier needs a GPU: the HIP path must not be skipped silently")
-    return hiplib
-
-
-def _params(lib, z, legs):
-    return [lib.leg_params_from_arrays(z[f"{l}_seg"], z[f"{l}_bounds"], z[f"{l}_seeds"]) for l in legs]
-
-
-def _generic_params(lib, z, legs):
-    """The fixture's legs with mid-range seeds for the generic chain (seeded positionally in its own link order: roll,
-    yaw, pitch, ...; the sequential seeds of the middle and hind legs lie outside those bounds)."""
-    out = []
-    for l in legs:
-        seeds = z[f"{l}_seeds"].copy()
-        seeds[19:26] = z[f"{l}_bounds"][[2, 0, 1, 3, 4, 5, 6]].mean(axis=1)
-        out.append(lib.leg_params_from_arrays(z[f"{l}_seg"], z[f"{l}_bounds"], seeds))
-    return out
-
-
-def _stack(z, legs, sl=slice(None)):
-    return np.stack([z[f"{l}_pose"][sl] for l in legs])[None]
+    return gpu_lib(hiplib)
 
 
 @pytest.mark.gpu
@@ -334,11 +358,8 @@ def test_gpu_fk_device_entry_point_on_a_torch_stream(lib):
     # both kernel variants (LDS-staged, the default, and per lane; SEQIK_FK_STAGED is read per call), including a range
     # that ends in a partial wavefront
     for staged in ("0", "1"):
-        os.environ["SEQIK_FK_STAGED"] = staged
-        try:
+        with switches(SEQIK_FK_STAGED=staged):
             v = lib.forward_kinematics(ang[:, :, :997], params, pose=pose[:, :, :997], want_dist=True)
-        finally:
-            os.environ.pop("SEQIK_FK_STAGED")
         assert np.array_equal(v["fk"], host["fk"][:, :, :997]) and np.array_equal(v["dist"], host["dist"][:, :, :997])
     for kind in ("seq", "generic"):
         ref = lib.forward_kinematics(ang, params, kind=kind, origin=pose[..., 0, :])["fk"]
@@ -348,6 +369,40 @@ def test_gpu_fk_device_entry_point_on_a_torch_stream(lib):
                                       d_origin=d_org.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         assert np.array_equal(out.cpu().numpy(), ref), kind
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 1])
+def test_gpu_fk_block_sizes_and_a_capped_grid(lib, fk_harness, kind):
+    """SEQIK_FK_GRID = 3 at 2 * 3 * block + 37 leg-frames: every workgroup makes two full trips of the grid-stride loop and
+    the third is ragged -- whole wavefronts, then a partial one on the per-lane path.  SEQIK_FK_BLOCK 64 and 256 with both
+    kernels, 1024 per lane (seven legs: the trips straddle leg seams), two sequences of three legs, and once with pose
+    and dist.  Bit for bit against the host-run rule, guard records around every output."""
+    import torch
+    runs = [(1, 1, 2 * 3 * b + 37, st, b, False) for st in ("0", "1") for b in (64, 256)]
+    runs += [(1, 7, (2 * 3 * 1024 + 37) // 7, "0", 1024, False), (1, 1, 2 * 3 * 256 + 37, "1", 256, True)]
+    runs += [(2, 3, 71, st, 64, True) for st in ("0", "1")]
+    assert 7 * runs[4][2] == 2 * 3 * 1024 + 37 and 2 * 3 * 71 > 2 * 3 * 64 + 37
+    for S, L, N, staged, block, with_pose in runs:
+        ang, segs, org = made_up_batch(S, L, N, 40 + block)
+        pose = np.random.default_rng(block).standard_normal((S, L, N, 5, 3))
+        src = dict(pose=pose) if with_pose else dict(origin=org)
+        ref = [fk_harness.fk(ang[:, l].reshape(-1, 7), segs[l], kind, want_dist=with_pose,
+                             **{k: v[:, l].reshape((S * N,) + v.shape[3:]) for k, v in src.items()}) for l in range(L)]
+        d_ang, d_src = torch.from_numpy(ang).cuda(), torch.from_numpy(pose if with_pose else org).cuda()
+        (fk, p_fk), (dist, p_dist) = guarded(S * L * N, 27), guarded(S * L * N, 4)
+        params = [lib.leg_params_from_arrays(s, np.zeros((7, 2)), np.zeros(27)) for s in segs]
+        with switches(SEQIK_FK_STAGED=staged, SEQIK_FK_BLOCK=str(block), SEQIK_FK_GRID="3"):
+            lib.forward_kinematics_device(d_ang, S, L, N, params, p_fk, kind=kind, d_dist=p_dist if with_pose else 0,
+                                          stream=torch.cuda.current_stream().cuda_stream,
+                                          **{"d_pose" if with_pose else "d_origin": d_src})
+            torch.cuda.synchronize()
+        got_fk, got_dist = unguarded(fk, 27).reshape(S, L, N, 9, 3), unguarded(dist, 4).reshape(S, L, N, 4)
+        for l in range(L):
+            assert same_bits(got_fk[:, l].reshape(-1, 9, 3), ref[l][0]), (kind, S, L, N, staged, block, with_pose, l)
+            if with_pose:
+                assert same_bits(got_dist[:, l].reshape(-1, 4), ref[l][1]), (kind, S, L, N, staged, block, l)
+        assert with_pose or (got_dist == SENTINEL).all()
 
 
 @pytest.mark.gpu

@@ -47,9 +47,10 @@ bits (tests/test_jacobians.py)."""
 import numpy as np
 import pytest
 
+from angle_map_support import gpu_lib, same_bits
 from conftest import ROOT  # noqa: F401
 from test_fk_accuracy import (H_FRAMES, H_JOINTS, H_N, OUTSIDE, SPEC, _MP, _split, build_families, h_batches, mp_chain,
-                              restatement, same_bits)
+                              restatement)
 from test_jacobians import (KEY_LINKS, STAGE_DOFS, jac_harness, nonzero_mask, numpy_jacobian)  # noqa: F401
 
 U = 2.0 ** -53
@@ -317,9 +318,7 @@ def test_host_outside_the_domain_makes_that_leg_frame_nan(jac_harness):  # noqa:
 
 @pytest.fixture(scope="module")
 def lib(hiplib):
-    if hiplib.load().seqik_device_count() < 1:
-        pytest.fail("GPU tier needs a GPU: the HIP path must not be skipped silently")
-    return hiplib
+    return gpu_lib(hiplib)
 
 
 @pytest.mark.gpu

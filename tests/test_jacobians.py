@@ -19,6 +19,7 @@ import sys
 import numpy as np
 import pytest
 
+from angle_map_support import gpu_lib, same_bits, switches
 from conftest import DOFS, ROOT, LegParamsC, load_golden
 from harness_build import build_harness
 from test_capi_symbols import assert_same_class, header_prototypes
@@ -37,11 +38,6 @@ DOF_LINK = {0: [(1, 0), (2, 1), (3, 2), (4, 1), (5, 2), (6, 1), (7, 1)],
 
 def nonzero_mask(kind):
     return np.array([[c == "1" for c in row] for row in PATTERN[kind]])   # (4, 7)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 class JacHarness:
@@ -314,9 +310,7 @@ def test_host_conditioning_of_the_shipped_recording(jac_harness):
 
 @pytest.fixture(scope="module")
 def lib(hiplib):
-    if hiplib.load().seqik_device_count() < 1:
-        pytest.fail("GPU tier needs a GPU: the HIP path must not be skipped silently")
-    return hiplib
+    return gpu_lib(hiplib)
 
 
 SENTINEL = -12345.678
@@ -342,16 +336,11 @@ def device_run(lib, ang, qdot, segs, kind, want, env=None):
     d_ang, d_q = torch.from_numpy(np.ascontiguousarray(ang)).cuda(), torch.from_numpy(np.ascontiguousarray(qdot)).cuda()
     bufs = {k: torch.full(((n + 2) * w,), SENTINEL, dtype=torch.float64, device="cuda") for k, w in WIDTH.items()}
     ptr = {k: (bufs[k].data_ptr() + 8 * WIDTH[k] if k in want else 0) for k in WIDTH}
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
+    with switches(**(env or {})):
         lib.leg_jacobians_device(d_ang.data_ptr(), S, L, N, _params_of(lib, segs), kind=kind, d_qdot=d_q.data_ptr(),
                                  d_jac=ptr["jac"], d_sigma=ptr["sigma"], d_vel=ptr["vel"],
                                  stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
     out = {}
     for k, w in WIDTH.items():
         got = bufs[k].cpu().numpy()

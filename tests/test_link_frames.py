@@ -19,6 +19,8 @@ import sys
 import numpy as np
 import pytest
 
+from angle_map_support import (_generic_params, _params, _stack, gpu_lib, guarded, made_up_batch, same_bits, switches,
+                               unguarded)
 from conftest import DOFS, ROOT, LegParamsC, load_golden
 from harness_build import build_harness
 from test_forward_kinematics import fk_harness, _lp  # noqa: F401  (fixture: the FK rule run on the host)
@@ -378,26 +380,7 @@ def test_frames_python_argument_errors(hiplib):
 
 @pytest.fixture(scope="module")
 def lib(hiplib):
-    if hiplib.load().seqik_device_count() < 1:
-        pytest.fail("GPU tier needs a GPU: the HIP path must not be skipped silently")
-    return hiplib
-
-
-def _params(lib, z, legs):
-    return [lib.leg_params_from_arrays(z[f"{l}_seg"], z[f"{l}_bounds"], z[f"{l}_seeds"]) for l in legs]
-
-
-def _generic_params(lib, z, legs):
-    out = []
-    for l in legs:
-        seeds = z[f"{l}_seeds"].copy()
-        seeds[19:26] = z[f"{l}_bounds"][[2, 0, 1, 3, 4, 5, 6]].mean(axis=1)
-        out.append(lib.leg_params_from_arrays(z[f"{l}_seg"], z[f"{l}_bounds"], seeds))
-    return out
-
-
-def _stack(z, legs, key="pose", sl=slice(None)):
-    return np.stack([z[f"{l}_{key}"][sl] for l in legs])[None]
+    return gpu_lib(hiplib)
 
 
 def _host_batch(frames_harness, ang, segs, kind, origin=None):
@@ -463,12 +446,30 @@ def test_gpu_frames_equal_the_host_rule_at_config3_size_and_on_tails(lib, frames
         o = np.ascontiguousarray(np.resize(org[:40], (1, 6, n, 3)))
         ref = _host_batch(frames_harness, a, segs, k, o)
         for staged in ("0", "1"):
-            os.environ["SEQIK_FRAMES_STAGED"] = staged
-            try:
+            with switches(SEQIK_FRAMES_STAGED=staged):
                 got = lib.link_frames(a, params, kind=kind, origin=o, rows3=True)["frames"]
-            finally:
-                os.environ.pop("SEQIK_FRAMES_STAGED")
             assert np.array_equal(got, ref, equal_nan=True), (kind, n, staged)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", [0, 1])
+def test_gpu_frames_block_sizes_and_a_capped_grid(lib, frames_harness, kind):
+    """SEQIK_FRAMES_GRID = 3 at 2 * 3 * block + 37 leg-frames: every workgroup makes two full trips of the grid-stride loop
+    and the third is ragged -- whole wavefronts, then a partial one on the per-lane path.  SEQIK_FRAMES_BLOCK 64 and 256
+    with both kernels, and two sequences of three legs, whose trips straddle leg and sequence seams.  Bit for bit against
+    the host-run rule, guard records around the output."""
+    import torch
+    runs = [(1, 1, 2 * 3 * b + 37, st, b) for st in ("0", "1") for b in (64, 256)] + [(2, 3, 71, st, 64) for st in ("0", "1")]
+    for S, L, N, staged, block in runs:
+        ang, segs, org = made_up_batch(S, L, N, 60 + block)
+        ref = _host_batch(frames_harness, ang, segs, kind, org)
+        out, p_out = guarded(S * L * N, 108)
+        params = [lib.leg_params_from_arrays(s, np.zeros((7, 2)), np.zeros(27)) for s in segs]
+        with switches(SEQIK_FRAMES_STAGED=staged, SEQIK_FRAMES_BLOCK=str(block), SEQIK_FRAMES_GRID="3"):
+            lib.link_frames_device(torch.from_numpy(ang).cuda(), S, L, N, params, p_out, kind=kind,
+                                   d_origin=torch.from_numpy(org).cuda(), stream=torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+        assert same_bits(unguarded(out, 108).reshape(ref.shape), ref), (kind, S, L, N, staged, block)
 
 
 @pytest.mark.gpu
