@@ -10,15 +10,14 @@
 //
 // Here: a kernel extracts the seven series per leg from the RAW key points (with numpy's rounding sequence:
 // sqrt((dx*dx + dy*dy) + dz*dz)), hipCUB radix-sorts each series (plain library sort; order statistics are
-// exact whatever the algorithm), and the requested ranks are returned.  The caller applies numpy's own
+// exact whatever the algorithm), and the requested ranks are returned -- the sort loop, the pick kernel and the
+// handle's open / close are seqik_order_stats.hpp, shared with seqik_head_align.hip.  The caller applies numpy's own
 // interpolation / mean / scale formulas to them (seqikpy_amd/alignment.py), so the affine constants are
 // bit-identical to the reference's.  Slabs can be added one at a time (streaming): the order of the frames does
 // not matter.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <new>
 
-#include "seqik_runtime.hpp"
+#include "seqik_order_stats.hpp"
 
 namespace {
 
@@ -56,27 +55,14 @@ __global__ void __launch_bounds__(256) seqik_align_extract_kernel(
     }
 }
 
-__global__ void seqik_align_pick_kernel(const double *sorted, int64_t capacity, int64_t n, const int64_t *ranks,
-                                        int32_t n_ranks, int32_t n_series, double *out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_series * n_ranks) return;
-    const int s = i / n_ranks, r = i % n_ranks;
-    int64_t k = ranks[r];
-    if (k < 0) k = 0;
-    if (k > n - 1) k = n - 1;
-    out[i] = sorted[(int64_t)s * capacity + k];
-}
-
 }  // namespace
 
-struct SeqikAlignStats {
-    int device = 0;
+struct SeqikAlignStats : seqik::SeriesHandle {  // d_series: [n_legs][7][capacity]
     int32_t n_legs = 0;
     int64_t capacity = 0, count = 0;  // frames per leg: room / filled
-    double *d_series = nullptr;       // [n_legs][7][capacity]
     double *d_stage = nullptr;        // staging for host slabs
     size_t stage_bytes = 0;
+    ~SeqikAlignStats() { (void)hipFree(d_stage); }  // (_close deletes the handle on its device)
 };
 
 extern "C" {
@@ -87,20 +73,9 @@ int seqik_align_stats_open(SeqikAlignStats **out, int32_t n_legs, int64_t capaci
     *out = nullptr;
     if (n_legs <= 0 || n_legs > 8 || capacity_frames <= 0)
         return bad_arg("seqik_align_stats_open", "bad sizes (n_legs 1..8, capacity_frames > 0)");
-    SeqikAlignStats *s = new (std::nothrow) SeqikAlignStats;
-    if (!s) return bad_arg("seqik_align_stats_open", "out of host memory");
-    s->n_legs = n_legs;
-    s->capacity = capacity_frames;
-    seqik::DeviceScope scope;
-    hipError_t e = seqik::resolve_device(opt ? opt->device : -1, &s->device);
-    if (e == hipSuccess) e = scope.enter(s->device);
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void **>(&s->d_series), sizeof(double) * kSeries * n_legs * capacity_frames);
-    if (e != hipSuccess) {
-        delete s;
-        return seqik::hip_fail(e, "seqik_align_stats_open");
-    }
-    *out = s;
+    if (int rc = seqik::open_series("seqik_align_stats_open", opt, (size_t)kSeries * n_legs * capacity_frames, out)) return rc;
+    (*out)->n_legs = n_legs;
+    (*out)->capacity = capacity_frames;
     return SEQIK_OK;
 }
 
@@ -170,34 +145,11 @@ int seqik_align_stats_finish(SeqikAlignStats *s, const int64_t *ranks, int32_t n
     if (s->count > 0x7fffffffLL) return bad_arg("seqik_align_stats_finish", "more than 2^31 frames per leg");
     seqik::DeviceScope scope;
     HIP_TRY(scope.enter(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const int n_series = kSeries * s->n_legs;
-    double *d_sorted = nullptr, *d_out = nullptr;
-    int64_t *d_ranks = nullptr;
-    void *d_tmp = nullptr;
-    const int rc = [&]() -> int {  // (the temporaries are freed on every path out)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_sorted), sizeof(double) * (size_t)n_series * s->capacity));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_out), sizeof(double) * n_series * n_ranks));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_ranks), sizeof(int64_t) * n_ranks));
-        HIP_TRY(hipMemcpyAsync(d_ranks, ranks, sizeof(int64_t) * n_ranks, hipMemcpyHostToDevice, stream));
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, s->d_series, d_sorted, (int)s->count, 0, 64, stream));
-        HIP_TRY(hipMalloc(&d_tmp, tmp_bytes));
-        for (int i = 0; i < n_series; ++i) {  // one full-width sort per series (a segmented sort would
-            hipError_t e_ = hipcub::DeviceRadixSort::SortKeys(       // put one block on each of these huge segments)
-                d_tmp, tmp_bytes, s->d_series + (int64_t)i * s->capacity, d_sorted + (int64_t)i * s->capacity, (int)s->count,
-                0, 64, stream);
-            if (e_ != hipSuccess) return seqik::hip_fail(e_, "hipcub::DeviceRadixSort::SortKeys");
-        }
-        hipLaunchKernelGGL(seqik_align_pick_kernel, dim3((n_series * n_ranks + 63) / 64), dim3(64), 0, stream, d_sorted,
-                           s->capacity, s->count, d_ranks, n_ranks, n_series, d_out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_series * n_ranks, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return SEQIK_OK;
-    }();
-    (void)hipFree(d_sorted); (void)hipFree(d_out); (void)hipFree(d_ranks); (void)hipFree(d_tmp);
-    return rc;
+    // the sorts run on a pooled context's stream: what _add enqueued on the caller's stream is waited for first
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
+    const int64_t count = s->count;  // every series: its first `count` of `capacity` values, one set of ranks
+    return seqik::order_statistics(s->device, s->d_series, s->capacity, kSeries * s->n_legs, count, ranks, 1, n_ranks,
+                                   [count](int) { return seqik::RankPick{count, 0}; }, out);
 }
 
 int seqik_align_stats_reset(SeqikAlignStats *s)
@@ -207,16 +159,6 @@ int seqik_align_stats_reset(SeqikAlignStats *s)
     return SEQIK_OK;
 }
 
-int seqik_align_stats_close(SeqikAlignStats *s)
-{
-    if (!s) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    (void)scope.enter(s->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_series);
-    (void)hipFree(s->d_stage);
-    delete s;
-    return SEQIK_OK;
-}
+int seqik_align_stats_close(SeqikAlignStats *s) { return seqik::close_series(s); }
 
 }  // extern "C"

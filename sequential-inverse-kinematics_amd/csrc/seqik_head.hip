@@ -1,11 +1,11 @@
-// seqik_head.hip -- head / antenna angle kernel and its C ABI entry points (include/seqik.h).
+// seqik_head.hip -- head / antenna angle kernel and its C ABI entry points (include/seqik.h).  The host side of a launch
+// (argument rules, grid, choice of kernel, the host entry point's buffers) is seqik_head_launch.hpp, shared with
+// seqik_head_align.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "seqik_core.hpp"
-#include "seqik_head.hpp"
-#include "seqik_runtime.hpp"
+#include "seqik_head_launch.hpp"
 
 namespace {
 
@@ -75,17 +75,10 @@ __global__ void __launch_bounds__(256) seqik_signed_angle_kernel(const double *v
         out[t] = seqik::signed_angle3(v1 + t * s1, v2 + t * s2, axis);
 }
 
-// the checks of both head entry points
-int head_validate(const void *r_head, const void *l_head, const void *neck, const void *angles, int64_t n_frames,
-                  int64_t neck_stride, int32_t n_points, int32_t compute_ant)
-{
-    if (!r_head || !l_head || !neck || !angles || n_frames < 0 || (neck_stride != 0 && neck_stride != 3) || n_points < 1)
-        return bad_arg("seqik_head_angles", "bad argument");
-    if (compute_ant && n_points < 2)
-        return bad_arg("seqik_head_angles", "the antenna angles need two key points per side "
-                                            "(antenna base and tip); pass compute_ant = 0 for single-point records");
-    return SEQIK_OK;
-}
+// by seqik::HeadVariant: per-lane loads + given roll, staged, per-lane
+const seqik::HeadKernel<seqik::HeadArgs> kHeadKernels[3] = {seqik_head_kernel<false, true>, seqik_head_kernel<true>,
+                                                            seqik_head_kernel<false>};
+constexpr const char *kWho = "seqik_head_angles";
 
 }  // namespace
 
@@ -104,24 +97,12 @@ int seqik_head_angles_ex_device(const double *d_r_head, const double *d_l_head, 
                                 double rest_antenna_pitch, int32_t compute_ant, const double *d_head_roll,
                                 double *d_angles, void *hip_stream)
 {
-    if (int rc = head_validate(d_r_head, d_l_head, d_neck, d_angles, n_frames, neck_stride, n_points, compute_ant)) return rc;
+    if (int rc = seqik::check_head_args(kWho, d_r_head, d_l_head, d_neck, d_angles, n_frames, neck_stride, n_points, compute_ant))
+        return rc;
     if (n_frames == 0) return SEQIK_OK;
-    seqik::HeadArgs a;
-    a.r_head = d_r_head; a.l_head = d_l_head; a.neck = d_neck; a.neck_stride = neck_stride;
-    a.rec = 3 * (int64_t)n_points; a.roll_in = compute_ant ? d_head_roll : nullptr;
-    a.rest_head_pitch = rest_head_pitch; a.rest_antenna_pitch = rest_antenna_pitch;
-    a.angles = d_angles; a.n_frames = n_frames; a.compute_ant = compute_ant;
-    int64_t blocks = (n_frames + 255) / 256;
-    // (round 5: 64 workgroups per CU in the grid instead of 8 -- at most six are resident (LDS), the rest queue up and each
-    // makes fewer grid-stride rounds: 16 M frames 0.483 -> 0.473 ms, 64 M 1.955 -> 1.902 ms; profiles/r05_head_blocks_per_cu.txt)
-    static const int per_cu = getenv("SEQIK_HEAD_BLOCKS_PER_CU") ? atoi(getenv("SEQIK_HEAD_BLOCKS_PER_CU")) : 64;
-    if (blocks > 256 * (int64_t)per_cu) blocks = 256 * (int64_t)per_cu;  // grid-stride beyond per_cu blocks per CU
-    // staged loads need 16-byte aligned records and read the antenna tips too (only worth it when they are used)
-    const bool staged = compute_ant && n_points == 2 && ((reinterpret_cast<uintptr_t>(d_r_head) | reinterpret_cast<uintptr_t>(d_l_head)) & 15) == 0;
-    if (a.roll_in) hipLaunchKernelGGL((seqik_head_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-    else if (staged) hipLaunchKernelGGL(seqik_head_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-    else hipLaunchKernelGGL(seqik_head_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
-    return seqik::launched();
+    const seqik::HeadArgs a = seqik::head_args(d_r_head, d_l_head, n_frames, n_points, d_neck, neck_stride, rest_head_pitch,
+                                               rest_antenna_pitch, compute_ant, d_head_roll, d_angles);
+    return seqik::launch_head(kHeadKernels, seqik::plan_head(a), a, hip_stream);
 }
 
 int seqik_head_angles(const double *r_head, const double *l_head, int64_t n_frames, const double *neck,
@@ -136,19 +117,17 @@ int seqik_head_angles_ex(const double *r_head, const double *l_head, int64_t n_f
                          int64_t neck_stride, double rest_head_pitch, double rest_antenna_pitch, int32_t compute_ant,
                          const double *head_roll, double *angles, const SeqikOptions *opt)
 {
-    if (int rc = head_validate(r_head, l_head, neck, angles, n_frames, neck_stride, n_points, compute_ant)) return rc;
+    if (int rc = seqik::check_head_args(kWho, r_head, l_head, neck, angles, n_frames, neck_stride, n_points, compute_ant))
+        return rc;
     if (n_frames == 0) return SEQIK_OK;
-    const size_t n = (size_t)n_frames;
     seqik::HostCall call;
-    double *d_roll, *d_r, *d_l, *d_n, *d_a;
-    call.upload(d_roll, n, compute_ant ? head_roll : nullptr);
-    call.upload(d_r, 3 * n_points * n, r_head);
-    call.upload(d_l, 3 * n_points * n, l_head);
-    call.upload(d_n, neck_stride ? 3 * n : 3, neck);
-    call.download(d_a, 7 * n, angles, (compute_ant ? 7 : 3) * n);
+    seqik::HeadBuffers d;
+    d.declare(call, seqik::head_args(r_head, l_head, n_frames, n_points, neck, neck_stride, rest_head_pitch,
+                                     rest_antenna_pitch, compute_ant, head_roll, angles));
     if (int rc = call.begin(opt ? opt->device : -1)) return rc;
-    return call.finish(seqik_head_angles_ex_device(d_r, d_l, n_frames, n_points, d_n, neck_stride, rest_head_pitch,
-                                                   rest_antenna_pitch, compute_ant, d_roll, d_a, call.stream()));
+    return call.finish(seqik_head_angles_ex_device(d.r_head, d.l_head, n_frames, n_points, d.neck, neck_stride,
+                                                   rest_head_pitch, rest_antenna_pitch, compute_ant, d.head_roll, d.angles,
+                                                   call.stream()));
 }
 
 int seqik_signed_angles(const double *v1, int64_t v1_stride, const double *v2, int64_t v2_stride, const double *axis,

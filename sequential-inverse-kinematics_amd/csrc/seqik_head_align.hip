@@ -10,15 +10,15 @@
 //     not selected holds +inf in the four restricted series, so rank r < n_stat of the full-length sort IS rank r of
 //     the subset and no compaction is needed (order statistics do not depend on the order of the subset);
 //   * seqik_head_raw_kernel is the head / antenna angle kernel of seqik_head.hip with the map in its prologue.
+// Shared with the older units: the handle's open / close, the sort loop and the pick kernel with seqik_align.hip
+// (seqik_order_stats.hpp); the host side of the angle launch with seqik_head.hip (seqik_head_launch.hpp).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-#include <new>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "seqik_core.hpp"
 #include "seqik_head_align.hpp"
-#include "seqik_runtime.hpp"
+#include "seqik_head_launch.hpp"
+#include "seqik_order_stats.hpp"
 
 namespace {
 
@@ -109,18 +109,6 @@ __global__ void __launch_bounds__(kTile) seqik_head_align_extract_kernel(Extract
     if (tid < 3 && s_cnt[tid]) atomicAdd(&a.counters[tid], (unsigned long long)s_cnt[tid]);
 }
 
-// out[r] = sorted[min(max(ranks[r], 0), limit - 1)] (the pick of seqik_align.hip for one series with a limit of its own)
-__global__ void seqik_head_align_pick_kernel(const double *sorted, int64_t limit, const int64_t *ranks, int32_t n_ranks,
-                                             double *out)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_ranks) return;
-    int64_t k = ranks[r];
-    if (k < 0) k = 0;
-    if (k > limit - 1) k = limit - 1;  // limit >= 1 (checked by the caller): 0 <= k < limit <= n
-    out[r] = sorted[k];
-}
-
 // ---- fused map + head / antenna angles -------------------------------------------------------------------------------
 
 struct HeadRawArgs {
@@ -204,18 +192,19 @@ __global__ void __launch_bounds__(256) seqik_head_raw_kernel(HeadRawArgs k)
     }
 }
 
-constexpr const char *kWhoRaw = "seqik_head_angles_raw";
+// [aligned records wanted][seqik::HeadVariant: per-lane loads + given roll, staged, per-lane]
+const seqik::HeadKernel<HeadRawArgs> kRawKernels[2][3] = {
+    {seqik_head_raw_kernel<false, true, false>, seqik_head_raw_kernel<true, false, false>, seqik_head_raw_kernel<false, false, false>},
+    {seqik_head_raw_kernel<false, true, true>, seqik_head_raw_kernel<true, false, true>, seqik_head_raw_kernel<false, false, true>}};
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+constexpr const char *kWhoRaw = "seqik_head_angles_raw";
 
 }  // namespace
 
-struct SeqikHeadAlignStats {
-    int device = 0;
+struct SeqikHeadAlignStats : seqik::SeriesHandle {  // d_series: [2][5][n] of the last _select, within [10 * capacity]
     int64_t capacity = 0;
-    int64_t n = 0;                // frames of the last _select (0: none yet)
+    int64_t n = 0;  // frames of the last _select (0: none yet)
     int64_t n_stat[2] = {0, 0};
-    double *d_series = nullptr;   // [2][5][n] of the last _select, within [10 * capacity]
 };
 
 extern "C" {
@@ -227,19 +216,8 @@ int seqik_head_align_stats_open(SeqikHeadAlignStats **out, int64_t capacity_fram
     *out = nullptr;
     if (capacity_frames < 3 || capacity_frames > 0x7fffffffLL)
         return bad_arg(who, "capacity_frames must lie in 3 .. 2^31 - 1");
-    SeqikHeadAlignStats *s = new (std::nothrow) SeqikHeadAlignStats;
-    if (!s) return bad_arg(who, "out of host memory");
-    s->capacity = capacity_frames;
-    seqik::DeviceScope scope;
-    hipError_t e = seqik::resolve_device(opt ? opt->device : -1, &s->device);
-    if (e == hipSuccess) e = scope.enter(s->device);
-    if (e == hipSuccess)
-        e = hipMalloc(reinterpret_cast<void **>(&s->d_series), sizeof(double) * 2 * kHeadSeries * (size_t)capacity_frames);
-    if (e != hipSuccess) {
-        delete s;
-        return seqik::hip_fail(e, who);
-    }
-    *out = s;
+    if (int rc = seqik::open_series(who, opt, 2 * kHeadSeries * (size_t)capacity_frames, out)) return rc;
+    (*out)->capacity = capacity_frames;
     return SEQIK_OK;
 }
 
@@ -287,50 +265,22 @@ int seqik_head_align_stats_pick(SeqikHeadAlignStats *s, const int64_t *ranks_sta
     if (n_ranks <= 0 || n_ranks > 16) return bad_arg(who, "n_ranks must be 1..16");
     if (s->n == 0) return bad_arg(who, "no recording was selected (call seqik_head_align_stats_select first)");
     if (s->n_stat[0] == 0 || s->n_stat[1] == 0) return bad_arg(who, "the threshold selected no frame on one side");
-    const int64_t n = s->n;
-    int64_t h_ranks[3 * 16];
+    int64_t h_ranks[3 * 16];  // rows: the stationary set of R, of L, all frames
     for (int r = 0; r < n_ranks; ++r) {
         h_ranks[r] = ranks_stat[r];
         h_ranks[n_ranks + r] = ranks_stat[n_ranks + r];
         h_ranks[2 * n_ranks + r] = ranks_all[r];
     }
-    seqik::DeviceScope scope;
-    HIP_TRY(scope.enter(s->device));
-    size_t tmp_bytes = 0;  // (a size query: no work is enqueued)
-    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, s->d_series, s->d_series, (int)n, 0, 64, nullptr));
-    seqik::HostCall call;
-    double *d_sorted = nullptr, *d_out = nullptr;
-    int64_t *d_ranks = nullptr;
-    char *d_tmp = nullptr;
-    call.scratch(d_sorted, (size_t)n);
-    call.scratch(d_tmp, tmp_bytes);
-    call.upload(d_ranks, 3 * (size_t)n_ranks, static_cast<const int64_t *>(h_ranks));
-    call.download(d_out, 2 * kHeadSeries * (size_t)n_ranks, out);
-    if (int rc = call.begin(s->device)) return rc;
-    for (int side = 0; side < 2; ++side) {
-        for (int j = 0; j < kHeadSeries; ++j) {  // one full-width sort per series, its ranks picked before the next one
-            const int i = side * kHeadSeries + j;
-            hipError_t e = hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp_bytes, s->d_series + (int64_t)i * n, d_sorted, (int)n, 0,
-                                                             64, call.stream());
-            if (e != hipSuccess) return seqik::hip_fail(e, "hipcub::DeviceRadixSort::SortKeys");
-            const bool all = j == kHeadSeries - 1;
-            hipLaunchKernelGGL(seqik_head_align_pick_kernel, dim3(1), dim3(64), 0, call.stream(), d_sorted,
-                               all ? n : s->n_stat[side], d_ranks + (all ? 2 : side) * n_ranks, n_ranks, d_out + i * n_ranks);
-            if (int rc = seqik::launched()) return rc;
-        }
-    }
-    return call.finish(SEQIK_OK);
+    // a side's first four series hold its n_stat selected values in front of +inf; the fifth (len) counts every frame
+    auto pick_of = [s](int i) {
+        const int side = i / kHeadSeries;
+        const bool all = i % kHeadSeries == kHeadSeries - 1;
+        return seqik::RankPick{all ? s->n : s->n_stat[side], all ? 2 : side};
+    };
+    return seqik::order_statistics(s->device, s->d_series, s->n, 2 * kHeadSeries, s->n, h_ranks, 3, n_ranks, pick_of, out);
 }
 
-int seqik_head_align_stats_close(SeqikHeadAlignStats *s)
-{
-    if (!s) return SEQIK_OK;
-    seqik::DeviceScope scope;
-    (void)scope.enter(s->device);
-    (void)hipFree(s->d_series);  // (every call on the handle synchronised before it returned)
-    delete s;
-    return SEQIK_OK;
-}
+int seqik_head_align_stats_close(SeqikHeadAlignStats *s) { return seqik::close_series(s); }
 
 int seqik_head_angles_raw_device(const double *d_r_head, const double *d_l_head, int64_t n_frames, int32_t n_points,
                                  const double *d_neck, int64_t neck_stride, double rest_head_pitch,
@@ -338,41 +288,20 @@ int seqik_head_angles_raw_device(const double *d_r_head, const double *d_l_head,
                                  const SeqikHeadAffine *affine, double *d_angles, double *d_r_aligned,
                                  double *d_l_aligned, void *hip_stream)
 {
-    if (int rc = seqik::check_head_args(kWhoRaw, d_r_head, d_l_head, d_neck, d_angles, affine, n_frames, neck_stride,
-                                        n_points, compute_ant))
+    if (!affine) return bad_arg(kWhoRaw, "null pointer");
+    if (int rc = seqik::check_head_args(kWhoRaw, d_r_head, d_l_head, d_neck, d_angles, n_frames, neck_stride, n_points, compute_ant))
         return rc;
     // asynchronous: a fault an earlier launch left in this stream's word is reported now (this kernel raises none)
     if (int rc = seqik_check_faults_stream(hip_stream)) return rc;
     if (n_frames == 0) return SEQIK_OK;
     HeadRawArgs k;
-    seqik::HeadArgs &a = k.h;
-    a.r_head = d_r_head; a.l_head = d_l_head; a.neck = d_neck; a.neck_stride = neck_stride;
-    a.rec = 3 * (int64_t)n_points; a.roll_in = compute_ant ? d_head_roll : nullptr;
-    a.rest_head_pitch = rest_head_pitch; a.rest_antenna_pitch = rest_antenna_pitch;
-    a.angles = d_angles; a.n_frames = n_frames; a.compute_ant = compute_ant;
+    k.h = seqik::head_args(d_r_head, d_l_head, n_frames, n_points, d_neck, neck_stride, rest_head_pitch, rest_antenna_pitch,
+                           compute_ant, d_head_roll, d_angles);
     k.affine[0] = affine[0]; k.affine[1] = affine[1];
     k.r_aligned = d_r_aligned; k.l_aligned = d_l_aligned;
     k.n_points = n_points; k.out_rec = n_points >= 2 ? 6 : 3;
-    int64_t blocks = (n_frames + 255) / 256;
-    // the grid of seqik_head_angles_ex_device: 64 workgroups per CU, grid-stride beyond (same environment override)
-    static const int per_cu = getenv("SEQIK_HEAD_BLOCKS_PER_CU") ? atoi(getenv("SEQIK_HEAD_BLOCKS_PER_CU")) : 64;
-    if (blocks > 256 * (int64_t)per_cu) blocks = 256 * (int64_t)per_cu;
-    const bool with_out = d_r_aligned || d_l_aligned;
-    // staged loads / stores need 16-byte aligned two-point records and read the antenna tips too
-    const bool staged = compute_ant && n_points == 2 && aligned16(d_r_head) && aligned16(d_l_head) &&
-                        aligned16(d_r_aligned) && aligned16(d_l_aligned);
-    const dim3 grid((unsigned)blocks), block(256);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-#define HEAD_RAW_LAUNCH(ST, ROLL)                                                                              \
-    do {                                                                                                       \
-        if (with_out) hipLaunchKernelGGL((seqik_head_raw_kernel<ST, ROLL, true>), grid, block, 0, s, k);        \
-        else hipLaunchKernelGGL((seqik_head_raw_kernel<ST, ROLL, false>), grid, block, 0, s, k);                \
-    } while (0)
-    if (a.roll_in) HEAD_RAW_LAUNCH(false, true);
-    else if (staged) HEAD_RAW_LAUNCH(true, false);
-    else HEAD_RAW_LAUNCH(false, false);
-#undef HEAD_RAW_LAUNCH
-    return seqik::launched();
+    return seqik::launch_head(kRawKernels[d_r_aligned || d_l_aligned], seqik::plan_head(k.h, d_r_aligned, d_l_aligned), k,
+                              hip_stream);
 }
 
 int seqik_head_angles_raw(const double *r_head, const double *l_head, int64_t n_frames, int32_t n_points,
@@ -380,24 +309,22 @@ int seqik_head_angles_raw(const double *r_head, const double *l_head, int64_t n_
                           int32_t compute_ant, const double *head_roll, const SeqikHeadAffine *affine, double *angles,
                           double *r_aligned, double *l_aligned, const SeqikOptions *opt)
 {
-    if (int rc = seqik::check_head_args(kWhoRaw, r_head, l_head, neck, angles, affine, n_frames, neck_stride, n_points,
-                                        compute_ant))
+    if (!affine) return bad_arg(kWhoRaw, "null pointer");
+    if (int rc = seqik::check_head_args(kWhoRaw, r_head, l_head, neck, angles, n_frames, neck_stride, n_points, compute_ant))
         return rc;
     if (n_frames == 0) return SEQIK_OK;
-    const size_t n = (size_t)n_frames, out_rec = n_points >= 2 ? 6 : 3;
+    const size_t out_doubles = (n_points >= 2 ? 6 : 3) * (size_t)n_frames;
     seqik::HostCall call;
-    double *d_roll, *d_r, *d_l, *d_n, *d_a, *d_ra, *d_la;
-    call.upload(d_roll, n, compute_ant ? head_roll : nullptr);
-    call.upload(d_r, 3 * (size_t)n_points * n, r_head);
-    call.upload(d_l, 3 * (size_t)n_points * n, l_head);
-    call.upload(d_n, neck_stride ? 3 * n : 3, neck);
-    call.download(d_a, 7 * n, angles, (compute_ant ? 7 : 3) * n);
-    call.download(d_ra, out_rec * n, r_aligned);
-    call.download(d_la, out_rec * n, l_aligned);
+    seqik::HeadBuffers d;
+    double *d_ra, *d_la;
+    d.declare(call, seqik::head_args(r_head, l_head, n_frames, n_points, neck, neck_stride, rest_head_pitch,
+                                     rest_antenna_pitch, compute_ant, head_roll, angles));
+    call.download(d_ra, out_doubles, r_aligned);
+    call.download(d_la, out_doubles, l_aligned);
     if (int rc = call.begin(opt ? opt->device : -1)) return rc;
-    return call.finish(seqik_head_angles_raw_device(d_r, d_l, n_frames, n_points, d_n, neck_stride, rest_head_pitch,
-                                                    rest_antenna_pitch, compute_ant, d_roll, affine, d_a, d_ra, d_la,
-                                                    call.stream()));
+    return call.finish(seqik_head_angles_raw_device(d.r_head, d.l_head, n_frames, n_points, d.neck, neck_stride,
+                                                    rest_head_pitch, rest_antenna_pitch, compute_ant, d.head_roll, affine,
+                                                    d.angles, d_ra, d_la, call.stream()));
 }
 
 }  // extern "C"

@@ -56,12 +56,12 @@ inline int check_segments(const char *who, const SeqikLegParams *legs, int32_t n
     return SEQIK_OK;
 }
 
-// The argument rules of the head / antenna entry points that take RAW key points (seqik_head_align.hip); the same rules
-// as seqik_head_angles_ex: one neck or one per frame, at least one key point per side, two for the antenna angles.
+// The argument rules of every head / antenna entry point (seqik_head.hip, seqik_head_align.hip): one neck or one per
+// frame, at least one key point per side, two for the antenna angles.
 inline int check_head_args(const char *who, const void *r_head, const void *l_head, const void *neck, const void *angles,
-                           const void *affine, int64_t n_frames, int64_t neck_stride, int32_t n_points, int32_t compute_ant)
+                           int64_t n_frames, int64_t neck_stride, int32_t n_points, int32_t compute_ant)
 {
-    if (!r_head || !l_head || !neck || !angles || !affine) return bad_arg(who, "null pointer");
+    if (!r_head || !l_head || !neck || !angles) return bad_arg(who, "null pointer");
     if (n_frames < 0 || n_frames > INT64_MAX / (8 * 3 * (int64_t)(n_points > 0 ? n_points : 1)))
         return bad_arg(who, "n_frames is negative or too large");
     if (neck_stride != 0 && neck_stride != 3) return bad_arg(who, "neck_stride must be 0 or 3");

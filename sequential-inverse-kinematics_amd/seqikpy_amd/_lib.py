@@ -27,7 +27,8 @@ COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_
                  "seqik_head_align.hip", "seqik_jacobian.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
-                "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp"]
+                "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
+                "seqik_order_stats.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -800,7 +801,7 @@ def resample_der_device(d_y, n_chains, n_frames, width, original_ts, new_ts, d_v
 HEAD_ALIGN_EXPORTED_SYMBOLS = [sig[0] for sig in SIGNATURES["seqik_head_align.h"]]
 #: what the antenna-alignment kernels are compiled from (``csrc_sha256(HEAD_ALIGN_SOURCES)`` ties
 #: profiles/head_align.json to a build; ``KERNEL_SOURCES`` stays the solver's own set)
-HEAD_ALIGN_SOURCES = ["seqik_head.hpp", "seqik_head_align.hpp", "seqik_head_align.hip"]
+HEAD_ALIGN_SOURCES = ["seqik_head.hpp", "seqik_head_align.hpp", "seqik_order_stats.hpp", "seqik_head_align.hip"]
 HEAD_STAT_THRESHOLD = 5e-5
 
 

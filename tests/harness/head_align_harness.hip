@@ -2,9 +2,23 @@
 //
 // Runs the per-element rules of the antenna alignment (csrc/seqik_head_align.hpp, `__host__ __device__`) on the HOST, one
 // frame after the other, so that the CPU-only test tier can compare them bit for bit with numpy and with the reference's
-// aligned output; the GPU tier compares the kernels with numpy on the host.  Built by tests/test_head_alignment.py with
-// `hipcc --offload-host-only`.
+// aligned output; the GPU tier compares the kernels with numpy on the host.  Also hands out the launch plan of the head
+// kernels (csrc/seqik_head_launch.hpp, host code).  Built by tests/test_head_alignment.py with `hipcc --offload-host-only`.
 #include "../../sequential-inverse-kinematics_amd/csrc/seqik_head_align.hpp"
+#include "../../sequential-inverse-kinematics_amd/csrc/seqik_head_launch.hpp"
+
+// plan_head as the head entry points call it (the pointers are only looked at, never followed; r_aligned / l_aligned:
+// the fused kernel's optional outputs, null for the plain one) -> out [2]: workgroups, seqik::HeadVariant
+extern "C" void harness_head_plan(int64_t n_frames, int32_t n_points, int32_t compute_ant, const double *r_head,
+                                  const double *l_head, const double *head_roll, const double *r_aligned,
+                                  const double *l_aligned, int64_t *out)
+{
+    const seqik::HeadPlan p = seqik::plan_head(
+        seqik::head_args(r_head, l_head, n_frames, n_points, nullptr, 0, 0.0, 0.0, compute_ant, head_roll, nullptr), r_aligned,
+        l_aligned);
+    out[0] = p.blocks;
+    out[1] = p.variant;
+}
 
 // One side.  head [n][n_points][3], thorax [n][n_thorax_points][3] -> d [n], len [n], mask [n] (1 = stationary; the last
 // two frames are no candidates); returns the number of stationary frames.
@@ -52,10 +66,7 @@ extern "C" void harness_head_angles_plain(const double *r_head, const double *l_
                                           double rest_antenna_pitch, int32_t compute_ant, const double *head_roll,
                                           double *angles)
 {
-    seqik::HeadArgs a;
-    a.r_head = r_head; a.l_head = l_head; a.neck = neck; a.neck_stride = neck_stride;
-    a.rec = 3 * (int64_t)n_points; a.roll_in = compute_ant ? head_roll : nullptr;
-    a.rest_head_pitch = rest_head_pitch; a.rest_antenna_pitch = rest_antenna_pitch;
-    a.angles = angles; a.n_frames = n; a.compute_ant = compute_ant;
+    const seqik::HeadArgs a = seqik::head_args(r_head, l_head, n, n_points, neck, neck_stride, rest_head_pitch,
+                                               rest_antenna_pitch, compute_ant, head_roll, angles);
     for (int64_t t = 0; t < n; ++t) seqik::head_angles_frame(a, t);
 }

@@ -12,7 +12,8 @@ CPU tier: the input generators really put the requested ranks where the GPU test
 and last element, on either side of the sign change, on a denormal), the numpy stand-in of test_alignment.py equals the
 reference, and ``AlignPose.leg_affines(on_gpu=True)`` equals the host path / falls back to it on non-finite input.
 GPU tier: key counts on both sides of every algorithm switch of the library sort, the grid-stride loop of the extraction,
-capacity != count, slabs / sequences / layouts from host and device memory, ``leg_affines`` on the real library, and the
+capacity != count, slabs / sequences / layouts from host and device memory, ``finish`` on another stream than ``add``,
+handles of different sizes sharing the pooled arena with the head statistics, ``leg_affines`` on the real library, and the
 refusal of host layouts whose chains do not lie inside their chain stride.
 
 Hard inputs (each a (S, L, N, 5, 3) array from a seeded generator):
@@ -554,6 +555,53 @@ def test_device_resident_input_on_a_side_stream(hiplib, four_sequences):
         st.add(d_padded, n_seq=S, n_frames=N, layout=L_(N * 20 + 37, 4, 20, 0, 0, 0), on_device=True, stream=side)
         assert_same(st.finish(ranks, stream=side), want, "padded")
     side.synchronize()
+
+
+@pytest.mark.gpu
+def test_finish_on_the_default_stream_after_a_synchronised_side_stream_add(hiplib, four_sequences):
+    """The documented way to mix streams: ``add`` with device memory is asynchronous on its stream, the caller
+    synchronises that stream, and ``finish`` on the default stream (0) sees the frames."""
+    import torch
+    pose, ranks, want = four_sequences
+    S, L, N = pose.shape[:3]
+    side = torch.cuda.Stream()
+    assert side.cuda_stream != 0
+    with torch.cuda.stream(side):
+        d_pose = torch.from_numpy(np.array(pose)).cuda()
+    with hiplib.AlignStats(L, S * N) as st:
+        st.add(d_pose, n_seq=S, n_frames=N, on_device=True, stream=side)
+        side.synchronize()
+        assert_same(st.finish(ranks), want, "finish on stream 0")
+        assert_same(st.finish(ranks, stream=side), want, "and again on the side stream")
+
+
+@pytest.mark.gpu
+def test_handles_of_different_sizes_and_a_head_call_share_the_pooled_arena(hiplib):
+    """``finish`` keeps its one-series sort buffer and the library sort's temporaries in the arena of a pooled host-call
+    context, which every host-buffer call borrows and regrows: two handles open at once, 1 leg x 1025 frames and 8 legs
+    x 5000 frames, finished small, large, small again with the head statistics (whose uploads take the same arena) in
+    between.  No call's scratch may survive as another's input: every result against numpy."""
+    from test_head_alignment import fixture_raw, np_series
+    small, large = mix(1, 1, 1025, seed=5), mix(1, 8, 5000, seed=6)
+    r_small, r_large = ranks_for(1025), ranks_for(5000)
+    want_small, want_large = reference([small], r_small), reference([large], r_large)
+    _, raw = fixture_raw()
+    head_ranks = lambda n: [0, n // 2, n - 1]  # noqa: E731
+    with hiplib.AlignStats(1, 1025) as a, hiplib.AlignStats(8, 5000) as b:
+        a.add(small)
+        b.add(large)
+        assert_same(a.finish(r_small), want_small, "small, first")
+        assert_same(b.finish(r_large), want_large, "large: the arena grows")
+        res = hiplib.head_align_stats(raw["R_head"], raw["L_head"], raw["Thorax"], head_ranks)
+        assert_same(a.finish(r_small), want_small, "small, inside the larger arena after the head call")
+        assert_same(b.finish(r_large), want_large, "large again")
+    assert res["n_nonfinite"] == 0 and res["order"] is not None
+    for i, side in enumerate("RL"):
+        d, ln, mask = np_series(raw[f"{side}_head"], raw["Thorax"])
+        assert res["n_stat"][i] == mask.sum()
+        series = [raw[f"{side}_head"][mask, 0, c] for c in range(3)] + [d[mask], ln]
+        for j, v in enumerate(series):
+            assert np.array_equal(res["order"][i, j], np.sort(v)[head_ranks(len(v))]), (side, j)
 
 
 @pytest.mark.gpu

@@ -6,13 +6,15 @@ tests/golden/anipose_raw_cut.npz and numpy on the host, never the new code.
 
 CPU tier: header and exports; the per-element rules run on the host (tests/harness/head_align_harness.hip) against
 numpy; ``head_affine`` / ``align_head`` against the golden; the fused rule against the plain head rule on the golden's
-aligned points; argument handling.  GPU tier (`-m gpu`): ``head_affines(on_gpu=True)`` against the host constants, the
+aligned points; the launch plan of the head kernels; argument handling.  GPU tier (`-m gpu`): ``head_affines(on_gpu=True)`` against the host constants, the
 fused kernel against ``head_angles`` on host-aligned points, ``run_body_ik`` on raw key points, the example's flag."""
 import ctypes
 import importlib.util
+import json
 import os
 import pickle
 import re
+import subprocess
 import sys
 
 import numpy as np
@@ -228,6 +230,73 @@ def test_host_run_fused_rule_equals_head_rule_on_the_reference_aligned_points(he
         per_frame_neck = np.repeat(neck, 1500, axis=0) + np.linspace(0, 1e-3, 1500)[:, None]
         got, _, _ = head_align_harness.angles_raw(r_raw, l_raw, per_frame_neck, rest, pair)
         assert np.array_equal(got, head_align_harness.angles_plain(r_al, l_al, per_frame_neck, rest))
+
+
+_PLAN_CHILD = """
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+lib.harness_head_plan.restype = None
+lib.harness_head_plan.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5 + [
+    ctypes.POINTER(ctypes.c_int64)]
+out = (ctypes.c_int64 * 2)()
+plans = []
+for case in json.loads(sys.argv[2]):
+    lib.harness_head_plan(*case, out)
+    plans.append(list(out))
+print(json.dumps(plans))
+"""
+
+
+def _head_plans(so, cases, blocks_per_cu):
+    """plan_head for every case (n_frames, n_points, compute_ant, r_head, l_head, head_roll, r_aligned, l_aligned; the
+    pointers as addresses, 0 = null) in a child process, because SEQIK_HEAD_BLOCKS_PER_CU is read once per process
+    -> [(workgroups, variant)]."""
+    env = {k: v for k, v in os.environ.items() if k != "SEQIK_HEAD_BLOCKS_PER_CU"}
+    if blocks_per_cu is not None:
+        env["SEQIK_HEAD_BLOCKS_PER_CU"] = str(blocks_per_cu)
+    run = subprocess.run([sys.executable, "-c", _PLAN_CHILD, so, json.dumps(cases)], env=env, capture_output=True,
+                         text=True, timeout=120)
+    assert run.returncode == 0, run.stderr
+    return [tuple(p) for p in json.loads(run.stdout)]
+
+
+def test_head_launch_plan_grid_staging_and_kernel_choice(head_align_harness):
+    """The launch plan both head units share (csrc/seqik_head_launch.hpp), with the numbers each unit's own launch code
+    gave before it was shared: ceil(n / 256) workgroups, at most 256 * SEQIK_HEAD_BLOCKS_PER_CU (64 when unset); the
+    staged kernel only with compute_ant, two points per side and every array that takes part 16-byte aligned (an
+    aligned output that is not asked for is aligned); a given roll takes the per-lane + roll kernel whatever the rest."""
+    so = head_align_harness.lib._name
+    GIVEN_ROLL, STAGED, PER_LANE = 0, 1, 2
+    a, odd = 1 << 20, (1 << 20) + 8          # a 16-byte aligned address and one that is only 8-byte aligned
+    plain = lambda n, k=2, ant=1, r=a, l=a + 4800, roll=0, ra=0, la=0: [n, k, ant, r, l, roll, ra, la]  # noqa: E731
+    # the grid: one workgroup per CU at most, so that the cap of 256 is reached at 65 537 frames
+    sizes = [0, 1, 256, 257, 65536, 65537, 10_000_000]
+    got = _head_plans(so, [plain(n) for n in sizes], blocks_per_cu=1)
+    assert [g[0] for g in got] == [0, 1, 1, 2, 256, 256, 256] and {g[1] for g in got} == {STAGED}
+    # ... and the default of 64 per CU
+    full = 256 * 64 * 256
+    got = _head_plans(so, [plain(n) for n in (257, full - 256, full, full + 1, 6_000_000_000)], blocks_per_cu=None)
+    assert [g[0] for g in got] == [2, 256 * 64 - 1, 256 * 64, 256 * 64, 256 * 64]
+    # the choice of kernel
+    cases = {
+        "aligned, no outputs": (plain(1000), STAGED),
+        "aligned, both outputs": (plain(1000, ra=a + 9600, la=a + 19200), STAGED),
+        "aligned, one output": (plain(1000, la=a + 9600), STAGED),
+        "head angles only": (plain(1000, ant=0), PER_LANE),
+        "single-point records": (plain(1000, k=1, ant=0), PER_LANE),
+        "three points per side": (plain(1000, k=3), PER_LANE),
+        "r_head misaligned": (plain(1000, r=odd), PER_LANE),
+        "l_head misaligned": (plain(1000, l=odd), PER_LANE),
+        "r_aligned alone misaligned": (plain(1000, ra=odd, la=a + 9600), PER_LANE),
+        "l_aligned alone misaligned": (plain(1000, la=odd), PER_LANE),
+        "given roll, all aligned": (plain(1000, roll=a + 9600), GIVEN_ROLL),
+        "given roll, outputs": (plain(1000, roll=a + 9600, ra=a + 19200, la=a + 28800), GIVEN_ROLL),
+        "given roll, misaligned input": (plain(1000, roll=odd, r=odd), GIVEN_ROLL),
+        "given roll, misaligned output": (plain(1000, roll=a + 9600, ra=odd), GIVEN_ROLL),
+        "given roll without antenna angles": (plain(1000, ant=0, roll=a + 9600), PER_LANE),   # the roll is not read
+    }
+    got = _head_plans(so, [c for c, _ in cases.values()], blocks_per_cu=1)
+    assert {k: g for k, g in zip(cases, got)} == {k: (4, want) for k, (_, want) in cases.items()}
 
 
 def test_argument_handling(hiplib, monkeypatch):
