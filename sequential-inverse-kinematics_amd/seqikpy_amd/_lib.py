@@ -24,11 +24,11 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip", "seqik_jacobian.hip"]
+                 "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
-                "seqik_order_stats.hpp"]
+                "seqik_order_stats.hpp", "seqik_sensitivity.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -255,6 +255,13 @@ JACOBIAN_SIGNATURES = {
         ("seqik_leg_jacobians_device", _int, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _vp, _vp, _vp)),
 }
 
+# The same for the key-point sensitivity of the sequential fit (include/seqik_sensitivity.h): a fifth table.
+SENSITIVITY_SIGNATURES = {
+    "seqik_sensitivity.h": (
+        ("seqik_fit_sensitivity", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _f64, _dp, _dp, _ip, _i32),
+        ("seqik_fit_sensitivity_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _f64, _vp, _vp, _vp, _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -358,7 +365,8 @@ def load():
             raise SeqikLibraryError(f"{LIB_PATH} has ABI {L.seqik_abi_version()}, this package needs {ABI_VERSION}: "
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
-                           list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values())):
+                           list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values()) +
+                           list(SENSITIVITY_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -570,6 +578,72 @@ def leg_jacobians_device(d_angles, n_seq, n_legs, n_frames, legs, kind="seq", d_
     lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, kind)
     _call("seqik_leg_jacobians_device", *head, _ptr(d_qdot, "qdot", lf + (7,)), _ptr(d_jac, "jac", lf + (4, 3, 7)),
           _ptr(d_sigma, "sigma", lf + (8,)), _ptr(d_vel, "vel", lf + (4, 3)), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_sensitivity.h (key-point sensitivity of the sequential fit), additive to ABI 7
+SENSITIVITY_EXPORTED_SYMBOLS = [sig[0] for sig in SENSITIVITY_SIGNATURES["seqik_sensitivity.h"]]
+SENS_BOUND_TOL = 1e-6        # SEQIK_SENS_BOUND_TOL
+SENS_FLAG_BAD_INPUT = 1 << 16
+
+
+def sens_flag_held(dof: int) -> int:
+    """The flag bit of ``fit_sensitivity`` that says DOF ``dof`` (``DOFS`` order) sits on a limit and is held there."""
+    return 1 << dof
+
+
+def sens_flag_not_pd(stage: int) -> int:
+    """The flag bit of ``fit_sensitivity`` that says stage ``stage`` (1..4) is not at a strict minimum."""
+    return 1 << (7 + stage)
+
+
+def _sigma_batch(kp_sigma, slf):
+    """``kp_sigma`` (a scalar, (4,) or anything else that broadcasts) as a contiguous (S, L, N, 4) array; None stays None."""
+    if kp_sigma is None:
+        return None
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(kp_sigma, dtype=np.float64), tuple(slf) + (4,)))
+
+
+def fit_sensitivity(angles, pose, legs, kp_sigma=None, want_sens=True, want_flags=True, bound_tol=SENS_BOUND_TOL,
+                    device=-1):
+    """``seqik_fit_sensitivity`` on host arrays: the solved angles (S, L, N, 7) of the sequential chain and the aligned key
+    points (S, L, N, 5, 3) they were fitted to -> dict(sens (S, L, N, 7, 4, 3) or None, std (S, L, N, 7) or None, flags
+    (S, L, N) int32 or None).
+
+    ``sens[..., d, k, c]`` is the derivative of the fitted angle of ``DOFS[d]`` with respect to component c of aligned key
+    point k + 1: the response of the four sequential solves with their exact Hessians (not the pseudo-inverse of the
+    Jacobian), 0 for a joint that sits on a limit of ``legs[l].bounds`` (within ``bound_tol`` rad; <= 0: never) and is
+    pushed against it.  ``std`` (when ``kp_sigma`` -- a scalar, (4,), or anything that broadcasts to (S, L, N, 4):
+    the isotropic standard deviation of key points 1..4 -- is given): the standard deviation that noise gives every angle.
+    ``flags``: bits 0..6 DOF held (``sens_flag_held``), bits 8..11 stage not at a strict minimum (its rows are NaN;
+    ``sens_flag_not_pd``), bit 16 non-finite input (the leg-frame's values are NaN).  At least one of the three must be
+    asked for.  ``legs`` carry the segment lengths and the bounds."""
+    angles, (S, L, N), _, head = _angles_batch(angles, legs, 0)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.shape != (S, L, N, 5, 3):
+        raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    try:
+        sigma = _sigma_batch(kp_sigma, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_sigma must broadcast to {(S, L, N, 4)}, got {np.shape(kp_sigma)}") from None
+    sens = np.full((S, L, N, 7, 4, 3), np.nan) if want_sens else None
+    std = np.full((S, L, N, 7), np.nan) if sigma is not None else None
+    flags = np.zeros((S, L, N), dtype=np.int32) if want_flags else None
+    _call("seqik_fit_sensitivity", head[0], _data(pose), *head[1:], _data(sigma), float(bound_tol), _data(sens), _data(std),
+          _data(flags, _ip), int(device))
+    return dict(sens=sens, std=std, flags=flags)
+
+
+def fit_sensitivity_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_kp_sigma=0, d_sens=0, d_std=0, d_flags=0,
+                           bound_tol=SENS_BOUND_TOL, stream=None):
+    """``seqik_fit_sensitivity_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_sensitivity.h`` (``d_pose`` (S, L, N, 5, 3), ``d_kp_sigma`` (S, L, N, 4), ``d_sens`` (S, L, N, 7, 4, 3),
+    ``d_std`` (S, L, N, 7) doubles, ``d_flags`` (S, L, N) int32; 0 / None: not computed, not written; at least one
+    output), asynchronous on ``stream`` (a hipStream_t as int, or a torch stream; None / 0 = the default stream) of the
+    current device."""
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, 0)
+    _call("seqik_fit_sensitivity_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
+          _ptr(d_kp_sigma, "kp_sigma", lf + (4,)), float(bound_tol), _ptr(d_sens, "sens", lf + (7, 4, 3)),
+          _ptr(d_std, "std", lf + (7,)), _ptr(d_flags, "flags", lf, dtype="int32"), _stream_ptr(stream))
 
 
 #: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h

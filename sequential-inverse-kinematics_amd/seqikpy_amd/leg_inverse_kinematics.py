@@ -316,9 +316,9 @@ class LegInvKinBase(ABC):
         ``{segment_name: (N, 4, 3, 7)}`` in the order of ``aligned_pos``; ``[t, k, :, d]`` is the derivative of key point
         k + 1 of frame t (forward-kinematics rows 4, 6, 7, 8: coxa, femur and tibia end, claw) with respect to the angle
         of ``DOFS[d]``, length per radian, in the leg's own frame (it does not depend on the origin).  The chain kind
-        follows the class; ``joint_angles`` defaults as in ``run_fk``.  Noise propagation is a numpy step on top: with
-        the pseudo-inverse ``P`` of a frame's stacked ``(12, 7)`` Jacobian, key-point covariance ``C`` gives angle
-        covariance ``P @ C @ P.T``.  ``export_path``: writes ``leg_jacobians.pkl`` there."""
+        follows the class; ``joint_angles`` defaults as in ``run_fk``.  Noise propagation from the key points to the angles of
+        the sequential fit is not the pseudo-inverse of this matrix: see ``LegInvKinSeq.run_angle_sensitivity`` /
+        ``angle_uncertainty``.  ``export_path``: writes ``leg_jacobians.pkl`` there."""
         out, _ = self._jacobian_outputs(joint_angles, True, False)
         if export_path is not None:
             save_file(Path(export_path) / "leg_jacobians.pkl", out)
@@ -514,6 +514,55 @@ class LegInvKinSeq(LegInvKinBase):
         return _lib.make_leg_params(leg_name, kc.bounds_dof, kc.body_size,
                                     self.initial_angles if initial_angles is None else initial_angles)
 
+    # -- angle error bars (include/seqik_sensitivity.h) ---------------------------------------
+    def _sensitivity_outputs(self, joint_angles, key_point_sigma, want_sens, want_flags, bound_tol):
+        """``_lib.fit_sensitivity`` per group of legs with the same frame count -> {segment_name: (leg_name, dict)}."""
+        out = {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
+            n = angles.shape[2]
+            sigma = None
+            if key_point_sigma is not None:
+                sigma = np.empty((1, len(items), n, 4))
+                for li, (_, leg_name, _, _) in enumerate(items):
+                    s = key_point_sigma[leg_name] if isinstance(key_point_sigma, dict) else key_point_sigma
+                    s = np.asarray(s, dtype=np.float64)
+                    if s.shape not in ((), (4,), (n, 4)):
+                        raise ValueError(f"key_point_sigma must be a scalar, (4,) or ({n}, 4), got {s.shape}")
+                    sigma[0, li] = s
+            res = _lib.fit_sensitivity(angles, pose, legs, kp_sigma=sigma, want_sens=want_sens, want_flags=want_flags,
+                                       bound_tol=bound_tol, device=self.device)
+            for li, (segment_name, leg_name, _, _) in enumerate(items):
+                out[segment_name] = (leg_name, {k: v[0, li].copy() for k, v in res.items() if v is not None})
+        return {name: out[name] for name, _, _ in self._leg_segments()}
+
+    def run_angle_sensitivity(self, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                              bound_tol: float = _lib.SENS_BOUND_TOL) -> Dict[str, Dict[str, np.ndarray]]:
+        """How the fitted angles move when the key points they were fitted to move, for every leg, on the GPU
+        (``seqik_fit_sensitivity``): ``{segment_name: dict(sens (N, 7, 4, 3), flags (N,))}`` in the order of
+        ``aligned_pos``.  ``sens[t, d, k, c]`` is the derivative of the angle of ``DOFS[d]`` of frame t with respect to
+        component c of aligned key point k + 1, radians per length -- the response of the four sequential solves with
+        their exact Hessians, 0 for a joint that sits on its limit (within ``bound_tol`` rad) and is pushed against it.
+        ``flags``: ``_lib.fit_sensitivity``.  The key points are the class's own aligned ones (with ``leg_affine``: after
+        the fused alignment; for the RAW key points multiply by the alignment's scale); ``joint_angles`` defaults to the
+        stored angles.  The full covariance of a frame's angles is ``S @ diag(sigma^2) @ S.T`` with ``S = sens[t].reshape(7,
+        12)``."""
+        return {name: res for name, (_, res) in
+                self._sensitivity_outputs(joint_angles, None, True, True, bound_tol).items()}
+
+    def angle_uncertainty(self, key_point_sigma, joint_angles: Optional[Dict[str, np.ndarray]] = None,
+                          bound_tol: float = _lib.SENS_BOUND_TOL) -> Dict[str, np.ndarray]:
+        """The standard deviation that key-point noise gives every fitted angle, on the GPU (``seqik_fit_sensitivity``,
+        ``std``): ``{"Angle_<leg>_<dof>": (N,)}``, radians.  ``key_point_sigma``: the isotropic standard deviation of key
+        points 1..4 (CTr, FTi, TiTa, claw) in the units of the aligned key points -- a scalar, a ``(4,)`` vector, an ``(N,
+        4)`` array (e.g. anipose's ``<kp>_error`` columns), or a ``{leg: one of those}`` dictionary.  A held joint has
+        0; a frame with a non-finite angle, key point or sigma has NaN."""
+        out = {}
+        for _, (leg_name, res) in self._sensitivity_outputs(joint_angles, key_point_sigma, False, False, bound_tol).items():
+            for di, dof in enumerate(DOFS):
+                out[f"Angle_{leg_name}_{dof}"] = res["std"][:, di].copy()
+        return out
+
     def _prior_angles(self, leg_name, n_frames, first_stage):
         """(N, 7) array with the columns of stages < first_stage taken from ``joint_angles_dict``
         (raises KeyError like the reference's chain factory when they are missing)."""
@@ -701,6 +750,15 @@ class LegInvKinGeneric(LegInvKinBase):
         seeds = {leg_name: {f"stage_{k}": np.zeros(STAGE_LINKS[k]) for k in (1, 2, 3)}}
         seeds[leg_name]["stage_4"] = np.asarray(seed9, dtype=np.float64)
         return _lib.make_leg_params(leg_name, kc.bounds_dof, kc.body_size, seeds)
+
+    def run_angle_sensitivity(self, joint_angles=None, bound_tol=None):
+        """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.run_angle_sensitivity``)."""
+        raise ValueError("the generic chain has no angle sensitivity: it fits seven angles to the three coordinates of the "
+                         "claw, so the angles it reports are not a function of the key points (use LegInvKinSeq)")
+
+    def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None):
+        """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.angle_uncertainty``)."""
+        return self.run_angle_sensitivity(joint_angles)
 
     def _store(self, leg_name, angles):
         # key order of the reference: the chain's link order, Base and Claw skipped (:533-539)
