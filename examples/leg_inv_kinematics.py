@@ -34,6 +34,9 @@ def main():
                          "the reference) instead of the default, concurrently solved and verified frame chunks (frame_parallel="
                          "'auto': 10-70x faster for one recording, equal to the serial walk to ~1e-5 rad)")
     ap.add_argument("--export", action="store_true", help="write leg_joint_angles.pkl / forward_kinematics.pkl")
+    ap.add_argument("--refine", action="store_true",
+                    help="afterwards refine the sequential angles against all four key points at once, every frame on its own "
+                         "(LegInvKinSeq.run_refine), and print the fit error before and after")
     args = ap.parse_args()
     if args.path:
         data_path = Path(args.path)
@@ -52,6 +55,16 @@ def main():
                                               frame_parallel=False if args.serial else "auto")
     n = len(next(iter(angles_seq.values())))
     print(f"Sequential IK of {len(fk_seq)} legs x {n} frames took {time.time() - start:.3f} s")
+
+    if args.refine:
+        start = time.time()
+        angles_ref, _ = seq_ik.run_refine(export_path=export)
+        print(f"Whole-leg refinement took {time.time() - start:.3f} s")
+        before, after = seq_ik.fit_error(angles_seq), seq_ik.fit_error(angles_ref)
+        for name in before:
+            info = seq_ik.refine_report[name.split("_")[0]]["info"]
+            print(f"  {name}: rms key-point distance {np.sqrt((before[name] ** 2).mean()):.4f} -> "
+                  f"{np.sqrt((after[name] ** 2).mean()):.4f}, median {int(np.median((info >> 16) & 255))} iterations")
 
     if args.generic:
         start = time.time()

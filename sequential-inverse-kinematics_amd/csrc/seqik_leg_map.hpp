@@ -47,7 +47,7 @@ inline int check_leg_map(const char *who, int64_t n_seq, int32_t n_legs, int64_t
 
 // ---- the launch plan ----
 // One leg-frame per lane, grid-stride.  Three switches per unit select variants for measurements and tests; they are
-// read per call, so that one process can run them all (prefix: SEQIK_FK, SEQIK_FRAMES, SEQIK_JAC, SEQIK_SENS):
+// read per call, so that one process can run them all (prefix: SEQIK_FK, SEQIK_FRAMES, SEQIK_JAC, SEQIK_SENS, SEQIK_REFINE):
 //   <prefix>_STAGED  0 / 1: the per-lane or the LDS-staged kernel (default 1, where the unit allows staging at all)
 //   <prefix>_BLOCK   threads per workgroup: a multiple of 64 from 64 to the unit's maximum, anything else means 256; a
 //                    staged launch takes at most the unit's staged maximum (its LDS per workgroup)

@@ -24,11 +24,11 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip"]
+                 "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip", "seqik_refine.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
-                "seqik_order_stats.hpp", "seqik_sensitivity.hpp"]
+                "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -146,6 +146,11 @@ class SeqikHeadAffine(ctypes.Structure):
                 ("template_base", ctypes.c_double * 3)]
 
 
+class SeqikRefineOptions(ctypes.Structure):
+    """Mirror of ``struct SeqikRefineOptions`` (include/seqik_refine.h)."""
+    _fields_ = [("max_iter", ctypes.c_int32), ("gtol", ctypes.c_double), ("ftol", ctypes.c_double)]
+
+
 def make_head_affine(origin, scale_base, scale_tip, template_base) -> SeqikHeadAffine:
     a = SeqikHeadAffine()
     for i in range(3):
@@ -162,6 +167,7 @@ _int, _i32, _i64, _f64, _size = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ct
 _vp, _vpp, _cp, _i64p = ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)
 _legs, _opt, _lay = ctypes.POINTER(SeqikLegParams), ctypes.POINTER(SeqikOptions), ctypes.POINTER(SeqikLayout)
 _aff, _haff = ctypes.POINTER(SeqikAffine), ctypes.POINTER(SeqikHeadAffine)
+_ropt = ctypes.POINTER(SeqikRefineOptions)
 SIGNATURES = {
     "seqik.h": (
         ("seqik_abi_version", _int),
@@ -260,6 +266,13 @@ SENSITIVITY_SIGNATURES = {
     "seqik_sensitivity.h": (
         ("seqik_fit_sensitivity", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _f64, _dp, _dp, _ip, _i32),
         ("seqik_fit_sensitivity_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _f64, _vp, _vp, _vp, _vp)),
+}
+
+# The same for the whole-leg refinement (include/seqik_refine.h): a sixth table.
+REFINE_SIGNATURES = {
+    "seqik_refine.h": (
+        ("seqik_refine_legs", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _ropt, _dp, _dp, _ip, _i32),
+        ("seqik_refine_legs_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _ropt, _vp, _vp, _vp, _vp)),
 }
 
 
@@ -366,7 +379,7 @@ def load():
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
                            list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values()) +
-                           list(SENSITIVITY_SIGNATURES.values())):
+                           list(SENSITIVITY_SIGNATURES.values()) + list(REFINE_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -644,6 +657,70 @@ def fit_sensitivity_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_kp
     _call("seqik_fit_sensitivity_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
           _ptr(d_kp_sigma, "kp_sigma", lf + (4,)), float(bound_tol), _ptr(d_sens, "sens", lf + (7, 4, 3)),
           _ptr(d_std, "std", lf + (7,)), _ptr(d_flags, "flags", lf, dtype="int32"), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_refine.h (whole-leg refinement of the sequential fit), additive to ABI 7
+REFINE_EXPORTED_SYMBOLS = [sig[0] for sig in REFINE_SIGNATURES["seqik_refine.h"]]
+REFINE_MAX_ITER, REFINE_GTOL, REFINE_FTOL = 200, 1e-10, 1e-14   # SEQIK_REFINE_MAX_ITER / _GTOL / _FTOL
+REFINE_STOP_GRADIENT, REFINE_STOP_DECREASE, REFINE_STOP_DAMPING, REFINE_STOP_MAX_ITER = 0, 1, 2, 4
+REFINE_BAD_INPUT = 1 << 24
+
+
+def refine_stop_reason(info):
+    """Why the lanes of ``refine_legs`` stopped (``REFINE_STOP_*``), from ``info``."""
+    return (np.asarray(info) >> 8) & 7
+
+
+def refine_iterations(info):
+    """The accepted iterations of the lanes of ``refine_legs``, from ``info``."""
+    return (np.asarray(info) >> 16) & 255
+
+
+def _refine_options(max_iter, gtol, ftol):
+    return ctypes.byref(SeqikRefineOptions(int(max_iter), float(gtol), float(ftol)))
+
+
+def refine_legs(angles, pose, legs, kp_weight=None, max_iter=REFINE_MAX_ITER, gtol=REFINE_GTOL, ftol=REFINE_FTOL,
+                want_cost=True, want_info=True, device=None):
+    """``seqik_refine_legs`` on host arrays: angles (S, L, N, 7) of the sequential chain -- normally the sequential fit's
+    -- and the aligned key points (S, L, N, 5, 3) -> dict(angles (S, L, N, 7), cost (S, L, N, 2) or None, info (S, L, N)
+    int32 or None).
+
+    Every leg-frame is refined on its own: from its start, clamped into ``legs[l].bounds``, a bounded Levenberg-Marquardt
+    minimises the weighted squared distance of the chain's four key points from key points 1..4 over all seven angles at
+    once.  ``kp_weight``: a scalar, (4,) or anything that broadcasts to (S, L, N, 4) (None: 1); a key point with weight
+    exactly 0 is not read and may be NaN.  ``cost[..., 0]`` is the weighted sum of squares at the clamped start,
+    ``cost[..., 1]`` at the result (never larger).  ``info``: bits 0..6 DOF held on a limit, ``refine_stop_reason``,
+    ``refine_iterations``, bit 24 (``REFINE_BAD_INPUT``) non-finite input: that leg-frame's angles and costs are NaN.
+    ``max_iter`` (1..255), ``gtol``, ``ftol``: include/seqik_refine.h.  ``device=None``: the current device."""
+    angles, (S, L, N), _, head = _angles_batch(angles, legs, 0)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.shape != (S, L, N, 5, 3):
+        raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    try:
+        weight = _sigma_batch(kp_weight, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_weight must broadcast to {(S, L, N, 4)}, got {np.shape(kp_weight)}") from None
+    out = np.full((S, L, N, 7), np.nan)
+    cost = np.full((S, L, N, 2), np.nan) if want_cost else None
+    info = np.zeros((S, L, N), dtype=np.int32) if want_info else None
+    _call("seqik_refine_legs", head[0], _data(pose), *head[1:], _data(weight), _refine_options(max_iter, gtol, ftol),
+          _data(out), _data(cost), _data(info, _ip), -1 if device is None else int(device))
+    return dict(angles=out, cost=cost, info=info)
+
+
+def refine_legs_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_angles_out, d_kp_weight=0, d_cost=0, d_info=0,
+                       max_iter=REFINE_MAX_ITER, gtol=REFINE_GTOL, ftol=REFINE_FTOL, stream=None):
+    """``seqik_refine_legs_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_refine.h`` (``d_pose`` (S, L, N, 5, 3), ``d_kp_weight`` (S, L, N, 4), ``d_angles_out`` (S, L, N, 7) --
+    it may be ``d_angles`` --, ``d_cost`` (S, L, N, 2) doubles, ``d_info`` (S, L, N) int32; 0 / None: all weights 1, not
+    written), asynchronous on ``stream`` (a hipStream_t as int, or a torch stream; None / 0 = the default stream) of the
+    current device."""
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, 0)
+    _call("seqik_refine_legs_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
+          _ptr(d_kp_weight, "kp_weight", lf + (4,)), _refine_options(max_iter, gtol, ftol),
+          _ptr(d_angles_out, "angles_out", lf + (7,)), _ptr(d_cost, "cost", lf + (2,)),
+          _ptr(d_info, "info", lf, dtype="int32"), _stream_ptr(stream))
 
 
 #: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h

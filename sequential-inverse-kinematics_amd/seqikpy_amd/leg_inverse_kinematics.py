@@ -495,6 +495,8 @@ class LegInvKinSeq(LegInvKinBase):
         self.frame_chunk_stats = {}
         #: per leg, where a chunked run was hard (see ``run_ik_and_fk``); empty after a serial walk
         self.frame_chunk_report = {}
+        #: per leg, ``cost`` (N, 2) and ``info`` (N,) of the last ``run_refine``
+        self.refine_report = {}
 
     def _fk_key_points(self, leg_name, segment_array):
         """Key points in the frame the solver works in: with ``leg_affine`` ``aligned_pos`` holds RAW key points and the
@@ -562,6 +564,62 @@ class LegInvKinSeq(LegInvKinBase):
             for di, dof in enumerate(DOFS):
                 out[f"Angle_{leg_name}_{dof}"] = res["std"][:, di].copy()
         return out
+
+    # -- whole-leg refinement (include/seqik_refine.h) ------------------------------------------
+    def run_refine(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, key_point_weight=None,
+                   export_path: Union[Path, str] = None, **opts
+                   ) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+        """The sequential fit's angles refined against all four key points at once, on the GPU (``seqik_refine_legs``).
+
+        The sequential fit is greedy -- no stage looks back, so the error accumulates towards the claw.  This starts
+        from ``joint_angles`` (default: the stored angles of the last ``run_ik_and_fk``) and, for every frame of every
+        leg, minimises the summed squared distance of the reconstructed CTr, FTi, TiTa and claw from key points 1..4
+        over all seven angles inside the joint limits.  FRAMES ARE REFINED INDEPENDENTLY, each from its own start: no
+        frame is a warm start for the next, so where a leg has two configurations that fit, an angle may move by more
+        than a radian from its start and neighbouring frames may differ by as much.
+
+        ``key_point_weight``: the weight of key points 1..4 -- a scalar, ``(4,)``, ``(N, 4)`` or a ``{leg: one of those}``
+        dictionary (default 1); a key point with weight exactly 0 is not read and may be NaN.  ``opts``: ``max_iter``,
+        ``gtol``, ``ftol`` of ``_lib.refine_legs``.  The key points are the class's own aligned ones (with ``leg_affine``:
+        after the fused alignment).  Returns ``(joint_angles_dict, forward_kinematics_dict)`` shaped as ``run_ik_and_fk``
+        returns them, the forward kinematics computed from the refined angles (``seqik_forward_kinematics``);
+        ``self.joint_angles_dict`` is NOT overwritten.  ``self.refine_report[leg]`` holds ``cost`` ``(N, 2)`` -- the sum
+        of squares at the clamped start and at the result -- and ``info`` ``(N,)`` (``_lib.refine_legs``).
+        ``export_path``: writes ``leg_joint_angles_refined.pkl`` and ``forward_kinematics_refined.pkl`` there."""
+        unknown = set(opts) - {"max_iter", "gtol", "ftol"}
+        if unknown:
+            raise ValueError(f"unknown refinement options: {sorted(unknown)}")
+        angles_out, fk_out, report = {}, {}, {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
+            n = angles.shape[2]
+            weight = None
+            if key_point_weight is not None:
+                weight = np.empty((1, len(items), n, 4))
+                for li, (_, leg_name, _, _) in enumerate(items):
+                    w = key_point_weight[leg_name] if isinstance(key_point_weight, dict) else key_point_weight
+                    w = np.asarray(w, dtype=np.float64)
+                    if w.shape not in ((), (4,), (n, 4)):
+                        raise ValueError(f"key_point_weight must be a scalar, (4,) or ({n}, 4), got {w.shape}")
+                    weight[0, li] = w
+            res = _lib.refine_legs(angles, pose, legs, kp_weight=weight, device=self.device, **opts)
+            fk = _lib.forward_kinematics(res["angles"], legs, kind=self._fk_kind, origin=pose[..., 0, :],
+                                         device=self.device)["fk"]
+            for li, (segment_name, leg_name, _, _) in enumerate(items):
+                for di, dof in enumerate(DOFS):
+                    angles_out[f"Angle_{leg_name}_{dof}"] = res["angles"][0, li, :, di].copy()
+                fk_out[segment_name] = fk[0, li].copy()
+                report[leg_name] = dict(cost=res["cost"][0, li].copy(), info=res["info"][0, li].copy())
+        order = [(name, leg_name) for name, leg_name, _ in self._leg_segments()]
+        angles_out = {f"Angle_{leg_name}_{dof}": angles_out[f"Angle_{leg_name}_{dof}"] for _, leg_name in order
+                      for dof in DOFS}
+        fk_out = {name: fk_out[name] for name, _ in order}
+        self.refine_report = {leg_name: report[leg_name] for _, leg_name in order}
+        if export_path is not None:
+            save_file(Path(export_path) / "leg_joint_angles_refined.pkl", angles_out)
+            save_file(Path(export_path) / "forward_kinematics_refined.pkl", fk_out)
+            self.logger.info("Refined joint angles and forward kinematics are saved at %s", export_path)
+        return angles_out, fk_out
 
     def _prior_angles(self, leg_name, n_frames, first_stage):
         """(N, 7) array with the columns of stages < first_stage taken from ``joint_angles_dict``
@@ -759,6 +817,11 @@ class LegInvKinGeneric(LegInvKinBase):
     def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None):
         """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.angle_uncertainty``)."""
         return self.run_angle_sensitivity(joint_angles)
+
+    def run_refine(self, joint_angles=None, key_point_weight=None, export_path=None, **opts):
+        """Not built for the generic chain: raises ``NotImplementedError`` (see ``LegInvKinSeq.run_refine``)."""
+        raise NotImplementedError("the whole-leg refinement is built for the sequential chain only: the generic chain "
+                                  "already fits all seven angles at once, to the claw alone (use LegInvKinSeq)")
 
     def _store(self, leg_name, angles):
         # key order of the reference: the chain's link order, Base and Claw skipped (:533-539)
