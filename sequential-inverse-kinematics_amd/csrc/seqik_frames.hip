@@ -20,7 +20,6 @@ struct FramesArgs {
 };
 
 using seqik::kFramesQuad;                          // 27 doubles: the quarter of a record one lane of the staged path holds
-using seqik::kSubTile;                             // 16 leg-frames per pass of the staged path
 constexpr int kFramesWaveLds = 64 * kFramesQuad;   // doubles of LDS per wavefront (STAGED): 16 records = 13.5 KiB
 
 // One leg-frame per lane, grid-stride over the flat index (64-bit throughout).  Per leg-frame 56 B of angles (+ 24 B of
@@ -45,20 +44,15 @@ __global__ void __launch_bounds__(256) seqik_frames_kernel(FramesArgs a)
         const int64_t i = t0 + threadIdx.x;
         const int64_t w0 = t0 + wave * 64;  // first leg-frame of this wavefront
         if (STAGED && w0 + 64 <= n) {
-            double *st = s_frames + wave * kFramesWaveLds;
-#pragma unroll 1
-            for (int p = 0; p < 64 / kSubTile; ++p) {
-                const int64_t r0 = w0 + p * kSubTile, rec = r0 + (lane >> 2);  // rec < w0 + 64 <= n
-                const int leg = a.ix.leg_of(rec);
-                seqik::FramesQuadSink sink;
-                sink.q = lane & 3;
-                seqik::link_frames_walk<KIND>(a.ix.legs[leg], a.angles + rec * 7, a.origin ? a.origin + rec * 3 : nullptr,
-                                              sink);
-                seqik::store_quad_pass<kFramesQuad>(st, lane, sink.buf, a.frames + r0 * kFramesRow);
-            }
+            seqik::staged_quad_passes<kFramesQuad>(
+                s_frames + wave * kFramesWaveLds, lane, w0, a.frames, [&](int64_t rec, seqik::QuadSink<kFramesQuad> &sink) {
+                    const int leg = a.ix.leg_of(rec);
+                    seqik::link_frames_walk<KIND>(a.ix.legs[leg], a.angles + rec * 7,
+                                                  a.origin ? a.origin + rec * 3 : nullptr, sink);
+                });
         } else if (i < n) {
             const int leg = a.ix.leg_of(i);
-            seqik::GlobalSink sink{a.frames + i * kFramesRow};
+            seqik::ArraySink sink{a.frames + i * kFramesRow};
             seqik::link_frames_walk<KIND>(a.ix.legs[leg], a.angles + i * 7, a.origin ? a.origin + i * 3 : nullptr, sink);
         }
     }

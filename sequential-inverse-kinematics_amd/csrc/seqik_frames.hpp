@@ -17,7 +17,7 @@
 // blocks do not depend on the origin.  An axis rotation appended on the right changes two columns of the block only,
 // which is how frame_mul_link computes it.
 #pragma once
-#include "seqik_fk.hpp"
+#include "seqik_leg_chain.hpp"
 
 namespace seqik {
 
@@ -105,32 +105,15 @@ SEQIK_HD void link_frames_walk(const FkLeg &fl, const double *ang, const double 
     frames_emit<8>(sink, b, col, finite);
 }
 
-struct FramesArraySink {
-    double *out;
-    template <int IDX> SEQIK_HD void put(double v) { out[IDX] = v; }
-};
-
-// Keeps quarter `q` of the record, doubles [27 q, 27 q + 27): the sink of the kernel's staged path, where four lanes share a
-// record (seqik_frames.hip).  IDX is a constant at every call, so which quarter a value belongs to and where it goes
-// inside it are known at compile time: one select per value, no indexing.
-constexpr int kFramesQuad = kFramesRow / 4;
-struct FramesQuadSink {
-    int q;
-    double buf[kFramesQuad];
-    template <int IDX> SEQIK_HD void put(double v)
-    {
-        constexpr int Q = IDX / kFramesQuad, J = IDX % kFramesQuad;
-        if constexpr (Q == 0) buf[J] = v;  // the first value offered for slot J; a later quarter's replaces it
-        else buf[J] = (q == Q) ? v : buf[J];
-    }
-};
+constexpr int kFramesQuad = kFramesRow / 4;  // 27 doubles: the quarter of a record one lane of the staged path holds
+using FramesQuadSink = QuadSink<kFramesQuad>;  // the unit's own name of it: host harnesses written against it still build
 
 // One leg-frame.  ang [7] in DOFS order, origin [3] (nullable: leg-local positions), out [9][3][4].
 // An angle outside the domain (non-finite, or |x| > SEQIK_ANGLE_MAX) makes all 108 values NaN.
 template <int KIND>
 SEQIK_HD void link_frames_leg_frame(const FkLeg &fl, const double *ang, const double *origin, double *out)
 {
-    FramesArraySink sink{out};
+    ArraySink sink{out};
     link_frames_walk<KIND>(fl, ang, origin, sink);
 }
 

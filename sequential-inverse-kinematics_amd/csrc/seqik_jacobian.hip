@@ -25,8 +25,7 @@ struct JacArgs {
     seqik::LegFrameIndex ix;
 };
 
-using seqik::GlobalSink;
-using seqik::kSubTile;                        // 16 leg-frames per pass of the staged path
+using seqik::ArraySink;
 constexpr int kJacWaveLds = 64 * kJacQuad;    // doubles of LDS per wavefront (STAGED): 16 records = 10 752 B
 
 // One leg-frame per lane, grid-stride over the flat index (64-bit throughout).  Per leg-frame 56 B of angles (+ 56 B of
@@ -52,24 +51,19 @@ __global__ void __launch_bounds__(256) seqik_jacobian_kernel(JacArgs a)
         if (JAC && STAGED && w0 + 64 <= n) {
             if constexpr (RED) {  // i < w0 + 64 <= n
                 const int leg = a.ix.leg_of(i);
-                seqik::JacBothSink<KIND, false, true, GlobalSink> sink;
+                seqik::JacBothSink<KIND, false, true, ArraySink> sink;
                 sink.red.begin(a.vel ? a.qdot + i * 7 : nullptr);
                 const bool finite = seqik::leg_jacobian_walk<KIND>(a.ix.legs[leg], a.angles + i * 7, sink);
                 sink.red.finish(finite, a.sigma ? a.sigma + i * kJacSigma : nullptr, a.vel ? a.vel + i * kJacVel : nullptr);
             }
-            double *st = s_jac + wave * kJacWaveLds;
-#pragma unroll 1
-            for (int p = 0; p < 64 / kSubTile; ++p) {
-                const int64_t r0 = w0 + p * kSubTile, rec = r0 + (lane >> 2);  // rec < w0 + 64 <= n
-                const int leg = a.ix.leg_of(rec);
-                seqik::JacQuadSink sink;
-                sink.q = lane & 3;
-                seqik::leg_jacobian_walk<KIND>(a.ix.legs[leg], a.angles + rec * 7, sink);
-                seqik::store_quad_pass<kJacQuad>(st, lane, sink.buf, a.jac + r0 * kJacRow);  // 16 records = 21 rows
-            }
+            seqik::staged_quad_passes<kJacQuad>(  // a pass: 16 records = 21 rows
+                s_jac + wave * kJacWaveLds, lane, w0, a.jac, [&](int64_t rec, seqik::QuadSink<kJacQuad> &sink) {
+                    const int leg = a.ix.leg_of(rec);
+                    seqik::leg_jacobian_walk<KIND>(a.ix.legs[leg], a.angles + rec * 7, sink);
+                });
         } else if (i < n) {
             const int leg = a.ix.leg_of(i);
-            seqik::JacBothSink<KIND, JAC, RED, GlobalSink> sink;
+            seqik::JacBothSink<KIND, JAC, RED, ArraySink> sink;
             sink.rec.out = JAC ? a.jac + i * kJacRow : nullptr;
             sink.red.begin(RED && a.vel ? a.qdot + i * 7 : nullptr);
             const bool finite = seqik::leg_jacobian_walk<KIND>(a.ix.legs[leg], a.angles + i * 7, sink);

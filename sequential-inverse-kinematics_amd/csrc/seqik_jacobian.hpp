@@ -31,7 +31,7 @@
 #pragma once
 #include <utility>
 
-#include "seqik_fk.hpp"
+#include "seqik_leg_chain.hpp"
 
 namespace seqik {
 
@@ -43,36 +43,6 @@ constexpr int kJacobiSweeps = 6;
 // nonzero pattern: bit d of [kind][k - 1] is set where (key point k, DOF d) is not a structural zero
 constexpr int kJacNonzero[2][4] = {{0x03, 0x0F, 0x3F, 0x7F}, {0x07, 0x0F, 0x3F, 0x7F}};
 constexpr bool jac_nonzero(int kind, int k0, int d) { return (kJacNonzero[kind][k0] >> d) & 1; }
-
-// What the walk keeps of the chain: the world axis of every DOF and the four key points.
-struct JacChain {
-    double ax[7][3];  // by DOF
-    double p[4][3];   // key points 1..4
-};
-
-template <int AXIS>
-SEQIK_HD void jac_axis(double *ax, const Frame &f)
-{
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ax[i] = f.r[3 * i + AXIS];
-}
-
-// Entry (key point K0 + 1, component C, DOF D) of a leg-frame's Jacobian; only called where it is not a structural zero.
-template <int K0, int C, int D>
-SEQIK_HD double jac_entry(const JacChain &ch)
-{
-    constexpr int C1 = (C + 1) % 3, C2 = (C + 2) % 3;
-    constexpr int O = D <= SEQIK_DOF_THC_ROLL ? -1 : D <= SEQIK_DOF_CTR_ROLL ? 0 : D == SEQIK_DOF_FTI_PITCH ? 1 : 2;
-    double d1, d2;
-    if constexpr (O < 0) {
-        d1 = ch.p[K0][C1];
-        d2 = ch.p[K0][C2];
-    } else {
-        d1 = ch.p[K0][C1] - ch.p[O][C1];
-        d2 = ch.p[K0][C2] - ch.p[O][C2];
-    }
-    return ch.ax[D][C1] * d2 - ch.ax[D][C2] * d1;
-}
 
 template <int KIND, int IDX, class Sink>
 SEQIK_HD void jac_emit_one(Sink &sink, const JacChain &ch, bool finite)
@@ -150,24 +120,9 @@ SEQIK_HD bool leg_jacobian_walk(const FkLeg &fl, const double *ang, Sink &sink)
     return finite;
 }
 
-struct JacArraySink {
-    double *out;
-    template <int IDX> SEQIK_HD void put(double v) { out[IDX] = v; }
-};
-
-// Keeps quarter `q` of the record, doubles [21 q, 21 q + 21): the sink of the kernel's staged path, where four lanes share
-// a record (FramesQuadSink's scheme: one compile-time select per value, no indexing).
-constexpr int kJacQuad = kJacRow / 4;
-struct JacQuadSink {
-    int q;
-    double buf[kJacQuad];
-    template <int IDX> SEQIK_HD void put(double v)
-    {
-        constexpr int Q = IDX / kJacQuad, J = IDX % kJacQuad;
-        if constexpr (Q == 0) buf[J] = v;
-        else buf[J] = (q == Q) ? v : buf[J];
-    }
-};
+constexpr int kJacQuad = kJacRow / 4;  // 21 doubles: the quarter of a record one lane of the staged path holds
+using JacArraySink = ArraySink;  // the unit's own names of the sinks: host harnesses written against them still build
+using JacQuadSink = QuadSink<kJacQuad>;
 
 SEQIK_HD double jac_dot7(const double *a, const double *b)
 {
@@ -293,7 +248,7 @@ SEQIK_HD void leg_jacobian_leg_frame(const FkLeg &fl, const double *ang, const d
                                      double *vel)
 {
     double scratch[kJacRow];
-    JacBothSink<KIND, true, true, JacArraySink> sink;
+    JacBothSink<KIND, true, true, ArraySink> sink;
     sink.rec.out = jac ? jac : scratch;
     sink.red.begin(qdot);
     const bool finite = leg_jacobian_walk<KIND>(fl, ang, sink);

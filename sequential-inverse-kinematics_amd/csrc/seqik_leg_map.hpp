@@ -1,15 +1,16 @@
 // seqik_leg_map.hpp -- what the units that map joint angles (S, L, N, 7) to one record per leg-frame share: forward
-// kinematics (seqik_fk.hip), link frames (seqik_frames.hip) and leg Jacobians (seqik_jacobian.hip).  The tail of their
-// kernel arguments, the argument checks they have in common, the launch plan with its environment switches, and the
-// pieces of the staged store path that frames and Jacobians have word for word.  The kernels, their staging schemes and
-// their own pointer rules stay in the units.
+// kinematics (seqik_fk.hip), link frames (seqik_frames.hip), leg Jacobians (seqik_jacobian.hip), fit sensitivity
+// (seqik_sensitivity.hip) and refinement (seqik_refine.hip).  The tail of their kernel arguments, the argument checks they
+// have in common, the launch plan with its environment switches, and the quarter-record staged store path of frames,
+// Jacobians and sensitivity.  The kernels' outer loops, their reductions and their own pointer rules stay in the units;
+// the device rules they share are in seqik_leg_chain.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "seqik_fk.hpp"
+#include "seqik_leg_chain.hpp"
 #include "seqik_runtime.hpp"
 
 namespace seqik {
@@ -91,14 +92,8 @@ int launch_leg_map(void (*kernel)(Args), const LegMapPlan &p, const Args &a, voi
     return launched();
 }
 
-// ---- the staged store path of the units whose record is too large to hold whole in LDS (frames, Jacobians) ----
+// ---- the staged store path of frames, Jacobians and sensitivity (the per-lane path stores through ArraySink) ----
 constexpr int kSubTile = 16;  // leg-frames per pass: four lanes share a record, each keeps a quarter of it
-
-// Straight to global memory, value by value (per-lane path).
-struct GlobalSink {
-    double *out;
-    template <int IDX> __device__ __forceinline__ void put(double v) { out[IDX] = v; }
-};
 
 // One pass: every lane writes its quarter (QUAD doubles) to the wavefront's LDS at lane * QUAD (<= 63 * QUAD + QUAD - 1,
 // inside the 64 * QUAD doubles at `st`), then the wavefront stores the kSubTile records at `global_row0` as QUAD fully
@@ -112,6 +107,21 @@ __device__ __forceinline__ void store_quad_pass(double *st, int lane, const doub
 #pragma unroll
     for (int k = 0; k < QUAD; ++k) __builtin_nontemporal_store(st[k * 64 + lane], global_row0 + k * 64 + lane);
     wave_lds_fence();  // the next pass's LDS writes stay behind these reads
+}
+
+// The 64 records (4 * QUAD doubles each, at `out`) of a whole wavefront from leg-frame w0 (w0 + 64 <= n_total), in four
+// passes of kSubTile through `st` (64 * QUAD doubles of LDS): `rule(rec, sink)` hands record rec to the lane's QuadSink.
+template <int QUAD, class Rule>
+__device__ __forceinline__ void staged_quad_passes(double *st, int lane, int64_t w0, double *out, Rule rule)
+{
+#pragma unroll 1
+    for (int p = 0; p < 64 / kSubTile; ++p) {
+        const int64_t r0 = w0 + p * kSubTile, rec = r0 + (lane >> 2);  // rec < w0 + 64
+        QuadSink<QUAD> sink;
+        sink.q = lane & 3;
+        rule(rec, sink);
+        store_quad_pass<QUAD>(st, lane, sink.buf, out + r0 * (4 * QUAD));
+    }
 }
 
 }  // namespace seqik

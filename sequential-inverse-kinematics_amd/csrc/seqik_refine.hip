@@ -21,7 +21,7 @@ struct RefineArgs {
     int32_t *info;            // nullable, [n_total]
     seqik::RefineOptions opt;
     seqik::LegFrameIndex ix;
-    seqik::SensBounds bounds[seqik::kFkMaxLegs];  // entries past n_legs repeat leg 0
+    seqik::LegBoundsTable bounds;
 };
 
 // One leg-frame per lane, grid-stride over the flat index (64-bit throughout), FP64.  Per leg-frame 56 + 120 (+ 32) B in
@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) seqik_refine_kernel(RefineArgs a)
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = a.ix.n_total;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int leg = a.ix.leg_of(i);
-        seqik::refine_leg_frame(a.ix.legs[leg], a.bounds[leg], a.angles + i * 7, a.pose + i * 15,
+        seqik::refine_leg_frame(a.ix.legs[leg], a.bounds.b[leg], a.angles + i * 7, a.pose + i * 15,
                                 a.kp_weight ? a.kp_weight + i * 4 : nullptr, a.opt, a.angles_out + i * 7,
                                 a.cost ? a.cost + i * seqik::kRefineCost : nullptr, a.info ? a.info + i : nullptr);
     }
@@ -82,7 +82,7 @@ int seqik_refine_legs_device(const double *d_angles, const double *d_pose, int64
     a.angles = d_angles; a.pose = d_pose; a.kp_weight = d_kp_weight;
     a.angles_out = d_angles_out; a.cost = d_cost; a.info = d_info;
     a.ix.fill(n, n_legs, n_frames, legs);
-    for (int l = 0; l < seqik::kFkMaxLegs; ++l) seqik::make_sens_bounds(legs[l < n_legs ? l : 0], a.bounds[l]);
+    a.bounds.fill(n_legs, legs);
     const seqik::LegMapPlan p = seqik::plan_leg_map("SEQIK_REFINE", n, false, 256, 256, 0);
     return seqik::launch_leg_map(seqik_refine_kernel, p, a, hip_stream);
 }

@@ -6,11 +6,11 @@
 // arithmetic so that the rule run on the host and the kernel agree bit for bit (-ffp-contract=off, correctly rounded
 // sqrt and /):
 //
-//   chain     sens_chain_walk of seqik_sensitivity.hpp (the walk of the Jacobian unit): world axes a_j, key points f_k.
+//   chain     seq_chain_walk of seqik_leg_chain.hpp: world axes a_j, key points f_k.
 //   residual  r[k][c] = w_k * (f_k[c] - t_k[c]);  c = ((r_1 . r_1 + r_2 . r_2) + r_3 . r_3) + r_4 . r_4, every dot product
 //             (x0 y0 + x1 y1) + x2 y2.  A key point with w_k == 0 is not read: t_k = 0, r_k = 0.
 //   J, A, g   key point by key point, and within a key point column by column: the column of DOF j for key point k is
-//             w_k * (a_j x (f_k - o_j)) (sens_column; only where it is not a structural zero, j < 2 k, stage 4: j < 7).
+//             w_k * (a_j x (f_k - o_j)) (jac_column; only where it is not a structural zero, j < 2 k, stage 4: j < 7).
 //             It adds J_j . r_k to g_j and J_i . J_j to A_ji for the columns i <= j of the same key point, which are
 //             the only ones held: 21 entries of J at most, never the 84.  Sums run over k ascending.
 //   held      DOF j is held when (q_j <= lb_j and g_j > 0) or (q_j >= ub_j and g_j < 0).
@@ -40,7 +40,7 @@
 #include <stdint.h>
 #include <utility>
 
-#include "seqik_sensitivity.hpp"
+#include "seqik_leg_chain.hpp"
 
 namespace seqik {
 
@@ -65,7 +65,7 @@ SEQIK_HD double refine_residual(const JacChain &ch, const double (&t)[4][3], con
     for (int k = 0; k < 4; ++k) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) r[k][i] = w[k] * (ch.p[k][i] - t[k][i]);
-        const double s = sens_dot(r[k], r[k]);
+        const double s = chain_dot(r[k], r[k]);
         c = k == 0 ? s : c + s;
     }
     return c;
@@ -77,14 +77,14 @@ SEQIK_HD void refine_column(const JacChain &ch, double w, const double *rk, doub
 {
     constexpr bool FIRST = K0 == D / 2;  // the first key point DOF D moves
     double col[3];
-    sens_column<K0, D>(col, ch);
+    jac_column<K0, D>(col, ch);
 #pragma unroll
     for (int c = 0; c < 3; ++c) Jk[D][c] = w * col[c];
-    const double gd = sens_dot(Jk[D], rk);
+    const double gd = chain_dot(Jk[D], rk);
     g[D] = FIRST ? gd : g[D] + gd;
 #pragma unroll
     for (int i = 0; i <= D; ++i) {
-        const double a = sens_dot(Jk[i], Jk[D]);
+        const double a = chain_dot(Jk[i], Jk[D]);
         A[D][i] = FIRST ? a : A[D][i] + a;
     }
 }
@@ -156,7 +156,7 @@ SEQIK_HD bool refine_solve(const double (&A)[7][7], const double *g, int held, d
 
 // One leg-frame.  ang [7], pose [5][3], kp_weight [4] nullable; ang_out [7] (may be ang), cost [2] nullable, info [1]
 // nullable.
-SEQIK_HD void refine_leg_frame(const FkLeg &fl, const SensBounds &sb, const double *ang, const double *pose,
+SEQIK_HD void refine_leg_frame(const FkLeg &fl, const LegBounds &sb, const double *ang, const double *pose,
                                const double *kp_weight, const RefineOptions &opt, double *ang_out, double *cost,
                                int32_t *info)
 {
@@ -203,7 +203,7 @@ SEQIK_HD void refine_leg_frame(const FkLeg &fl, const SensBounds &sb, const doub
     for (int d = 0; d < 7; ++d) q[d] = refine_clamp(q[d], sb.lb[d], sb.ub[d]);
     JacChain ch;
     double r[4][3];
-    sens_chain_walk(fl, q, ch);
+    seq_chain_walk(fl, q, ch);
     double c = refine_residual(ch, t, w, r);
     const double c0 = c;
     const double len = ((fl.nseg[0] + fl.nseg[1]) + fl.nseg[2]) + fl.nseg[3];  // minus the leg length; only its square is used
@@ -249,7 +249,7 @@ SEQIK_HD void refine_leg_frame(const FkLeg &fl, const SensBounds &sb, const doub
             if (usable) {
                 JacChain cn;
                 double rn[4][3];
-                sens_chain_walk(fl, qn, cn);
+                seq_chain_walk(fl, qn, cn);
                 const double c_new = refine_residual(cn, t, w, rn);
                 if (c_new < c) {
                     accepted = true;

@@ -24,18 +24,16 @@ struct SensArgs {
     int32_t *flags;          // nullable, [n_total]
     double tol;
     seqik::LegFrameIndex ix;
-    seqik::SensBounds bounds[seqik::kFkMaxLegs];  // entries past n_legs repeat leg 0
+    seqik::LegBoundsTable bounds;
 };
 
-using seqik::GlobalSink;
-using seqik::kSubTile;                        // 16 leg-frames per pass of the staged path
 constexpr int kSensWaveLds = 64 * kSensQuad;  // doubles of LDS per wavefront (STAGED): 16 records = 10 752 B
 
 // The rule of leg-frame i into `res`.
 __device__ __forceinline__ void sens_of(const SensArgs &a, int64_t i, seqik::SensResult &res)
 {
     const int leg = a.ix.leg_of(i);
-    seqik::sens_leg_frame_rule(a.ix.legs[leg], a.bounds[leg], a.angles + i * 7, a.pose + i * 15,
+    seqik::sens_leg_frame_rule(a.ix.legs[leg], a.bounds.b[leg], a.angles + i * 7, a.pose + i * 15,
                                a.std_out ? a.kp_sigma + i * 4 : nullptr, a.tol, res);
 }
 
@@ -71,22 +69,17 @@ __global__ void __launch_bounds__(256) seqik_sensitivity_kernel(SensArgs a)
                 sens_of(a, i, res);
                 sens_reduce(a, i, res);
             }
-            double *st = s_sens + wave * kSensWaveLds;
-#pragma unroll 1
-            for (int p = 0; p < 64 / kSubTile; ++p) {
-                const int64_t r0 = w0 + p * kSubTile, rec = r0 + (lane >> 2);  // rec < w0 + 64 <= n
-                seqik::SensResult res;
-                sens_of(a, rec, res);
-                seqik::JacQuadSink sink;
-                sink.q = lane & 3;
-                seqik::sens_emit(sink, res);
-                seqik::store_quad_pass<kSensQuad>(st, lane, sink.buf, a.sens + r0 * kSensRow);  // 16 records = 21 rows
-            }
+            seqik::staged_quad_passes<kSensQuad>(  // a pass: 16 records = 21 rows
+                s_sens + wave * kSensWaveLds, lane, w0, a.sens, [&](int64_t rec, seqik::QuadSink<kSensQuad> &sink) {
+                    seqik::SensResult res;
+                    sens_of(a, rec, res);
+                    seqik::sens_emit(sink, res);
+                });
         } else if (i < n) {
             seqik::SensResult res;
             sens_of(a, i, res);
             if constexpr (SENS) {
-                GlobalSink sink{a.sens + i * kSensRow};
+                seqik::ArraySink sink{a.sens + i * kSensRow};
                 seqik::sens_emit(sink, res);
             }
             if constexpr (RED) sens_reduce(a, i, res);
@@ -136,7 +129,7 @@ int seqik_fit_sensitivity_device(const double *d_angles, const double *d_pose, i
     a.angles = d_angles; a.pose = d_pose; a.kp_sigma = d_kp_sigma; a.sens = d_sens; a.std_out = d_std; a.flags = d_flags;
     a.tol = bound_tol;
     a.ix.fill(n, n_legs, n_frames, legs);
-    for (int l = 0; l < seqik::kFkMaxLegs; ++l) seqik::make_sens_bounds(legs[l < n_legs ? l : 0], a.bounds[l]);
+    a.bounds.fill(n_legs, legs);
     // Staged only when a record is requested (staging concerns the record).
     const bool sens = d_sens != nullptr, red = d_std || d_flags;
     const seqik::LegMapPlan p = seqik::plan_leg_map("SEQIK_SENS", n, sens, 256, 256, kSensWaveLds);

@@ -7,7 +7,7 @@
 // free); differentiating that condition gives
 //     S_F = G_FF^-1 ( J_F^T [on key point s]  -  G_FE S_E ),
 //     G_ab = J_a . J_b + r . (a_i x (a_j x (f_s - o_j))),   i = min(a, b), j = max(a, b)
-// with J_a = a_a x (f_s - o_a) the Jacobian column of seqik_jacobian.hpp (a_a the world axis of DOF a, o_a its origin).
+// with J_a = a_a x (f_s - o_a) the Jacobian column of seqik_leg_chain.hpp (a_a the world axis of DOF a, o_a its origin).
 // G is the exact Hessian of the stage's cost: 3 equations fit 2 unknowns, the residual does not vanish, and the second
 // term -- the exact second derivative of a revolute chain -- is not small next to the first.
 //
@@ -24,7 +24,7 @@
 //
 // S[7][4][3] = d angle / d (aligned key point k, component c); block lower triangular: the row of a stage-s DOF holds +0.0
 // for the key points after s, stored and never computed (sens_nonzero).  Every dot product is (x0 y0 + x1 y1) + x2 y2,
-// every cross product that of seqik_jacobian.hpp, G_FE S_E is summed over E ascending and only where S_E is not a
+// every cross product that of seqik_leg_chain.hpp, G_FE S_E is summed over E ascending and only where S_E is not a
 // structural zero.  std_j = sqrt(sum_k sigma_k^2 ((S_jk0^2 + S_jk1^2) + S_jk2^2)), k ascending up to the DOF's stage.
 //
 // Domain: an angle outside the domain of seqik_fk.hpp, a non-finite key-point coordinate or -- when std is asked for -- a
@@ -40,96 +40,19 @@ namespace seqik {
 
 constexpr int kSensRow = 84;  // doubles of sensitivity per leg-frame: 7 DOFs x 4 key points x 3 components
 constexpr int kSensStd = 7;   // doubles of standard deviation per leg-frame
-constexpr int kSensQuad = kSensRow / 4;
-static_assert(kSensQuad == kJacQuad, "the staged path reuses JacQuadSink");
+constexpr int kSensQuad = kSensRow / 4;  // 21 doubles: the quarter of a record one lane of the staged path holds
 constexpr int32_t SENS_FLAG_NOT_PD0 = 1 << 8;      // << (stage - 1)
 constexpr int32_t SENS_FLAG_BAD_INPUT = 1 << 16;
 
-// What the rule reads of a leg besides the segment lengths: the limits of the seven DOFs.
-struct SensBounds {
-    double lb[7], ub[7];
-};
-
-inline void make_sens_bounds(const SeqikLegParams &lp, SensBounds &sb)
-{
-    for (int d = 0; d < 7; ++d) {
-        sb.lb[d] = lp.bounds[d][0];
-        sb.ub[d] = lp.bounds[d][1];
-    }
-}
-
 constexpr int sens_stage_of(int dof) { return dof / 2 + 1; }                        // 1..4
 constexpr bool sens_nonzero(int dof, int k0) { return k0 < sens_stage_of(dof); }    // k0 = key point - 1
-
-SEQIK_HD void sens_cross(double *out, const double *a, const double *d)
-{
-    out[0] = a[1] * d[2] - a[2] * d[1];
-    out[1] = a[2] * d[0] - a[0] * d[2];
-    out[2] = a[0] * d[1] - a[1] * d[0];
-}
-
-SEQIK_HD double sens_dot(const double *x, const double *y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-// The chain walk of leg_jacobian_walk for the sequential chain, without its 84 entries: the world axis of every DOF and
-// the four key points, leg-local, with the same frame_mul_link calls in the same order (restated here, so that the
-// Jacobian kernels' code stays what it was).
-SEQIK_HD void sens_chain_walk(const FkLeg &fl, const double *x, JacChain &ch)
-{
-    double sn, cs;
-    Frame a, b;
-    frame_identity(a);
-    sincos_cw(x[SEQIK_DOF_THC_YAW], sn, cs);
-    frame_mul_link<AXIS_X>(b, a, sn, cs, 0.0);
-    jac_axis<AXIS_X>(ch.ax[SEQIK_DOF_THC_YAW], b);
-    sincos_cw(x[SEQIK_DOF_THC_PITCH], sn, cs);
-    frame_mul_link<AXIS_Y>(a, b, sn, cs, 0.0);
-    jac_axis<AXIS_Y>(ch.ax[SEQIK_DOF_THC_PITCH], a);
-    sincos_cw(x[SEQIK_DOF_THC_ROLL], sn, cs);
-    frame_mul_link<AXIS_Z>(b, a, sn, cs, 0.0);
-    jac_axis<AXIS_Z>(ch.ax[SEQIK_DOF_THC_ROLL], b);
-    sincos_cw(x[SEQIK_DOF_CTR_PITCH], sn, cs);
-    frame_mul_link<AXIS_Y>(a, b, sn, cs, fl.nseg[0]);
-    jac_axis<AXIS_Y>(ch.ax[SEQIK_DOF_CTR_PITCH], a);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ch.p[0][k] = a.t[k];  // coxa end; CTr_roll (translation 0) sits in it too
-    sincos_cw(x[SEQIK_DOF_CTR_ROLL], sn, cs);
-    frame_mul_link<AXIS_Z>(b, a, sn, cs, 0.0);
-    jac_axis<AXIS_Z>(ch.ax[SEQIK_DOF_CTR_ROLL], b);
-    sincos_cw(x[SEQIK_DOF_FTI_PITCH], sn, cs);
-    frame_mul_link<AXIS_Y>(a, b, sn, cs, fl.nseg[1]);
-    jac_axis<AXIS_Y>(ch.ax[SEQIK_DOF_FTI_PITCH], a);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ch.p[1][k] = a.t[k];  // femur end
-    sincos_cw(x[SEQIK_DOF_TITA_PITCH], sn, cs);
-    frame_mul_link<AXIS_Y>(b, a, sn, cs, fl.nseg[2]);
-    jac_axis<AXIS_Y>(ch.ax[SEQIK_DOF_TITA_PITCH], b);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        ch.p[2][k] = b.t[k];                                // tibia end
-        ch.p[3][k] = b.r[3 * k + 2] * fl.nseg[3] + b.t[k];  // claw (it does not rotate)
-    }
-}
-
-// J_d = a_d x (f - o_d) for key point K0 + 1; the origin of a DOF as in jac_entry.
-template <int K0, int D>
-SEQIK_HD void sens_column(double *J, const JacChain &ch)
-{
-    constexpr int O = D <= SEQIK_DOF_THC_ROLL ? -1 : D <= SEQIK_DOF_CTR_ROLL ? 0 : D == SEQIK_DOF_FTI_PITCH ? 1 : 2;
-    double lev[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if constexpr (O < 0) lev[c] = ch.p[K0][c];
-        else lev[c] = ch.p[K0][c] - ch.p[O][c];
-    }
-    sens_cross(J, ch.ax[D], lev);
-}
 
 // G_ab of the stage whose residual is r, a <= b: J_a . J_b + r . (a_a x J_b)
 SEQIK_HD double sens_hessian(const double *Ja, const double *Jb, const double *axis_a, const double *r)
 {
     double h[3];
-    sens_cross(h, axis_a, Jb);
-    return sens_dot(Ja, Jb) + sens_dot(r, h);
+    chain_cross(h, axis_a, Jb);
+    return chain_dot(Ja, Jb) + chain_dot(r, h);
 }
 
 SEQIK_HD bool sens_held(double q, double lb, double ub, double g, double tol)
@@ -140,7 +63,7 @@ SEQIK_HD bool sens_held(double q, double lb, double ub, double g, double tol)
 // Stage ST = 1..4: fills the rows of its own DOFs in S (key points 1..ST) from the rows of the earlier stages -> the
 // stage's flag bits.
 template <int ST>
-SEQIK_HD int32_t sens_stage(const JacChain &ch, const SensBounds &sb, const double *q, const double *pose, double tol,
+SEQIK_HD int32_t sens_stage(const JacChain &ch, const LegBounds &sb, const double *q, const double *pose, double tol,
                             double (&S)[7][4][3])
 {
     constexpr int K0 = ST - 1, A = 2 * K0, B = A + 1, NE = A;
@@ -150,18 +73,18 @@ SEQIK_HD int32_t sens_stage(const JacChain &ch, const SensBounds &sb, const doub
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = ch.p[K0][c] - (pose[3 * ST + c] - pose[c]);
     double Ja[3], Jb[3] = {0.0, 0.0, 0.0};
-    sens_column<K0, A>(Ja, ch);
-    if constexpr (TWO) sens_column<K0, B>(Jb, ch);
+    jac_column<K0, A>(Ja, ch);
+    if constexpr (TWO) jac_column<K0, B>(Jb, ch);
     // G_ae, G_be for the earlier DOFs e (the larger index is the own DOF's)
     double Gae[NE > 0 ? NE : 1], Gbe[NE > 0 ? NE : 1];
     if constexpr (NE > 0) {
         double Je[NE][3];
-        if constexpr (NE > 0) sens_column<K0, 0>(Je[0], ch);
-        if constexpr (NE > 1) sens_column<K0, 1>(Je[1], ch);
-        if constexpr (NE > 2) sens_column<K0, 2>(Je[2], ch);
-        if constexpr (NE > 3) sens_column<K0, 3>(Je[3], ch);
-        if constexpr (NE > 4) sens_column<K0, 4>(Je[4], ch);
-        if constexpr (NE > 5) sens_column<K0, 5>(Je[5], ch);
+        if constexpr (NE > 0) jac_column<K0, 0>(Je[0], ch);
+        if constexpr (NE > 1) jac_column<K0, 1>(Je[1], ch);
+        if constexpr (NE > 2) jac_column<K0, 2>(Je[2], ch);
+        if constexpr (NE > 3) jac_column<K0, 3>(Je[3], ch);
+        if constexpr (NE > 4) jac_column<K0, 4>(Je[4], ch);
+        if constexpr (NE > 5) jac_column<K0, 5>(Je[5], ch);
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             Gae[e] = sens_hessian(Je[e], Ja, ch.ax[e], r);
@@ -171,8 +94,8 @@ SEQIK_HD int32_t sens_stage(const JacChain &ch, const SensBounds &sb, const doub
     const double Gaa = sens_hessian(Ja, Ja, ch.ax[A], r);
     const double Gab = TWO ? sens_hessian(Ja, Jb, ch.ax[A], r) : 0.0;
     const double Gbb = TWO ? sens_hessian(Jb, Jb, ch.ax[TWO ? B : A], r) : 0.0;
-    const bool held_a = sens_held(q[A], sb.lb[A], sb.ub[A], sens_dot(Ja, r), tol);
-    const bool held_b = TWO ? sens_held(q[TWO ? B : A], sb.lb[TWO ? B : A], sb.ub[TWO ? B : A], sens_dot(Jb, r), tol) : true;
+    const bool held_a = sens_held(q[A], sb.lb[A], sb.ub[A], chain_dot(Ja, r), tol);
+    const bool held_b = TWO ? sens_held(q[TWO ? B : A], sb.lb[TWO ? B : A], sb.ub[TWO ? B : A], chain_dot(Jb, r), tol) : true;
     const bool both = !held_a && !held_b;
     const double det = Gaa * Gbb - Gab * Gab;
     // positive definite on the free DOFs (nothing free: nothing to test)
@@ -217,7 +140,7 @@ struct SensResult {
 };
 
 // ang [7], pose [5][3], kp_sigma [4] nullable (read for the domain test only: given exactly when std is wanted).
-SEQIK_HD void sens_leg_frame_rule(const FkLeg &fl, const SensBounds &sb, const double *ang, const double *pose,
+SEQIK_HD void sens_leg_frame_rule(const FkLeg &fl, const LegBounds &sb, const double *ang, const double *pose,
                                   const double *kp_sigma, double tol, SensResult &res)
 {
     double x[7], kp[15];
@@ -241,7 +164,7 @@ SEQIK_HD void sens_leg_frame_rule(const FkLeg &fl, const SensBounds &sb, const d
         for (int d = 0; d < 7; ++d) x[d] = 0.0;
     }
     JacChain ch;
-    sens_chain_walk(fl, x, ch);
+    seq_chain_walk(fl, x, ch);
     int32_t flags = sens_stage<1>(ch, sb, x, kp, tol, res.S);
     flags |= sens_stage<2>(ch, sb, x, kp, tol, res.S);
     flags |= sens_stage<3>(ch, sb, x, kp, tol, res.S);
@@ -260,7 +183,7 @@ SEQIK_HD void sens_emit_one(Sink &sink, const SensResult &res)
 }
 
 // Hands the record to `sink.template put<IDX>(v)`, IDX = 12 * DOF + 3 * (k - 1) + component, each IDX once and in
-// increasing order (the sinks of seqik_jacobian.hpp / seqik_leg_map.hpp).
+// increasing order (the sinks of seqik_leg_chain.hpp).
 template <class Sink, int... IDX>
 SEQIK_HD void sens_emit_all(Sink &sink, const SensResult &res, std::integer_sequence<int, IDX...>)
 {
@@ -294,13 +217,13 @@ SEQIK_HD void sens_std(const SensResult &res, const double *kp_sigma, double *ou
 }
 
 // One leg-frame.  sens [7][4][3], std [7], flags [1]: each nullable (std needs kp_sigma).
-SEQIK_HD void sens_leg_frame(const FkLeg &fl, const SensBounds &sb, const double *ang, const double *pose,
+SEQIK_HD void sens_leg_frame(const FkLeg &fl, const LegBounds &sb, const double *ang, const double *pose,
                              const double *kp_sigma, double tol, double *sens, double *std_out, int32_t *flags)
 {
     SensResult res;
     sens_leg_frame_rule(fl, sb, ang, pose, std_out ? kp_sigma : nullptr, tol, res);
     if (sens) {
-        JacArraySink sink{sens};
+        ArraySink sink{sens};
         sens_emit(sink, res);
     }
     if (std_out) sens_std(res, kp_sigma, std_out);

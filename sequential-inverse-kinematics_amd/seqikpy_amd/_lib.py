@@ -28,7 +28,7 @@ COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
-                "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp"]
+                "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp", "seqik_leg_chain.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 

@@ -4,6 +4,7 @@
 // other, so that the CPU-only test tier can hold it to its bound and its identities; the GPU tier compares the kernel with
 // it bit for bit.  Built by tests/test_jacobians.py through harness_build.build_harness.
 #include "../../sequential-inverse-kinematics_amd/csrc/seqik_jacobian.hpp"
+#include "staged_pass.hpp"
 
 // angles [n][7] (DOFS order), qdot nullable [n][7]; jac [n][4][3][7], sigma [n][8], vel [n][4][3]: each nullable
 extern "C" int harness_leg_jacobians(const double *angles, int64_t n, const SeqikLegParams *leg, int32_t kind,
@@ -32,11 +33,11 @@ extern "C" int harness_leg_jacobians_reduce_only(const double *angles, int64_t n
     for (int64_t i = 0; i < n; ++i) {
         double *s = sigma ? sigma + i * seqik::kJacSigma : nullptr, *v = vel ? vel + i * seqik::kJacVel : nullptr;
         if (kind == seqik::FK_KIND_SEQ) {
-            seqik::JacBothSink<seqik::FK_KIND_SEQ, false, true, seqik::JacArraySink> sink;
+            seqik::JacBothSink<seqik::FK_KIND_SEQ, false, true, seqik::ArraySink> sink;
             sink.red.begin(vel ? qdot + i * 7 : nullptr);
             sink.red.finish(seqik::leg_jacobian_walk<seqik::FK_KIND_SEQ>(fl, angles + i * 7, sink), s, v);
         } else {
-            seqik::JacBothSink<seqik::FK_KIND_GENERIC, false, true, seqik::JacArraySink> sink;
+            seqik::JacBothSink<seqik::FK_KIND_GENERIC, false, true, seqik::ArraySink> sink;
             sink.red.begin(vel ? qdot + i * 7 : nullptr);
             sink.red.finish(seqik::leg_jacobian_walk<seqik::FK_KIND_GENERIC>(fl, angles + i * 7, sink), s, v);
         }
@@ -44,29 +45,17 @@ extern "C" int harness_leg_jacobians_reduce_only(const double *angles, int64_t n
     return SEQIK_OK;
 }
 
-// The kernel's staged pass re-enacted on the host: 64 lanes, four per record, each keeping its quarter (21 values) through
-// JacQuadSink and writing it at lane * 21 of a staging image that is then copied out row by row -- n must be a multiple
-// of 16.  Must equal harness_leg_jacobians bit for bit.
+// The kernel's staged pass on the host (staged_pass.hpp), n a multiple of 16: must equal harness_leg_jacobians bit for bit.
 extern "C" int harness_leg_jacobians_staged(const double *angles, int64_t n, const SeqikLegParams *leg, int32_t kind,
                                             double *jac)
 {
     if ((kind != seqik::FK_KIND_SEQ && kind != seqik::FK_KIND_GENERIC) || n % 16) return SEQIK_ERR_BAD_ARG;
     seqik::FkLeg fl;
     seqik::make_fk_leg(*leg, fl);
-    double st[64 * seqik::kJacQuad];
-    for (int64_t r0 = 0; r0 < n; r0 += 16) {
-        for (int lane = 0; lane < 64; ++lane) {
-            const int64_t rec = r0 + (lane >> 2);
-            seqik::JacQuadSink sink;
-            sink.q = lane & 3;
-            if (kind == seqik::FK_KIND_SEQ) seqik::leg_jacobian_walk<seqik::FK_KIND_SEQ>(fl, angles + rec * 7, sink);
-            else seqik::leg_jacobian_walk<seqik::FK_KIND_GENERIC>(fl, angles + rec * 7, sink);
-            for (int j = 0; j < seqik::kJacQuad; ++j) st[lane * seqik::kJacQuad + j] = sink.buf[j];
-        }
-        double *gj = jac + r0 * seqik::kJacRow;
-        for (int k = 0; k < seqik::kJacQuad; ++k)
-            for (int lane = 0; lane < 64; ++lane) gj[k * 64 + lane] = st[k * 64 + lane];
-    }
+    staged_pass_host<seqik::kJacQuad>(n, jac, [&](int64_t rec, seqik::QuadSink<seqik::kJacQuad> &sink) {
+        if (kind == seqik::FK_KIND_SEQ) seqik::leg_jacobian_walk<seqik::FK_KIND_SEQ>(fl, angles + rec * 7, sink);
+        else seqik::leg_jacobian_walk<seqik::FK_KIND_GENERIC>(fl, angles + rec * 7, sink);
+    });
     return SEQIK_OK;
 }
 

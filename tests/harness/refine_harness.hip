@@ -14,9 +14,9 @@ extern "C" int harness_refine_legs(const double *angles, const double *pose, int
 {
     if (!angles || !pose || !angles_out || max_iter < 1 || max_iter > 255) return SEQIK_ERR_BAD_ARG;
     seqik::FkLeg fl;
-    seqik::SensBounds sb;
+    seqik::LegBounds sb;
     seqik::make_fk_leg(*leg, fl);
-    seqik::make_sens_bounds(*leg, sb);
+    seqik::make_leg_bounds(*leg, sb);
     seqik::RefineOptions opt;
     opt.max_iter = max_iter; opt.gtol = gtol; opt.ftol = ftol; opt.pad_ = 0;
     for (int64_t i = 0; i < n; ++i)

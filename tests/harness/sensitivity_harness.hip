@@ -4,6 +4,7 @@
 // the other, so that the CPU-only test tier can hold it to its bound, its identities and the solver; the GPU tier
 // compares the kernel with it bit for bit.  Built by tests/test_sensitivity.py through harness_build.build_harness.
 #include "../../sequential-inverse-kinematics_amd/csrc/seqik_sensitivity.hpp"
+#include "staged_pass.hpp"
 
 // angles [n][7] (DOFS order), pose [n][5][3], kp_sigma nullable [n][4]; sens [n][7][4][3], std [n][7], flags [n]: each
 // nullable (std needs kp_sigma)
@@ -13,9 +14,9 @@ extern "C" int harness_fit_sensitivity(const double *angles, const double *pose,
 {
     if (std_out && !kp_sigma) return SEQIK_ERR_BAD_ARG;
     seqik::FkLeg fl;
-    seqik::SensBounds sb;
+    seqik::LegBounds sb;
     seqik::make_fk_leg(*leg, fl);
-    seqik::make_sens_bounds(*leg, sb);
+    seqik::make_leg_bounds(*leg, sb);
     for (int64_t i = 0; i < n; ++i)
         seqik::sens_leg_frame(fl, sb, angles + i * 7, pose + i * 15, kp_sigma ? kp_sigma + i * 4 : nullptr, bound_tol,
                               sens ? sens + i * seqik::kSensRow : nullptr, std_out ? std_out + i * seqik::kSensStd : nullptr,
@@ -23,31 +24,19 @@ extern "C" int harness_fit_sensitivity(const double *angles, const double *pose,
     return SEQIK_OK;
 }
 
-// The kernel's staged pass re-enacted on the host: 64 lanes, four per record, each keeping its quarter (21 values) through
-// JacQuadSink and writing it at lane * 21 of a staging image that is then copied out row by row -- n must be a multiple
-// of 16.  Must equal harness_fit_sensitivity bit for bit.
+// The kernel's staged pass on the host (staged_pass.hpp), n a multiple of 16: must equal harness_fit_sensitivity bit for bit.
 extern "C" int harness_fit_sensitivity_staged(const double *angles, const double *pose, int64_t n, const SeqikLegParams *leg,
                                               double bound_tol, double *sens)
 {
     if (n % 16) return SEQIK_ERR_BAD_ARG;
     seqik::FkLeg fl;
-    seqik::SensBounds sb;
+    seqik::LegBounds sb;
     seqik::make_fk_leg(*leg, fl);
-    seqik::make_sens_bounds(*leg, sb);
-    double st[64 * seqik::kSensQuad];
-    for (int64_t r0 = 0; r0 < n; r0 += 16) {
-        for (int lane = 0; lane < 64; ++lane) {
-            const int64_t rec = r0 + (lane >> 2);
-            seqik::SensResult res;
-            seqik::sens_leg_frame_rule(fl, sb, angles + rec * 7, pose + rec * 15, nullptr, bound_tol, res);
-            seqik::JacQuadSink sink;
-            sink.q = lane & 3;
-            seqik::sens_emit(sink, res);
-            for (int j = 0; j < seqik::kSensQuad; ++j) st[lane * seqik::kSensQuad + j] = sink.buf[j];
-        }
-        double *gs = sens + r0 * seqik::kSensRow;
-        for (int k = 0; k < seqik::kSensQuad; ++k)
-            for (int lane = 0; lane < 64; ++lane) gs[k * 64 + lane] = st[k * 64 + lane];
-    }
+    seqik::make_leg_bounds(*leg, sb);
+    staged_pass_host<seqik::kSensQuad>(n, sens, [&](int64_t rec, seqik::QuadSink<seqik::kSensQuad> &sink) {
+        seqik::SensResult res;
+        seqik::sens_leg_frame_rule(fl, sb, angles + rec * 7, pose + rec * 15, nullptr, bound_tol, res);
+        seqik::sens_emit(sink, res);
+    });
     return SEQIK_OK;
 }
