@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--refine", action="store_true",
                     help="afterwards refine the sequential angles against all four key points at once, every frame on its own "
                          "(LegInvKinSeq.run_refine), and print the fit error before and after")
+    ap.add_argument("--smooth", type=float, default=None, metavar="MU",
+                    help="afterwards fit every leg's whole trajectory at once, with the penalty MU (dimensionless; try 0.1) on "
+                         "the change of every angle from frame to frame (LegInvKinSeq.run_smooth), and print what it did")
     args = ap.parse_args()
     if args.path:
         data_path = Path(args.path)
@@ -65,6 +68,14 @@ def main():
             info = seq_ik.refine_report[name.split("_")[0]]["info"]
             print(f"  {name}: rms key-point distance {np.sqrt((before[name] ** 2).mean()):.4f} -> "
                   f"{np.sqrt((after[name] ** 2).mean()):.4f}, median {int(np.median((info >> 16) & 255))} iterations")
+
+    if args.smooth is not None:
+        start = time.time()
+        seq_ik.run_smooth(smooth=args.smooth, export_path=export)
+        print(f"Trajectory refinement (smooth = {args.smooth}) took {time.time() - start:.3f} s")
+        for leg, rep in seq_ik.smooth_report.items():
+            print(f"  {leg}: cost {rep['cost'][0]:.4f} -> {rep['cost'][1]:.4f} in {rep['steps']} steps (stop reason {rep['reason']}), "
+                  f"largest frame-to-frame change {rep['largest_change'][0]:.3f} -> {rep['largest_change'][1]:.3f} rad")
 
     if args.generic:
         start = time.time()

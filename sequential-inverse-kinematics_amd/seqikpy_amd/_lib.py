@@ -24,11 +24,13 @@ _LIB_DIR = CSRC if _IN_TREE else _NATIVE
 LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so"))  # SEQIK_LIB: A/B builds
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
-                 "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip", "seqik_refine.hip"]
+                 "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip", "seqik_refine.hip",
+                 "seqik_smooth.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
-                "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp", "seqik_leg_chain.hpp"]
+                "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp", "seqik_leg_chain.hpp",
+                "seqik_smooth.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -149,6 +151,12 @@ class SeqikHeadAffine(ctypes.Structure):
 class SeqikRefineOptions(ctypes.Structure):
     """Mirror of ``struct SeqikRefineOptions`` (include/seqik_refine.h)."""
     _fields_ = [("max_iter", ctypes.c_int32), ("gtol", ctypes.c_double), ("ftol", ctypes.c_double)]
+
+
+class SeqikSmoothOptions(ctypes.Structure):
+    """Mirror of ``struct SeqikSmoothOptions`` (include/seqik_smooth.h)."""
+    _fields_ = [("smooth", ctypes.c_double * 7), ("max_iter", ctypes.c_int32), ("gtol", ctypes.c_double),
+                ("ftol", ctypes.c_double)]
 
 
 def make_head_affine(origin, scale_base, scale_tip, template_base) -> SeqikHeadAffine:
@@ -275,6 +283,16 @@ REFINE_SIGNATURES = {
         ("seqik_refine_legs_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _ropt, _vp, _vp, _vp, _vp)),
 }
 
+# The same for the trajectory refinement (include/seqik_smooth.h): a seventh table.
+_sopt = ctypes.POINTER(SeqikSmoothOptions)
+SMOOTH_SIGNATURES = {
+    "seqik_smooth.h": (
+        ("seqik_smooth_workspace_bytes", _i64, _i64, _i32, _i64),
+        ("seqik_smooth_legs", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _sopt, _dp, _ip, _dp, _ip, _i32),
+        ("seqik_smooth_legs_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _sopt, _vp, _vp, _vp, _vp, _vp,
+         _i64, _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -379,7 +397,8 @@ def load():
                                     "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`)")
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
                            list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values()) +
-                           list(SENSITIVITY_SIGNATURES.values()) + list(REFINE_SIGNATURES.values())):
+                           list(SENSITIVITY_SIGNATURES.values()) + list(REFINE_SIGNATURES.values()) +
+                           list(SMOOTH_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -1418,3 +1437,75 @@ def solve_seq_device(d_pose, n_seq, n_legs, n_frames, legs, d_angles, d_fk=0, d_
           _ptr(d_nfev, "nfev", shape(4), "int32"), _ptr(d_init, "init", (n_seq, n_legs, 7)),
           ctypes.byref(layout) if layout is not None else None, _affine_array(affine, n_legs), ctypes.byref(opt),
           _stream_ptr(stream))
+
+
+#: entry points of include/seqik_smooth.h (trajectory refinement: the whole-leg fit with smoothness across frames),
+#: additive to ABI 7
+SMOOTH_EXPORTED_SYMBOLS = [sig[0] for sig in SMOOTH_SIGNATURES["seqik_smooth.h"]]
+SMOOTH_DEFAULT, SMOOTH_MAX_ITER = 0.1, 300   # SEQIK_SMOOTH_DEFAULT / SEQIK_SMOOTH_MAX_ITER
+
+
+def _smooth_options(smooth, max_iter, gtol, ftol):
+    s = np.asarray(smooth, dtype=np.float64)
+    if s.shape not in ((), (7,)):
+        raise ValueError(f"smooth must be a scalar or (7,), got {s.shape}")
+    return ctypes.byref(SeqikSmoothOptions((ctypes.c_double * 7)(*np.broadcast_to(s, (7,))), int(max_iter), float(gtol),
+                                           float(ftol)))
+
+
+def smooth_workspace_bytes(n_seq, n_legs, n_frames):
+    """``seqik_smooth_workspace_bytes``: the device workspace ``smooth_legs_device`` needs for these sizes."""
+    n = (_lib or load()).seqik_smooth_workspace_bytes(int(n_seq), int(n_legs), int(n_frames))
+    if n < 0:
+        _raise(ERR_ARG)
+    return n
+
+
+def smooth_legs(angles, pose, legs, smooth=SMOOTH_DEFAULT, kp_weight=None, max_iter=SMOOTH_MAX_ITER, gtol=REFINE_GTOL,
+                ftol=REFINE_FTOL, device=None):
+    """``seqik_smooth_legs`` on host arrays: angles (S, L, N, 7) of the sequential chain -- normally the sequential fit's
+    -- and the aligned key points (S, L, N, 5, 3) -> dict(angles (S, L, N, 7), frame_info (S, L, N) int32, cost (S, L,
+    2), info (S, L, 3) int32).
+
+    Every (sequence, leg) pair is ONE trajectory: a bounded Levenberg-Marquardt minimises, over all frames at once, the
+    data term of ``refine_legs`` plus ``smooth[j] * len^2`` times the squared change of angle j between neighbouring
+    frames (``smooth``: a scalar or (7,), dimensionless; ``len``: the leg length), inside ``legs[l].bounds``.  A frame
+    with non-finite input (``frame_info`` bit 24, ``REFINE_BAD_INPUT``) gets NaN angles, takes no part and cuts the
+    coupling there.  ``frame_info`` bits 0..6: DOF held on a limit.  ``cost[..., 0]`` is the objective at the clamped
+    start, ``cost[..., 1]`` at the result (never larger).  ``info[..., 0]``: why the trajectory stopped
+    (``REFINE_STOP_*``), ``info[..., 1]`` its accepted steps, ``info[..., 2]`` its rejected trials.  ``kp_weight``,
+    ``gtol``, ``ftol``: as ``refine_legs``; ``max_iter`` 1..1000.  ``device=None``: the current device."""
+    angles, (S, L, N), _, head = _angles_batch(angles, legs, 0)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.shape != (S, L, N, 5, 3):
+        raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    weight = None
+    if kp_weight is not None:
+        try:
+            weight = np.ascontiguousarray(np.broadcast_to(np.asarray(kp_weight, dtype=np.float64), (S, L, N, 4)))
+        except ValueError:
+            raise ValueError(f"kp_weight must broadcast to {(S, L, N, 4)}") from None
+    out = np.full((S, L, N, 7), np.nan)
+    finfo = np.zeros((S, L, N), dtype=np.int32)
+    cost = np.full((S, L, 2), np.nan)
+    info = np.zeros((S, L, 3), dtype=np.int32)
+    _call("seqik_smooth_legs", head[0], _data(pose), *head[1:], _data(weight), _smooth_options(smooth, max_iter, gtol, ftol),
+          _data(out), _data(finfo, _ip), _data(cost), _data(info, _ip), -1 if device is None else int(device))
+    return dict(angles=out, frame_info=finfo, cost=cost, info=info)
+
+
+def smooth_legs_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_angles_out, d_workspace, workspace_bytes,
+                       d_kp_weight=0, d_frame_info=0, d_cost=0, d_info=0, smooth=SMOOTH_DEFAULT, max_iter=SMOOTH_MAX_ITER,
+                       gtol=REFINE_GTOL, ftol=REFINE_FTOL, stream=None):
+    """``seqik_smooth_legs_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_smooth.h`` (``d_angles_out`` may be ``d_angles``; ``d_frame_info`` (S, L, N) int32, ``d_cost`` (S, L,
+    2) doubles, ``d_info`` (S, L, 3) int32; 0 / None: all weights 1, not written) and a workspace of
+    ``smooth_workspace_bytes`` bytes (a pointer, or a uint8 tensor), on ``stream`` of the current device.  UNLIKE THE OTHER
+    ``*_device`` WRAPPERS THIS ONE SYNCHRONISES THE STREAM, once per trial round; it returns with the last launch enqueued."""
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, 0)
+    tl = lf[:2]
+    _call("seqik_smooth_legs_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
+          _ptr(d_kp_weight, "kp_weight", lf + (4,)), _smooth_options(smooth, max_iter, gtol, ftol),
+          _ptr(d_angles_out, "angles_out", lf + (7,)), _ptr(d_frame_info, "frame_info", lf, dtype="int32"),
+          _ptr(d_cost, "cost", tl + (2,)), _ptr(d_info, "info", tl + (3,), dtype="int32"),
+          _ptr(d_workspace, "workspace", None, dtype="uint8"), int(workspace_bytes), _stream_ptr(stream))

@@ -497,6 +497,8 @@ class LegInvKinSeq(LegInvKinBase):
         self.frame_chunk_report = {}
         #: per leg, ``cost`` (N, 2) and ``info`` (N,) of the last ``run_refine``
         self.refine_report = {}
+        #: per leg, what the last ``run_smooth`` reports of its trajectory
+        self.smooth_report = {}
 
     def _fk_key_points(self, leg_name, segment_array):
         """Key points in the frame the solver works in: with ``leg_affine`` ``aligned_pos`` holds RAW key points and the
@@ -565,6 +567,20 @@ class LegInvKinSeq(LegInvKinBase):
                 out[f"Angle_{leg_name}_{dof}"] = res["std"][:, di].copy()
         return out
 
+    @staticmethod
+    def _key_point_weights(items, n, key_point_weight):
+        """``key_point_weight`` of ``run_refine`` / ``run_smooth`` for one batch of legs -> (1, L, n, 4), or None."""
+        if key_point_weight is None:
+            return None
+        weight = np.empty((1, len(items), n, 4))
+        for li, (_, leg_name, _, _) in enumerate(items):
+            w = key_point_weight[leg_name] if isinstance(key_point_weight, dict) else key_point_weight
+            w = np.asarray(w, dtype=np.float64)
+            if w.shape not in ((), (4,), (n, 4)):
+                raise ValueError(f"key_point_weight must be a scalar, (4,) or ({n}, 4), got {w.shape}")
+            weight[0, li] = w
+        return weight
+
     # -- whole-leg refinement (include/seqik_refine.h) ------------------------------------------
     def run_refine(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, key_point_weight=None,
                    export_path: Union[Path, str] = None, **opts
@@ -592,16 +608,7 @@ class LegInvKinSeq(LegInvKinBase):
         angles_out, fk_out, report = {}, {}, {}
         for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
             legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
-            n = angles.shape[2]
-            weight = None
-            if key_point_weight is not None:
-                weight = np.empty((1, len(items), n, 4))
-                for li, (_, leg_name, _, _) in enumerate(items):
-                    w = key_point_weight[leg_name] if isinstance(key_point_weight, dict) else key_point_weight
-                    w = np.asarray(w, dtype=np.float64)
-                    if w.shape not in ((), (4,), (n, 4)):
-                        raise ValueError(f"key_point_weight must be a scalar, (4,) or ({n}, 4), got {w.shape}")
-                    weight[0, li] = w
+            weight = self._key_point_weights(items, angles.shape[2], key_point_weight)
             res = _lib.refine_legs(angles, pose, legs, kp_weight=weight, device=self.device, **opts)
             fk = _lib.forward_kinematics(res["angles"], legs, kind=self._fk_kind, origin=pose[..., 0, :],
                                          device=self.device)["fk"]
@@ -620,6 +627,52 @@ class LegInvKinSeq(LegInvKinBase):
             save_file(Path(export_path) / "forward_kinematics_refined.pkl", fk_out)
             self.logger.info("Refined joint angles and forward kinematics are saved at %s", export_path)
         return angles_out, fk_out
+
+    # -- trajectory refinement (include/seqik_smooth.h) ------------------------------------------
+    def run_smooth(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, smooth=_lib.SMOOTH_DEFAULT,
+                   key_point_weight=None, export_path: Union[Path, str] = None, **opts) -> Dict[str, np.ndarray]:
+        """The whole-leg fit of ``run_refine`` over ALL frames of a leg at once, with a penalty on the change of every
+        angle from frame to frame, on the GPU (``seqik_smooth_legs``).
+
+        ``run_refine`` fits every frame on its own, and where a leg has two configurations that fit, neighbouring frames
+        land in different ones: the per-frame fit improves and the trajectory gets worse.  This starts from
+        ``joint_angles`` (default: the stored angles of the last ``run_ik_and_fk``) and minimises, per leg, the summed
+        squared key-point distances of all frames plus ``smooth[j] * leg_length^2`` times the squared change of angle j
+        between neighbouring frames, inside the joint limits, by one bounded Levenberg-Marquardt for the whole
+        trajectory.  ``smooth``: a scalar or ``(7,)`` in ``DOFS`` order, dimensionless (0.1 removes the 2.6 rad jumps of
+        the shipped recording's RF leg; 0.01 leaves most of them).  A frame with a non-finite angle or key point comes
+        back as NaN and cuts the coupling between its neighbours.  It is a LOCAL method: it ends in the minimum its start
+        leads to.
+
+        ``key_point_weight``: as ``run_refine``.  ``opts``: ``max_iter`` (accepted steps, default 300), ``gtol``,
+        ``ftol`` of ``_lib.smooth_legs``.  Returns the joint-angle dictionary shaped as ``run_ik_and_fk`` returns it;
+        ``self.joint_angles_dict`` is NOT overwritten.  ``self.smooth_report[leg]`` holds ``cost`` ``(2,)`` -- the
+        objective at the clamped start and at the result --, ``reason`` (``_lib.REFINE_STOP_*``), ``steps``,
+        ``rejected``, ``frame_info`` ``(N,)`` and ``largest_change`` ``(2,)``: the largest frame-to-frame change of any
+        angle before and after, radians.  ``export_path``: writes ``leg_joint_angles_smooth.pkl`` there."""
+        unknown = set(opts) - {"max_iter", "gtol", "ftol"}
+        if unknown:
+            raise ValueError(f"unknown smoothing options: {sorted(unknown)}")
+        angles_out, report = {}, {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
+            weight = self._key_point_weights(items, angles.shape[2], key_point_weight)
+            res = _lib.smooth_legs(angles, pose, legs, smooth=smooth, kp_weight=weight, device=self.device, **opts)
+            for li, (_, leg_name, _, _) in enumerate(items):
+                for di, dof in enumerate(DOFS):
+                    angles_out[f"Angle_{leg_name}_{dof}"] = res["angles"][0, li, :, di].copy()
+                change = [np.abs(np.diff(a[0, li], axis=0)) for a in (angles, res["angles"])]
+                change = [float(c[np.isfinite(c)].max()) if np.isfinite(c).any() else 0.0 for c in change]
+                reason, steps, rejected = (int(v) for v in res["info"][0, li])
+                report[leg_name] = dict(cost=res["cost"][0, li].copy(), reason=reason, steps=steps, rejected=rejected,
+                                        frame_info=res["frame_info"][0, li].copy(), largest_change=np.array(change))
+        order = [leg_name for _, leg_name, _ in self._leg_segments()]
+        angles_out = {f"Angle_{leg_name}_{dof}": angles_out[f"Angle_{leg_name}_{dof}"] for leg_name in order for dof in DOFS}
+        self.smooth_report = {leg_name: report[leg_name] for leg_name in order}
+        if export_path is not None:
+            save_file(Path(export_path) / "leg_joint_angles_smooth.pkl", angles_out)
+            self.logger.info("Smoothed joint angles are saved at %s", export_path)
+        return angles_out
 
     def _prior_angles(self, leg_name, n_frames, first_stage):
         """(N, 7) array with the columns of stages < first_stage taken from ``joint_angles_dict``
@@ -822,6 +875,10 @@ class LegInvKinGeneric(LegInvKinBase):
         """Not built for the generic chain: raises ``NotImplementedError`` (see ``LegInvKinSeq.run_refine``)."""
         raise NotImplementedError("the whole-leg refinement is built for the sequential chain only: the generic chain "
                                   "already fits all seven angles at once, to the claw alone (use LegInvKinSeq)")
+
+    def run_smooth(self, joint_angles=None, smooth=_lib.SMOOTH_DEFAULT, key_point_weight=None, export_path=None, **opts):
+        """Not built for the generic chain: raises ``NotImplementedError`` (see ``LegInvKinSeq.run_smooth``)."""
+        raise NotImplementedError("the trajectory refinement is built for the sequential chain only (use LegInvKinSeq)")
 
     def _store(self, leg_name, angles):
         # key order of the reference: the chain's link order, Base and Claw skipped (:533-539)
