@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "sequential-inverse-kinematics_amd"))
 
 import numpy as np  # noqa: E402
 
-from seqikpy_amd.data import BOUNDS, INITIAL_ANGLES  # noqa: E402
+from seqikpy_amd.data import BOUNDS, DOFS, INITIAL_ANGLES  # noqa: E402
 from seqikpy_amd.kinematic_chain import KinematicChainGeneric, KinematicChainSeq  # noqa: E402
 from seqikpy_amd.leg_inverse_kinematics import LegInvKinGeneric, LegInvKinSeq  # noqa: E402
 from seqikpy_amd.utils import load_file  # noqa: E402
@@ -37,6 +37,10 @@ def main():
     ap.add_argument("--refine", action="store_true",
                     help="afterwards refine the sequential angles against all four key points at once, every frame on its own "
                          "(LegInvKinSeq.run_refine), and print the fit error before and after")
+    ap.add_argument("--sigma", type=float, default=None, metavar="X",
+                    help="with --refine: the standard deviation of every aligned key point, in their units; prints the "
+                         "median and the largest standard deviation it gives every refined angle "
+                         "(LegInvKinSeq.run_refine(key_point_sigma=X))")
     ap.add_argument("--smooth", type=float, default=None, metavar="MU",
                     help="afterwards fit every leg's whole trajectory at once, with the penalty MU (dimensionless; try 0.1) on "
                          "the change of every angle from frame to frame (LegInvKinSeq.run_smooth), and print what it did")
@@ -61,13 +65,19 @@ def main():
 
     if args.refine:
         start = time.time()
-        angles_ref, _ = seq_ik.run_refine(export_path=export)
+        angles_ref, _ = seq_ik.run_refine(export_path=export, key_point_sigma=args.sigma)
         print(f"Whole-leg refinement took {time.time() - start:.3f} s")
         before, after = seq_ik.fit_error(angles_seq), seq_ik.fit_error(angles_ref)
         for name in before:
             info = seq_ik.refine_report[name.split("_")[0]]["info"]
             print(f"  {name}: rms key-point distance {np.sqrt((before[name] ** 2).mean()):.4f} -> "
                   f"{np.sqrt((after[name] ** 2).mean()):.4f}, median {int(np.median((info >> 16) & 255))} iterations")
+        if args.sigma is not None:
+            print(f"  standard deviation of the refined angles at key-point sigma {args.sigma} (median / largest, rad):")
+            for leg, rep in seq_ik.refine_report.items():
+                std = rep["std"]
+                print(f"  {leg}: " + ", ".join(f"{dof} {np.nanmedian(std[:, i]):.4f} / {np.nanmax(std[:, i]):.4f}"
+                                              for i, dof in enumerate(DOFS)))
 
     if args.smooth is not None:
         start = time.time()

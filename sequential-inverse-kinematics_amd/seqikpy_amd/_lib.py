@@ -25,12 +25,12 @@ LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so")
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
                  "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip", "seqik_refine.hip",
-                 "seqik_smooth.hip"]
+                 "seqik_smooth.hip", "seqik_refine_sens.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
                 "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp", "seqik_leg_chain.hpp",
-                "seqik_smooth.hpp"]
+                "seqik_smooth.hpp", "seqik_refine_sens.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -293,6 +293,14 @@ SMOOTH_SIGNATURES = {
          _i64, _vp)),
 }
 
+# The same for the error bars of the whole-leg refinement (include/seqik_refine_sensitivity.h): an eighth table.
+REFINE_SENS_SIGNATURES = {
+    "seqik_refine_sensitivity.h": (
+        ("seqik_refine_sensitivity", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _dp, _f64, _dp, _dp, _dp, _ip, _i32),
+        ("seqik_refine_sensitivity_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _f64, _vp, _vp, _vp, _vp,
+         _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -398,7 +406,7 @@ def load():
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
                            list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values()) +
                            list(SENSITIVITY_SIGNATURES.values()) + list(REFINE_SIGNATURES.values()) +
-                           list(SMOOTH_SIGNATURES.values())):
+                           list(SMOOTH_SIGNATURES.values()) + list(REFINE_SENS_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -740,6 +748,70 @@ def refine_legs_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_angles
           _ptr(d_kp_weight, "kp_weight", lf + (4,)), _refine_options(max_iter, gtol, ftol),
           _ptr(d_angles_out, "angles_out", lf + (7,)), _ptr(d_cost, "cost", lf + (2,)),
           _ptr(d_info, "info", lf, dtype="int32"), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_refine_sensitivity.h (error bars of the whole-leg refinement), additive to ABI 7
+REFINE_SENS_EXPORTED_SYMBOLS = [sig[0] for sig in REFINE_SENS_SIGNATURES["seqik_refine_sensitivity.h"]]
+REFINE_SENS_FLAG_NOT_PD = 1 << 8
+REFINE_SENS_FLAG_BAD_INPUT = 1 << 16
+
+
+def refine_sensitivity(angles, pose, legs, kp_weight=None, kp_sigma=None, bound_tol=SENS_BOUND_TOL, want_sens=True,
+                       want_std=None, want_grad=True, want_flags=True, device=None):
+    """``seqik_refine_sensitivity`` on host arrays: angles (S, L, N, 7) that minimise the whole-leg fit -- the output of
+    ``refine_legs`` -- and the aligned key points (S, L, N, 5, 3) they were fitted to -> dict(sens (S, L, N, 7, 4, 3),
+    std (S, L, N, 7), grad (S, L, N), flags (S, L, N) int32; None for what is not asked for).
+
+    ``sens[..., d, k, c]`` is the derivative of the refined angle of ``DOFS[d]`` with respect to component c of aligned
+    key point k + 1: the inverse of the exact Hessian of the whole-leg fit on the free joints applied to the weighted
+    Jacobian (not the pseudo-inverse of the Jacobian, and not ``fit_sensitivity``'s block-triangular response of the
+    four sequential solves); 0 for a joint that sits on a limit of ``legs[l].bounds`` (within ``bound_tol`` rad; 0:
+    never) and is pushed against it.  THE VALUES ARE THE FIT'S RESPONSE ONLY AT ANGLES THAT MINIMISE IT: ``grad`` -- the
+    left side of the gradient test of ``refine_legs`` at these angles -- tells whether they do.  ``kp_weight``: the
+    weights the fit was made with (as ``refine_legs``; a key point with weight exactly 0 is not read and its columns
+    are 0).  ``std`` (``want_std``; default: whenever ``kp_sigma`` -- a scalar, (4,), or anything that broadcasts to (S,
+    L, N, 4) -- is given): the standard deviation that key-point noise gives every angle.  ``flags``: bits 0..6 DOF held
+    (``sens_flag_held``), bit 8 (``REFINE_SENS_FLAG_NOT_PD``) the angles are not a strict minimum (the rows of the free
+    joints are NaN), bit 16 bad input (the leg-frame's values are NaN).  At least one of the four must be asked for.
+    ``device=None``: the current device."""
+    angles, (S, L, N), _, head = _angles_batch(angles, legs, 0)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.shape != (S, L, N, 5, 3):
+        raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    try:
+        weight = _sigma_batch(kp_weight, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_weight must broadcast to {(S, L, N, 4)}, got {np.shape(kp_weight)}") from None
+    try:
+        sigma = _sigma_batch(kp_sigma, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_sigma must broadcast to {(S, L, N, 4)}, got {np.shape(kp_sigma)}") from None
+    if want_std is None:
+        want_std = sigma is not None
+    if want_std and sigma is None:
+        raise ValueError("std needs kp_sigma")
+    sens = np.full((S, L, N, 7, 4, 3), np.nan) if want_sens else None
+    std = np.full((S, L, N, 7), np.nan) if want_std else None
+    grad = np.full((S, L, N), np.nan) if want_grad else None
+    flags = np.zeros((S, L, N), dtype=np.int32) if want_flags else None
+    _call("seqik_refine_sensitivity", head[0], _data(pose), *head[1:], _data(weight), _data(sigma if want_std else None),
+          float(bound_tol), _data(sens), _data(std), _data(grad), _data(flags, _ip), -1 if device is None else int(device))
+    return dict(sens=sens, std=std, grad=grad, flags=flags)
+
+
+def refine_sensitivity_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_kp_weight=0, d_kp_sigma=0, d_sens=0,
+                              d_std=0, d_grad=0, d_flags=0, bound_tol=SENS_BOUND_TOL, stream=None):
+    """``seqik_refine_sensitivity_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_refine_sensitivity.h`` (``d_pose`` (S, L, N, 5, 3), ``d_kp_weight`` and ``d_kp_sigma`` (S, L, N, 4),
+    ``d_sens`` (S, L, N, 7, 4, 3), ``d_std`` (S, L, N, 7), ``d_grad`` (S, L, N) doubles, ``d_flags`` (S, L, N) int32; 0 /
+    None: all weights 1, not computed, not written; at least one output), asynchronous on ``stream`` (a hipStream_t as
+    int, or a torch stream; None / 0 = the default stream) of the current device.  ``d_angles`` may be the output buffer
+    of ``refine_legs_device`` enqueued before it on the same stream."""
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, 0)
+    _call("seqik_refine_sensitivity_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
+          _ptr(d_kp_weight, "kp_weight", lf + (4,)), _ptr(d_kp_sigma, "kp_sigma", lf + (4,)), float(bound_tol),
+          _ptr(d_sens, "sens", lf + (7, 4, 3)), _ptr(d_std, "std", lf + (7,)), _ptr(d_grad, "grad", lf),
+          _ptr(d_flags, "flags", lf, dtype="int32"), _stream_ptr(stream))
 
 
 #: entry points of include/seqik_gaps.h (skip mode for missing key points), kept apart from the ABI-7 set of seqik.h

@@ -555,17 +555,105 @@ class LegInvKinSeq(LegInvKinBase):
                 self._sensitivity_outputs(joint_angles, None, True, True, bound_tol).items()}
 
     def angle_uncertainty(self, key_point_sigma, joint_angles: Optional[Dict[str, np.ndarray]] = None,
-                          bound_tol: float = _lib.SENS_BOUND_TOL) -> Dict[str, np.ndarray]:
+                          bound_tol: float = _lib.SENS_BOUND_TOL, fit: str = "sequential",
+                          key_point_weight=None) -> Dict[str, np.ndarray]:
         """The standard deviation that key-point noise gives every fitted angle, on the GPU (``seqik_fit_sensitivity``,
         ``std``): ``{"Angle_<leg>_<dof>": (N,)}``, radians.  ``key_point_sigma``: the isotropic standard deviation of key
         points 1..4 (CTr, FTi, TiTa, claw) in the units of the aligned key points -- a scalar, a ``(4,)`` vector, an ``(N,
         4)`` array (e.g. anipose's ``<kp>_error`` columns), or a ``{leg: one of those}`` dictionary.  A held joint has
-        0; a frame with a non-finite angle, key point or sigma has NaN."""
+        0; a frame with a non-finite angle, key point or sigma has NaN.
+
+        ``fit``: which fit ``joint_angles`` are the answer of.  ``"sequential"`` (default): ``run_ik_and_fk``'s four
+        stage solves.  ``"refine"``: the whole-leg fit of ``run_refine`` (``seqik_refine_sensitivity``); pass
+        ``run_refine``'s angles as ``joint_angles`` and the ``key_point_weight`` it was run with -- the values are that
+        fit's error bars only at angles that minimise it (``run_refine_sensitivity`` returns ``grad``, which tells)."""
+        if fit not in ("sequential", "refine"):
+            raise ValueError(f"fit must be 'sequential' or 'refine', got {fit!r}")
+        if fit == "refine":
+            res_by_segment = self._refine_sensitivity_outputs(joint_angles, key_point_weight, key_point_sigma, bound_tol,
+                                                              False, False, False)
+            return {f"Angle_{leg_name}_{dof}": res["std"][:, di].copy() for leg_name, res in res_by_segment.values()
+                    for di, dof in enumerate(DOFS)}
+        if key_point_weight is not None:
+            raise ValueError("key_point_weight belongs to fit='refine': the sequential fit has no weights")
         out = {}
         for _, (leg_name, res) in self._sensitivity_outputs(joint_angles, key_point_sigma, False, False, bound_tol).items():
             for di, dof in enumerate(DOFS):
                 out[f"Angle_{leg_name}_{dof}"] = res["std"][:, di].copy()
         return out
+
+    @staticmethod
+    def _key_point_sigmas(items, n, key_point_sigma):
+        """``key_point_sigma`` for one batch of legs -> (1, L, n, 4), or None."""
+        if key_point_sigma is None:
+            return None
+        sigma = np.empty((1, len(items), n, 4))
+        for li, (_, leg_name, _, _) in enumerate(items):
+            s = key_point_sigma[leg_name] if isinstance(key_point_sigma, dict) else key_point_sigma
+            s = np.asarray(s, dtype=np.float64)
+            if s.shape not in ((), (4,), (n, 4)):
+                raise ValueError(f"key_point_sigma must be a scalar, (4,) or ({n}, 4), got {s.shape}")
+            sigma[0, li] = s
+        return sigma
+
+    # -- error bars of the whole-leg refinement (include/seqik_refine_sensitivity.h) ------------
+    def _refine_sensitivity_outputs(self, joint_angles, key_point_weight, key_point_sigma, bound_tol, want_sens, want_grad,
+                                    want_flags):
+        """``_lib.refine_sensitivity`` per group of legs with the same frame count -> {segment_name: (leg_name, dict)}."""
+        out = {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
+            n = angles.shape[2]
+            res = _lib.refine_sensitivity(angles, pose, legs, kp_weight=self._key_point_weights(items, n, key_point_weight),
+                                          kp_sigma=self._key_point_sigmas(items, n, key_point_sigma), bound_tol=bound_tol,
+                                          want_sens=want_sens, want_grad=want_grad, want_flags=want_flags,
+                                          device=self.device)
+            for li, (segment_name, leg_name, _, _) in enumerate(items):
+                out[segment_name] = (leg_name, {k: v[0, li].copy() for k, v in res.items() if v is not None})
+        return {name: out[name] for name, _, _ in self._leg_segments()}
+
+    def run_refine_sensitivity(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, key_point_weight=None,
+                               bound_tol: float = _lib.SENS_BOUND_TOL) -> Dict[str, Dict[str, np.ndarray]]:
+        """How the angles of the whole-leg fit (``run_refine``) move when the key points move, for every leg, on the GPU
+        (``seqik_refine_sensitivity``): ``{segment_name: dict(sens (N, 7, 4, 3), flags (N,), grad (N,))}`` in the order
+        of ``aligned_pos``.  ``sens[t, d, k, c]`` is the derivative of the angle of ``DOFS[d]`` of frame t with respect
+        to component c of aligned key point k + 1, radians per length: the inverse of the fit's exact Hessian on the
+        free joints applied to the weighted Jacobian.  Unlike ``run_angle_sensitivity`` it is a full matrix -- in the
+        whole-leg fit every angle answers to every key point.
+
+        THE VALUES ARE THE WHOLE-LEG FIT'S RESPONSE ONLY AT ANGLES THAT MINIMISE THAT FIT, that is ``run_refine``'s
+        output: pass it as ``joint_angles`` (default: the stored angles, as everywhere) with the ``key_point_weight`` it
+        was run with.  ``grad`` tells whether they do: the left side of ``run_refine``'s gradient test at these angles
+        (``<= gtol``, 1e-10 by default, where the refinement stopped on it).  ``flags``: bits 0..6 joint held on a limit
+        (its row is 0), bit 8 the angles are not a strict minimum (the free rows are NaN), bit 16 bad input
+        (``_lib.refine_sensitivity``).  The key points are the class's own aligned ones (with ``leg_affine``: after the
+        fused alignment; for the RAW key points multiply by the alignment's scale).  The full covariance of a frame's
+        angles is ``S @ diag(sigma^2) @ S.T`` with ``S = sens[t].reshape(7, 12)``."""
+        return {name: res for name, (_, res) in
+                self._refine_sensitivity_outputs(joint_angles, key_point_weight, None, bound_tol, True, True, True).items()}
+
+    def _refine_with_error_bars(self, angles, pose, legs, weight, sigma, bound_tol, opts):
+        """``refine_legs_device`` then ``refine_sensitivity_device`` on the same stream: the refined angles do not leave
+        the device in between -> the dict of ``_lib.refine_legs`` plus ``std`` (1, L, N, 7) and ``sens_flags`` (1, L, N)."""
+        import torch
+        S, L, N = angles.shape[:3]
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device < 0 else self.device)
+        with torch.cuda.device(dev):
+            up = lambda a: 0 if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            d_ang, d_pose, d_w, d_sig = up(angles), up(pose), up(weight), up(sigma)
+            d_out = torch.empty((S, L, N, 7), dtype=torch.float64, device=dev)
+            d_cost = torch.empty((S, L, N, 2), dtype=torch.float64, device=dev)
+            d_info = torch.empty((S, L, N), dtype=torch.int32, device=dev)
+            d_std = torch.empty((S, L, N, 7), dtype=torch.float64, device=dev)
+            d_flags = torch.empty((S, L, N), dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.refine_legs_device(d_ang, d_pose, S, L, N, legs, d_out, d_kp_weight=d_w, d_cost=d_cost, d_info=d_info,
+                                    stream=stream, **opts)
+            _lib.refine_sensitivity_device(d_out, d_pose, S, L, N, legs, d_kp_weight=d_w, d_kp_sigma=d_sig, d_std=d_std,
+                                           d_flags=d_flags, bound_tol=bound_tol, stream=stream)
+            torch.cuda.synchronize(dev)
+            return dict(angles=d_out.cpu().numpy(), cost=d_cost.cpu().numpy(), info=d_info.cpu().numpy(),
+                        std=d_std.cpu().numpy(), sens_flags=d_flags.cpu().numpy())
 
     @staticmethod
     def _key_point_weights(items, n, key_point_weight):
@@ -583,7 +671,8 @@ class LegInvKinSeq(LegInvKinBase):
 
     # -- whole-leg refinement (include/seqik_refine.h) ------------------------------------------
     def run_refine(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, key_point_weight=None,
-                   export_path: Union[Path, str] = None, **opts
+                   export_path: Union[Path, str] = None, key_point_sigma=None,
+                   bound_tol: float = _lib.SENS_BOUND_TOL, **opts
                    ) -> Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray]]:
         """The sequential fit's angles refined against all four key points at once, on the GPU (``seqik_refine_legs``).
 
@@ -601,7 +690,13 @@ class LegInvKinSeq(LegInvKinBase):
         returns them, the forward kinematics computed from the refined angles (``seqik_forward_kinematics``);
         ``self.joint_angles_dict`` is NOT overwritten.  ``self.refine_report[leg]`` holds ``cost`` ``(N, 2)`` -- the sum
         of squares at the clamped start and at the result -- and ``info`` ``(N,)`` (``_lib.refine_legs``).
-        ``export_path``: writes ``leg_joint_angles_refined.pkl`` and ``forward_kinematics_refined.pkl`` there."""
+        ``export_path``: writes ``leg_joint_angles_refined.pkl`` and ``forward_kinematics_refined.pkl`` there.
+
+        ``key_point_sigma`` (as ``angle_uncertainty``'s; default None: nothing changes): the error bars of the refined
+        angles in the same visit to the device -- the sensitivity kernel (``seqik_refine_sensitivity_device``) reads the
+        refined angles where the refinement left them.  ``self.refine_report[leg]`` then also holds ``std`` ``(N, 7)``,
+        what ``angle_uncertainty(key_point_sigma, refined, fit="refine", key_point_weight=...)`` returns, and
+        ``sens_flags`` ``(N,)`` (``_lib.refine_sensitivity``'s flags; ``bound_tol`` is its held-joint tolerance)."""
         unknown = set(opts) - {"max_iter", "gtol", "ftol"}
         if unknown:
             raise ValueError(f"unknown refinement options: {sorted(unknown)}")
@@ -609,7 +704,11 @@ class LegInvKinSeq(LegInvKinBase):
         for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
             legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
             weight = self._key_point_weights(items, angles.shape[2], key_point_weight)
-            res = _lib.refine_legs(angles, pose, legs, kp_weight=weight, device=self.device, **opts)
+            if key_point_sigma is None:
+                res = _lib.refine_legs(angles, pose, legs, kp_weight=weight, device=self.device, **opts)
+            else:
+                sigma = self._key_point_sigmas(items, angles.shape[2], key_point_sigma)
+                res = self._refine_with_error_bars(angles, pose, legs, weight, sigma, bound_tol, opts)
             fk = _lib.forward_kinematics(res["angles"], legs, kind=self._fk_kind, origin=pose[..., 0, :],
                                          device=self.device)["fk"]
             for li, (segment_name, leg_name, _, _) in enumerate(items):
@@ -617,6 +716,8 @@ class LegInvKinSeq(LegInvKinBase):
                     angles_out[f"Angle_{leg_name}_{dof}"] = res["angles"][0, li, :, di].copy()
                 fk_out[segment_name] = fk[0, li].copy()
                 report[leg_name] = dict(cost=res["cost"][0, li].copy(), info=res["info"][0, li].copy())
+                if key_point_sigma is not None:
+                    report[leg_name].update(std=res["std"][0, li].copy(), sens_flags=res["sens_flags"][0, li].copy())
         order = [(name, leg_name) for name, leg_name, _ in self._leg_segments()]
         angles_out = {f"Angle_{leg_name}_{dof}": angles_out[f"Angle_{leg_name}_{dof}"] for _, leg_name in order
                       for dof in DOFS}
@@ -867,8 +968,12 @@ class LegInvKinGeneric(LegInvKinBase):
         raise ValueError("the generic chain has no angle sensitivity: it fits seven angles to the three coordinates of the "
                          "claw, so the angles it reports are not a function of the key points (use LegInvKinSeq)")
 
-    def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None):
+    def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None, fit="sequential", key_point_weight=None):
         """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.angle_uncertainty``)."""
+        return self.run_angle_sensitivity(joint_angles)
+
+    def run_refine_sensitivity(self, joint_angles=None, key_point_weight=None, bound_tol=None):
+        """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.run_refine_sensitivity``)."""
         return self.run_angle_sensitivity(joint_angles)
 
     def run_refine(self, joint_angles=None, key_point_weight=None, export_path=None, **opts):
