@@ -40,7 +40,8 @@ def main():
     ap.add_argument("--sigma", type=float, default=None, metavar="X",
                     help="with --refine: the standard deviation of every aligned key point, in their units; prints the "
                          "median and the largest standard deviation it gives every refined angle "
-                         "(LegInvKinSeq.run_refine(key_point_sigma=X))")
+                         "(LegInvKinSeq.run_refine(key_point_sigma=X)).  With --smooth: the median standard deviation of "
+                         "the smoothed angles per leg (LegInvKinSeq.run_smooth(key_point_sigma=X))")
     ap.add_argument("--smooth", type=float, default=None, metavar="MU",
                     help="afterwards fit every leg's whole trajectory at once, with the penalty MU (dimensionless; try 0.1) on "
                          "the change of every angle from frame to frame (LegInvKinSeq.run_smooth), and print what it did")
@@ -81,11 +82,15 @@ def main():
 
     if args.smooth is not None:
         start = time.time()
-        seq_ik.run_smooth(smooth=args.smooth, export_path=export)
+        seq_ik.run_smooth(smooth=args.smooth, export_path=export, key_point_sigma=args.sigma)
         print(f"Trajectory refinement (smooth = {args.smooth}) took {time.time() - start:.3f} s")
         for leg, rep in seq_ik.smooth_report.items():
             print(f"  {leg}: cost {rep['cost'][0]:.4f} -> {rep['cost'][1]:.4f} in {rep['steps']} steps (stop reason {rep['reason']}), "
                   f"largest frame-to-frame change {rep['largest_change'][0]:.3f} -> {rep['largest_change'][1]:.3f} rad")
+            if args.sigma is not None:
+                print(f"  {leg}: median standard deviation of the smoothed angles at key-point sigma {args.sigma}: "
+                      f"{np.nanmedian(rep['std']):.4f} rad (" +
+                      ", ".join(f"{dof} {np.nanmedian(rep['std'][:, i]):.4f}" for i, dof in enumerate(DOFS)) + ")")
 
     if args.generic:
         start = time.time()

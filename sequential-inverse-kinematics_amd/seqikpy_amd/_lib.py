@@ -25,12 +25,12 @@ LIB_PATH = os.environ.get("SEQIK_LIB", os.path.join(_LIB_DIR, "libseqik_hip.so")
 COMPILE_UNITS = ["seqik_hip.hip", "seqik_runtime.hip", "seqik_head.hip", "seqik_stream.hip", "seqik_align.hip",
                  "seqik_peer.hip", "seqik_fk.hip", "seqik_gaps.hip", "seqik_resample.hip", "seqik_frames.hip",
                  "seqik_head_align.hip", "seqik_jacobian.hip", "seqik_sensitivity.hip", "seqik_refine.hip",
-                 "seqik_smooth.hip", "seqik_refine_sens.hip"]
+                 "seqik_smooth.hip", "seqik_refine_sens.hip", "seqik_smooth_sens.hip"]
 CSRC_HEADERS = ["seqik_core.hpp", "seqik_consts.hpp", "seqik_head.hpp", "seqik_generic.hpp", "seqik_device_scope.hpp",
                 "seqik_runtime.hpp", "seqik_fk.hpp", "seqik_gaps.hpp", "seqik_resample.hpp", "seqik_frames.hpp",
                 "seqik_head_align.hpp", "seqik_jacobian.hpp", "seqik_leg_map.hpp", "seqik_head_launch.hpp",
                 "seqik_order_stats.hpp", "seqik_sensitivity.hpp", "seqik_refine.hpp", "seqik_leg_chain.hpp",
-                "seqik_smooth.hpp", "seqik_refine_sens.hpp"]
+                "seqik_smooth.hpp", "seqik_refine_sens.hpp", "seqik_smooth_sens.hpp"]
 SOURCES = COMPILE_UNITS + CSRC_HEADERS   # what a build depends on
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 
@@ -301,6 +301,16 @@ REFINE_SENS_SIGNATURES = {
          _vp)),
 }
 
+# The same for the error bars of the smoothed trajectory (include/seqik_smooth_sensitivity.h): a ninth table.
+SMOOTH_SENS_SIGNATURES = {
+    "seqik_smooth_sensitivity.h": (
+        ("seqik_smooth_sensitivity_workspace_bytes", _i64, _i64, _i32, _i64, _i32),
+        ("seqik_smooth_sensitivity", _int, _dp, _dp, _i64, _i32, _i64, _legs, _i32, _dp, _dp, _dp, _f64, _i32, _dp, _dp, _dp,
+         _ip, _i32),
+        ("seqik_smooth_sensitivity_device", _int, _vp, _vp, _i64, _i32, _i64, _legs, _i32, _vp, _vp, _dp, _f64, _i32, _vp,
+         _vp, _vp, _vp, _vp, _i64, _vp)),
+}
+
 
 class SeqikLibraryError(RuntimeError):
     pass
@@ -406,7 +416,8 @@ def load():
         for signatures in (list(SIGNATURES.values()) + list(EXTENSION_SIGNATURES.values()) +
                            list(STREAM_GAPS_SIGNATURES.values()) + list(JACOBIAN_SIGNATURES.values()) +
                            list(SENSITIVITY_SIGNATURES.values()) + list(REFINE_SIGNATURES.values()) +
-                           list(SMOOTH_SIGNATURES.values()) + list(REFINE_SENS_SIGNATURES.values())):
+                           list(SMOOTH_SIGNATURES.values()) + list(REFINE_SENS_SIGNATURES.values()) +
+                           list(SMOOTH_SENS_SIGNATURES.values())):
             for name, restype, *argtypes in signatures:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -1580,4 +1591,92 @@ def smooth_legs_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_angles
           _ptr(d_kp_weight, "kp_weight", lf + (4,)), _smooth_options(smooth, max_iter, gtol, ftol),
           _ptr(d_angles_out, "angles_out", lf + (7,)), _ptr(d_frame_info, "frame_info", lf, dtype="int32"),
           _ptr(d_cost, "cost", tl + (2,)), _ptr(d_info, "info", tl + (3,), dtype="int32"),
+          _ptr(d_workspace, "workspace", None, dtype="uint8"), int(workspace_bytes), _stream_ptr(stream))
+
+
+#: entry points of include/seqik_smooth_sensitivity.h (error bars of the smoothed trajectory), additive to ABI 7
+SMOOTH_SENS_EXPORTED_SYMBOLS = [sig[0] for sig in SMOOTH_SENS_SIGNATURES["seqik_smooth_sensitivity.h"]]
+SMOOTH_SENS_MAX_HALF_WIDTH = 32
+SMOOTH_SENS_FLAG_NOT_PD = 1 << 8
+SMOOTH_SENS_FLAG_BAD_INPUT = 1 << 16
+SMOOTH_SENS_FLAG_BAD_SIGMA = 1 << 17
+
+
+def _smooth_vector(smooth):
+    """``smooth`` (a scalar or (7,)) as the ``const double[7]`` of include/seqik_smooth_sensitivity.h."""
+    s = np.asarray(smooth, dtype=np.float64)
+    if s.shape not in ((), (7,)):
+        raise ValueError(f"smooth must be a scalar or (7,), got {s.shape}")
+    return (ctypes.c_double * 7)(*np.broadcast_to(s, (7,)))
+
+
+def smooth_sensitivity_workspace_bytes(n_seq, n_legs, n_frames, half_width=0):
+    """``seqik_smooth_sensitivity_workspace_bytes``: the device workspace ``smooth_sensitivity_device`` needs."""
+    n = (_lib or load()).seqik_smooth_sensitivity_workspace_bytes(int(n_seq), int(n_legs), int(n_frames), int(half_width))
+    if n < 0:
+        _raise(ERR_ARG)
+    return n
+
+
+def smooth_sensitivity(angles, pose, legs, smooth=SMOOTH_DEFAULT, kp_weight=None, kp_sigma=None, half_width=0,
+                       bound_tol=SENS_BOUND_TOL, want_sens=True, want_std=None, want_grad=True, want_flags=True, device=None):
+    """``seqik_smooth_sensitivity`` on host arrays: angles (S, L, N, 7) that minimise the trajectory fit -- the output of
+    ``smooth_legs`` with the same ``smooth`` and ``kp_weight`` -- and the aligned key points (S, L, N, 5, 3) they were
+    fitted to -> dict(sens (S, L, N, 2 W + 1, 7, 4, 3), std (S, L, N, 7), grad (S, L, N), flags (S, L, N) int32; None for
+    what is not asked for), W = ``half_width`` (0..32).
+
+    ``sens[..., t, d, j, k, c]`` is the derivative of angle ``DOFS[j]`` of frame t with respect to component c of aligned
+    key point k + 1 of frame t + d - W: the trajectory fit couples the frames, so an angle answers to the key points of
+    its neighbours too.  A block whose source frame lies outside the recording, or beyond a frame with bad input, is 0.
+    ``std``: the standard deviation of every angle under key-point noise ``kp_sigma`` that is independent between
+    frames, key points and components -- ALL frames' noise, whatever ``half_width``.  THE VALUES ARE THE FIT'S RESPONSE
+    ONLY AT ANGLES THAT MINIMISE IT: ``grad`` (per frame; its maximum over a trajectory is the left side of the gradient
+    test of ``smooth_legs``) tells whether they do.  ``flags``: bits 0..6 DOF held, bit 8 (``SMOOTH_SENS_FLAG_NOT_PD``) the
+    run of frames is not a strict minimum (free rows NaN), bit 16 bad input (the frame's values are NaN), bit 17
+    (``SMOOTH_SENS_FLAG_BAD_SIGMA``) a negative or non-finite sigma (``std`` of the run is NaN).  ``device=None``: the
+    current device."""
+    angles, (S, L, N), _, head = _angles_batch(angles, legs, 0)
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    if pose.shape != (S, L, N, 5, 3):
+        raise ValueError(f"pose must have shape {(S, L, N, 5, 3)}, got {pose.shape}")
+    try:
+        weight = _sigma_batch(kp_weight, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_weight must broadcast to {(S, L, N, 4)}, got {np.shape(kp_weight)}") from None
+    try:
+        sigma = _sigma_batch(kp_sigma, (S, L, N))
+    except ValueError:
+        raise ValueError(f"kp_sigma must broadcast to {(S, L, N, 4)}, got {np.shape(kp_sigma)}") from None
+    if want_std is None:
+        want_std = sigma is not None
+    if want_std and sigma is None:
+        raise ValueError("std needs kp_sigma")
+    W = int(half_width)
+    if not 0 <= W <= SMOOTH_SENS_MAX_HALF_WIDTH:
+        raise ValueError(f"half_width must lie in 0..{SMOOTH_SENS_MAX_HALF_WIDTH}, got {half_width}")
+    sens = np.full((S, L, N, 2 * W + 1, 7, 4, 3), np.nan) if want_sens else None
+    std = np.full((S, L, N, 7), np.nan) if want_std else None
+    grad = np.full((S, L, N), np.nan) if want_grad else None
+    flags = np.zeros((S, L, N), dtype=np.int32) if want_flags else None
+    _call("seqik_smooth_sensitivity", head[0], _data(pose), *head[1:], _data(weight), _data(sigma if want_std else None),
+          _smooth_vector(smooth), float(bound_tol), W, _data(sens), _data(std), _data(grad), _data(flags, _ip),
+          -1 if device is None else int(device))
+    return dict(sens=sens, std=std, grad=grad, flags=flags)
+
+
+def smooth_sensitivity_device(d_angles, d_pose, n_seq, n_legs, n_frames, legs, d_workspace, workspace_bytes, d_kp_weight=0,
+                              d_kp_sigma=0, d_sens=0, d_std=0, d_grad=0, d_flags=0, smooth=SMOOTH_DEFAULT, half_width=0,
+                              bound_tol=SENS_BOUND_TOL, stream=None):
+    """``seqik_smooth_sensitivity_device``: raw device pointers (ints) or torch tensors in the dense layouts of
+    ``include/seqik_smooth_sensitivity.h`` (``d_sens`` (S, L, N, 2 W + 1, 7, 4, 3), ``d_std`` (S, L, N, 7), ``d_grad`` (S,
+    L, N) doubles, ``d_flags`` (S, L, N) int32; 0 / None: all weights 1, not computed, not written; at least one output)
+    and a workspace of ``smooth_sensitivity_workspace_bytes`` bytes, asynchronous on ``stream`` of the current device.
+    Unlike ``smooth_legs_device`` it allocates nothing and waits for nothing: at most five launches, fit for graph
+    capture.  ``d_angles`` may be the output buffer of ``smooth_legs_device`` enqueued before it on the same stream."""
+    lf, head = _angle_map_head(d_angles, n_seq, n_legs, n_frames, legs, 0)
+    W = int(half_width)
+    _call("seqik_smooth_sensitivity_device", head[0], _ptr(d_pose, "pose", lf + (5, 3)), *head[1:],
+          _ptr(d_kp_weight, "kp_weight", lf + (4,)), _ptr(d_kp_sigma, "kp_sigma", lf + (4,)), _smooth_vector(smooth),
+          float(bound_tol), W, _ptr(d_sens, "sens", lf + (2 * W + 1, 7, 4, 3)), _ptr(d_std, "std", lf + (7,)),
+          _ptr(d_grad, "grad", lf), _ptr(d_flags, "flags", lf, dtype="int32"),
           _ptr(d_workspace, "workspace", None, dtype="uint8"), int(workspace_bytes), _stream_ptr(stream))

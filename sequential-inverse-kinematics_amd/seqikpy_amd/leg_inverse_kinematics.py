@@ -556,7 +556,7 @@ class LegInvKinSeq(LegInvKinBase):
 
     def angle_uncertainty(self, key_point_sigma, joint_angles: Optional[Dict[str, np.ndarray]] = None,
                           bound_tol: float = _lib.SENS_BOUND_TOL, fit: str = "sequential",
-                          key_point_weight=None) -> Dict[str, np.ndarray]:
+                          key_point_weight=None, smooth=None) -> Dict[str, np.ndarray]:
         """The standard deviation that key-point noise gives every fitted angle, on the GPU (``seqik_fit_sensitivity``,
         ``std``): ``{"Angle_<leg>_<dof>": (N,)}``, radians.  ``key_point_sigma``: the isotropic standard deviation of key
         points 1..4 (CTr, FTi, TiTa, claw) in the units of the aligned key points -- a scalar, a ``(4,)`` vector, an ``(N,
@@ -566,16 +566,29 @@ class LegInvKinSeq(LegInvKinBase):
         ``fit``: which fit ``joint_angles`` are the answer of.  ``"sequential"`` (default): ``run_ik_and_fk``'s four
         stage solves.  ``"refine"``: the whole-leg fit of ``run_refine`` (``seqik_refine_sensitivity``); pass
         ``run_refine``'s angles as ``joint_angles`` and the ``key_point_weight`` it was run with -- the values are that
-        fit's error bars only at angles that minimise it (``run_refine_sensitivity`` returns ``grad``, which tells)."""
-        if fit not in ("sequential", "refine"):
-            raise ValueError(f"fit must be 'sequential' or 'refine', got {fit!r}")
+        fit's error bars only at angles that minimise it (``run_refine_sensitivity`` returns ``grad``, which tells).
+        ``"smooth"``: the trajectory fit of ``run_smooth`` (``seqik_smooth_sensitivity``); pass ``run_smooth``'s angles
+        and the ``smooth`` (required: the penalty is part of the quantity) and ``key_point_weight`` it was run with.  The
+        penalty couples the frames, so an angle's standard deviation collects the noise of ALL frames' key points, taken
+        as independent between frames; it is as good as the stationarity ``run_smooth`` reached
+        (``run_smooth_sensitivity`` returns ``grad``)."""
+        if fit not in ("sequential", "refine", "smooth") or (fit == "smooth" and smooth is None):
+            raise ValueError(f"fit must be 'sequential', 'refine', or 'smooth' together with smooth= (the penalty the "
+                             f"trajectory was fitted with); got fit={fit!r}, smooth={smooth!r}")
+        if smooth is not None and fit != "smooth":
+            raise ValueError(f"smooth belongs to fit='smooth': fit={fit!r} has no penalty")
+        if fit == "smooth":
+            res_by_segment = self._smooth_sensitivity_outputs(joint_angles, smooth, key_point_weight, key_point_sigma, 0,
+                                                              bound_tol, False, False, False)
+            return {f"Angle_{leg_name}_{dof}": res["std"][:, di].copy() for leg_name, res in res_by_segment.values()
+                    for di, dof in enumerate(DOFS)}
         if fit == "refine":
             res_by_segment = self._refine_sensitivity_outputs(joint_angles, key_point_weight, key_point_sigma, bound_tol,
                                                               False, False, False)
             return {f"Angle_{leg_name}_{dof}": res["std"][:, di].copy() for leg_name, res in res_by_segment.values()
                     for di, dof in enumerate(DOFS)}
         if key_point_weight is not None:
-            raise ValueError("key_point_weight belongs to fit='refine': the sequential fit has no weights")
+            raise ValueError("key_point_weight belongs to fit='refine' and fit='smooth': the sequential fit has no weights")
         out = {}
         for _, (leg_name, res) in self._sensitivity_outputs(joint_angles, key_point_sigma, False, False, bound_tol).items():
             for di, dof in enumerate(DOFS):
@@ -731,7 +744,8 @@ class LegInvKinSeq(LegInvKinBase):
 
     # -- trajectory refinement (include/seqik_smooth.h) ------------------------------------------
     def run_smooth(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, smooth=_lib.SMOOTH_DEFAULT,
-                   key_point_weight=None, export_path: Union[Path, str] = None, **opts) -> Dict[str, np.ndarray]:
+                   key_point_weight=None, export_path: Union[Path, str] = None, key_point_sigma=None,
+                   bound_tol: float = _lib.SENS_BOUND_TOL, **opts) -> Dict[str, np.ndarray]:
         """The whole-leg fit of ``run_refine`` over ALL frames of a leg at once, with a penalty on the change of every
         angle from frame to frame, on the GPU (``seqik_smooth_legs``).
 
@@ -750,7 +764,19 @@ class LegInvKinSeq(LegInvKinBase):
         ``self.joint_angles_dict`` is NOT overwritten.  ``self.smooth_report[leg]`` holds ``cost`` ``(2,)`` -- the
         objective at the clamped start and at the result --, ``reason`` (``_lib.REFINE_STOP_*``), ``steps``,
         ``rejected``, ``frame_info`` ``(N,)`` and ``largest_change`` ``(2,)``: the largest frame-to-frame change of any
-        angle before and after, radians.  ``export_path``: writes ``leg_joint_angles_smooth.pkl`` there."""
+        angle before and after, radians.  ``export_path``: writes ``leg_joint_angles_smooth.pkl`` there.
+
+        The trajectory usually stops on the cost decrease (``reason`` 1), not on the gradient test: the angles are then
+        stationary only as far as ``run_smooth_sensitivity``'s ``grad`` says (both legs of the shipped recording stop with
+        reason 1, at a largest ``grad`` of 3.6e-8 and 5.4e-8 where ``gtol`` is 1e-10).
+
+        ``key_point_sigma`` (as ``angle_uncertainty``'s; default None: nothing changes): the error bars of the smoothed
+        angles in the same visit to the device -- ``seqik_smooth_sensitivity_device`` is enqueued behind
+        ``seqik_smooth_legs_device`` on one stream and reads the angles where the fit left them.
+        ``self.smooth_report[leg]`` then also holds ``std`` ``(N, 7)``, what ``angle_uncertainty(key_point_sigma,
+        smoothed, fit="smooth", smooth=..., key_point_weight=...)`` returns, and ``sens_flags`` ``(N,)``
+        (``_lib.smooth_sensitivity``'s flags; ``bound_tol`` is its held-joint tolerance).  THE ERROR BARS ARE AS GOOD AS
+        THE STATIONARITY THE FIT REACHED."""
         unknown = set(opts) - {"max_iter", "gtol", "ftol"}
         if unknown:
             raise ValueError(f"unknown smoothing options: {sorted(unknown)}")
@@ -758,7 +784,11 @@ class LegInvKinSeq(LegInvKinBase):
         for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
             legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
             weight = self._key_point_weights(items, angles.shape[2], key_point_weight)
-            res = _lib.smooth_legs(angles, pose, legs, smooth=smooth, kp_weight=weight, device=self.device, **opts)
+            if key_point_sigma is None:
+                res = _lib.smooth_legs(angles, pose, legs, smooth=smooth, kp_weight=weight, device=self.device, **opts)
+            else:
+                sigma = self._key_point_sigmas(items, angles.shape[2], key_point_sigma)
+                res = self._smooth_with_error_bars(angles, pose, legs, smooth, weight, sigma, bound_tol, opts)
             for li, (_, leg_name, _, _) in enumerate(items):
                 for di, dof in enumerate(DOFS):
                     angles_out[f"Angle_{leg_name}_{dof}"] = res["angles"][0, li, :, di].copy()
@@ -767,6 +797,8 @@ class LegInvKinSeq(LegInvKinBase):
                 reason, steps, rejected = (int(v) for v in res["info"][0, li])
                 report[leg_name] = dict(cost=res["cost"][0, li].copy(), reason=reason, steps=steps, rejected=rejected,
                                         frame_info=res["frame_info"][0, li].copy(), largest_change=np.array(change))
+                if key_point_sigma is not None:
+                    report[leg_name].update(std=res["std"][0, li].copy(), sens_flags=res["sens_flags"][0, li].copy())
         order = [leg_name for _, leg_name, _ in self._leg_segments()]
         angles_out = {f"Angle_{leg_name}_{dof}": angles_out[f"Angle_{leg_name}_{dof}"] for leg_name in order for dof in DOFS}
         self.smooth_report = {leg_name: report[leg_name] for leg_name in order}
@@ -774,6 +806,70 @@ class LegInvKinSeq(LegInvKinBase):
             save_file(Path(export_path) / "leg_joint_angles_smooth.pkl", angles_out)
             self.logger.info("Smoothed joint angles are saved at %s", export_path)
         return angles_out
+
+    # -- error bars of the smoothed trajectory (include/seqik_smooth_sensitivity.h) ---------------
+    def _smooth_with_error_bars(self, angles, pose, legs, smooth, weight, sigma, bound_tol, opts):
+        """``smooth_legs_device`` then ``smooth_sensitivity_device`` on the same stream: the smoothed angles do not leave
+        the device in between -> the dict of ``_lib.smooth_legs`` plus ``std`` (1, L, N, 7) and ``sens_flags`` (1, L, N)."""
+        import torch
+        S, L, N = angles.shape[:3]
+        dev = torch.device("cuda", torch.cuda.current_device() if self.device < 0 else self.device)
+        with torch.cuda.device(dev):
+            up = lambda a: 0 if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            d_ang, d_pose, d_w, d_sig = up(angles), up(pose), up(weight), up(sigma)
+            d_out = torch.empty((S, L, N, 7), dtype=torch.float64, device=dev)
+            d_finfo = torch.empty((S, L, N), dtype=torch.int32, device=dev)
+            d_cost = torch.empty((S, L, 2), dtype=torch.float64, device=dev)
+            d_info = torch.empty((S, L, 3), dtype=torch.int32, device=dev)
+            d_std = torch.empty((S, L, N, 7), dtype=torch.float64, device=dev)
+            d_flags = torch.empty((S, L, N), dtype=torch.int32, device=dev)
+            ws_bytes = max(_lib.smooth_workspace_bytes(S, L, N), _lib.smooth_sensitivity_workspace_bytes(S, L, N, 0))
+            d_ws = torch.empty((max(ws_bytes, 8),), dtype=torch.uint8, device=dev)   # one workspace, used in turn
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.smooth_legs_device(d_ang, d_pose, S, L, N, legs, d_out, d_ws, ws_bytes, d_kp_weight=d_w,
+                                    d_frame_info=d_finfo, d_cost=d_cost, d_info=d_info, smooth=smooth, stream=stream, **opts)
+            _lib.smooth_sensitivity_device(d_out, d_pose, S, L, N, legs, d_ws, ws_bytes, d_kp_weight=d_w, d_kp_sigma=d_sig,
+                                           d_std=d_std, d_flags=d_flags, smooth=smooth, bound_tol=bound_tol, stream=stream)
+            torch.cuda.synchronize(dev)
+            return dict(angles=d_out.cpu().numpy(), frame_info=d_finfo.cpu().numpy(), cost=d_cost.cpu().numpy(),
+                        info=d_info.cpu().numpy(), std=d_std.cpu().numpy(), sens_flags=d_flags.cpu().numpy())
+
+    def _smooth_sensitivity_outputs(self, joint_angles, smooth, key_point_weight, key_point_sigma, half_width, bound_tol,
+                                    want_sens, want_grad, want_flags):
+        """``_lib.smooth_sensitivity`` per group of legs with the same frame count -> {segment_name: (leg_name, dict)}."""
+        out = {}
+        for items, angles, pose in self._fk_batches(joint_angles, want_pose=True):
+            legs = [self._leg_params(leg_name) for _, leg_name, _, _ in items]
+            n = angles.shape[2]
+            res = _lib.smooth_sensitivity(angles, pose, legs, smooth=smooth,
+                                          kp_weight=self._key_point_weights(items, n, key_point_weight),
+                                          kp_sigma=self._key_point_sigmas(items, n, key_point_sigma), half_width=half_width,
+                                          bound_tol=bound_tol, want_sens=want_sens, want_grad=want_grad,
+                                          want_flags=want_flags, device=self.device)
+            for li, (segment_name, leg_name, _, _) in enumerate(items):
+                out[segment_name] = (leg_name, {k: v[0, li].copy() for k, v in res.items() if v is not None})
+        return {name: out[name] for name, _, _ in self._leg_segments()}
+
+    def run_smooth_sensitivity(self, joint_angles: Optional[Dict[str, np.ndarray]] = None, smooth=_lib.SMOOTH_DEFAULT,
+                               key_point_weight=None, half_width: int = 0,
+                               bound_tol: float = _lib.SENS_BOUND_TOL) -> Dict[str, Dict[str, np.ndarray]]:
+        """How the angles of the trajectory fit (``run_smooth``) move when the key points move, for every leg, on the GPU
+        (``seqik_smooth_sensitivity``): ``{segment_name: dict(sens (N, 2 W + 1, 7, 4, 3), flags (N,), grad (N,))}`` in the
+        order of ``aligned_pos``, W = ``half_width`` (0..32).  ``sens[t, d, j, k, c]`` is the derivative of the angle of
+        ``DOFS[j]`` of frame t with respect to component c of aligned key point k + 1 of frame ``t + d - W``: the penalty
+        couples the frames, so an angle answers to its neighbours' key points too (the blocks fall off with ``|d - W|``;
+        the centre block ``d = W`` is the frame's own).  A block whose source frame lies outside the recording or beyond a
+        NaN frame is 0.
+
+        THE VALUES ARE THE TRAJECTORY FIT'S RESPONSE ONLY AT ANGLES THAT MINIMISE THAT FIT, that is ``run_smooth``'s
+        output: pass it as ``joint_angles`` with the ``smooth`` and ``key_point_weight`` it was run with.  ``grad`` (per
+        frame; its maximum is the left side of ``run_smooth``'s gradient test) tells how far they do -- ``run_smooth``
+        usually stops on the cost decrease, not on the gradient, and the values are as good as that stationarity.
+        ``flags``: bits 0..6 joint held on a limit (its rows are 0), bit 8 the run of frames is not a strict minimum (the
+        free rows are NaN), bit 16 bad input (``_lib.smooth_sensitivity``)."""
+        return {name: res for name, (_, res) in
+                self._smooth_sensitivity_outputs(joint_angles, smooth, key_point_weight, None, half_width, bound_tol, True,
+                                                 True, True).items()}
 
     def _prior_angles(self, leg_name, n_frames, first_stage):
         """(N, 7) array with the columns of stages < first_stage taken from ``joint_angles_dict``
@@ -968,8 +1064,14 @@ class LegInvKinGeneric(LegInvKinBase):
         raise ValueError("the generic chain has no angle sensitivity: it fits seven angles to the three coordinates of the "
                          "claw, so the angles it reports are not a function of the key points (use LegInvKinSeq)")
 
-    def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None, fit="sequential", key_point_weight=None):
+    def angle_uncertainty(self, key_point_sigma, joint_angles=None, bound_tol=None, fit="sequential", key_point_weight=None,
+                          smooth=None):
         """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.angle_uncertainty``)."""
+        return self.run_angle_sensitivity(joint_angles)
+
+    def run_smooth_sensitivity(self, joint_angles=None, smooth=_lib.SMOOTH_DEFAULT, key_point_weight=None, half_width=0,
+                               bound_tol=None):
+        """Not defined for the generic chain: raises ``ValueError`` (see ``LegInvKinSeq.run_smooth_sensitivity``)."""
         return self.run_angle_sensitivity(joint_angles)
 
     def run_refine_sensitivity(self, joint_angles=None, key_point_weight=None, bound_tol=None):
@@ -981,7 +1083,8 @@ class LegInvKinGeneric(LegInvKinBase):
         raise NotImplementedError("the whole-leg refinement is built for the sequential chain only: the generic chain "
                                   "already fits all seven angles at once, to the claw alone (use LegInvKinSeq)")
 
-    def run_smooth(self, joint_angles=None, smooth=_lib.SMOOTH_DEFAULT, key_point_weight=None, export_path=None, **opts):
+    def run_smooth(self, joint_angles=None, smooth=_lib.SMOOTH_DEFAULT, key_point_weight=None, export_path=None,
+                   key_point_sigma=None, bound_tol=None, **opts):
         """Not built for the generic chain: raises ``NotImplementedError`` (see ``LegInvKinSeq.run_smooth``)."""
         raise NotImplementedError("the trajectory refinement is built for the sequential chain only (use LegInvKinSeq)")
 

@@ -36,7 +36,8 @@ class build_py_with_hip(build_py):
         shutil.copy2(lib, os.path.join(dst, os.path.basename(lib)))
         for header in ("seqik.h", "seqik_fk.h", "seqik_gaps.h", "seqik_resample.h", "seqik_frames.h", "seqik_head_align.h",
                        "seqik_resample_der.h", "seqik_stream_gaps.h", "seqik_jacobian.h",
-                       "seqik_sensitivity.h", "seqik_refine.h", "seqik_smooth.h", "seqik_refine_sensitivity.h"):
+                       "seqik_sensitivity.h", "seqik_refine.h", "seqik_smooth.h", "seqik_refine_sensitivity.h",
+                       "seqik_smooth_sensitivity.h"):
             shutil.copy2(os.path.join(ROOT, "include", header), os.path.join(dst, header))
 
 
