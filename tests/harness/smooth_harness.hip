@@ -19,14 +19,62 @@ void size_problem(seqik::SmoothProblem &p, int64_t n_traj, int32_t n_legs, int64
     seqik::smooth_carve(p, ws.data() + (8 - (uintptr_t)ws.data() % 8) % 8);
 }
 
+// smooth_run_host's loop over the same phase functions, looking between the phases at what the rule itself does not
+// report: paths[traj] = {trials lost to a pivot that was not positive, trials lost to an angle outside the domain, the
+// trial round after which the trajectory stopped (0: before any trial)} -> the trial rounds run.  The tests hold its
+// outputs to smooth_run_host's bit for bit.
+int64_t run_watched(const seqik::SmoothProblem &p, int64_t *paths)
+{
+    using namespace seqik;
+    const int64_t R = p.n_traj * p.n_frames;
+    int64_t rounds = 0;
+    std::vector<char> pivot((size_t)p.n_traj);
+    for (int64_t i = 0; i < 3 * p.n_traj; ++i) paths[i] = 0;
+    for (int64_t r = 0; r < R; ++r) smooth_init(p, r);
+    for (int64_t r = 0; r < R; ++r) smooth_start_cost(p, r);
+    smooth_tree_host(p, true);
+    for (int64_t traj = 0; traj < p.n_traj; ++traj) smooth_start(p, traj);
+    for (;;) {
+        for (int64_t r = 0; r < R; ++r) smooth_assemble(p, r);
+        *p.active = 0;
+        for (int64_t traj = 0; traj < p.n_traj; ++traj) {
+            const bool ran = p.traj[traj].status != SMOOTH_STOPPED;
+            smooth_stop(p, traj);
+            if (ran && p.traj[traj].status == SMOOTH_STOPPED) paths[3 * traj + 2] = rounds;
+        }
+        if (*p.active == 0) break;
+        ++rounds;
+        for (int64_t r = 0; r < R; ++r)
+            for (int c = 0; c < kSmoothLanes; ++c) smooth_setup(p, r, c);
+        smooth_solve_host(p);
+        for (int64_t traj = 0; traj < p.n_traj; ++traj) {
+            pivot[traj] = p.traj[traj].status == SMOOTH_TRIAL && (p.traj[traj].flags & SMOOTH_UNUSABLE);
+            paths[3 * traj] += pivot[traj];
+        }
+        for (int64_t r = 0; r < R; ++r) smooth_trial(p, r);
+        for (int64_t traj = 0; traj < p.n_traj; ++traj)
+            paths[3 * traj + 1] += p.traj[traj].status == SMOOTH_TRIAL && (p.traj[traj].flags & SMOOTH_UNUSABLE) && !pivot[traj];
+        smooth_tree_host(p, false);
+        for (int64_t traj = 0; traj < p.n_traj; ++traj) {
+            const bool ran = p.traj[traj].status == SMOOTH_TRIAL;
+            if (smooth_decide(p, traj))
+                for (int64_t i = traj * p.n_frames * 7; i < (traj + 1) * p.n_frames * 7; ++i) p.q[i] = p.qn[i];
+            if (ran && p.traj[traj].status == SMOOTH_STOPPED) paths[3 * traj + 2] = rounds;
+        }
+    }
+    for (int64_t r = 0; r < R; ++r) smooth_finish(p, r);
+    return rounds;
+}
+
 }  // namespace
 
 // The layouts of include/seqik_smooth.h with the options spelled out; *rounds (nullable) receives the trial rounds run.
 // The segment lengths are taken as they are (the C ABI refuses a non-finite one before it reaches the rule).
-extern "C" int harness_smooth_legs(const double *angles, const double *pose, int64_t n_seq, int32_t n_legs, int64_t n_frames,
-                                   const SeqikLegParams *legs, const double *kp_weight, const double *smooth,
-                                   int32_t max_iter, double gtol, double ftol, double *angles_out, int32_t *frame_info,
-                                   double *cost, int32_t *info, int64_t *rounds)
+// `paths` (nullable, [n_seq * n_legs][3]): the decision paths each trajectory took, see run_watched.
+extern "C" int harness_smooth_legs_paths(const double *angles, const double *pose, int64_t n_seq, int32_t n_legs,
+                                         int64_t n_frames, const SeqikLegParams *legs, const double *kp_weight,
+                                         const double *smooth, int32_t max_iter, double gtol, double ftol, double *angles_out,
+                                         int32_t *frame_info, double *cost, int32_t *info, int64_t *rounds, int64_t *paths)
 {
     if (!angles || !pose || !angles_out || !legs || !smooth || max_iter < 1 || max_iter > 1000 || n_legs < 1 || n_legs > 8)
         return SEQIK_ERR_BAD_ARG;
@@ -42,9 +90,18 @@ extern "C" int harness_smooth_legs(const double *angles, const double *pose, int
         seqik::make_fk_leg(legs[l < n_legs ? l : 0], p.legs[l]);
         seqik::make_leg_bounds(legs[l < n_legs ? l : 0], p.bounds[l]);
     }
-    const int64_t r = seqik::smooth_run_host(p);
+    const int64_t r = paths ? run_watched(p, paths) : seqik::smooth_run_host(p);
     if (rounds) *rounds = r;
     return SEQIK_OK;
+}
+
+extern "C" int harness_smooth_legs(const double *angles, const double *pose, int64_t n_seq, int32_t n_legs, int64_t n_frames,
+                                   const SeqikLegParams *legs, const double *kp_weight, const double *smooth,
+                                   int32_t max_iter, double gtol, double ftol, double *angles_out, int32_t *frame_info,
+                                   double *cost, int32_t *info, int64_t *rounds)
+{
+    return harness_smooth_legs_paths(angles, pose, n_seq, n_legs, n_frames, legs, kp_weight, smooth, max_iter, gtol, ftol,
+                                     angles_out, frame_info, cost, info, rounds, nullptr);
 }
 
 // The linear solve alone, one trajectory: rows [n][154] (D 49 row-major of which the lower triangle is read, L 49, U 49,

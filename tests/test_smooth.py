@@ -7,7 +7,9 @@ and on the shipped recording, run on the host (tests/harness/smooth_harness.hip)
 ``_lib.smooth_legs``, ``LegInvKinSeq.run_smooth`` -- with the library call answered by the host-run rule.  GPU tier
 (``-m gpu``): every output of the kernels against the host-run rule bit for bit, with guard records around every buffer
 and the workspace, over frame counts whose strides cross wavefront and workgroup seams, with the default plan and with one
-workgroup of 64 lanes; both entry points; 600 frames of the shipped recording.
+workgroup of 64 lanes; both entry points; 600 frames of the shipped recording; the decision batch -- rejected trials,
+reasons 0, 1, 2 and 4, trajectories stopping in different rounds, asserted on the host-run rule first -- run to its natural
+end; a converged batch fed back; 1025 and 2049 frames (eleven and twelve strides); 2 x 3 x 513 frames on one wavefront.
 
 Against scipy on the stacked problem: tests/test_smooth_accuracy.py."""
 import ctypes
@@ -445,7 +447,59 @@ def made_up_batch(seed, S, L, N):
     return ang, pose, weight, np.array(segs), np.array(bounds)
 
 
+WIDE_LIMIT, GLITCH = 1e10, 1e30
+
+
+def decision_batch(seed, S=3, L=3, N=24):
+    """made_up_batch with two changes that open the rule's rarest path: the last leg has no limits to speak of (+-1e10,
+    beyond the angle domain of 2^30) and one key point of one frame of its middle trajectory is a tracking glitch at 1e30.
+    From there every step leaves the angle domain whatever the damping, so every trial is unusable and the trajectory
+    ends on reason 2 after 25 rejections, at a finite cost."""
+    ang, pose, weight, segs, bounds = made_up_batch(seed, S, L, N)
+    bounds[L - 1] = np.stack([np.full(7, -WIDE_LIMIT), np.full(7, WIDE_LIMIT)], 1)
+    pose[S // 2, L - 1, N // 2 - 1, 4, 0] = GLITCH
+    return ang, pose, weight, segs, bounds
+
+
+# the batch whose trajectories take every decision path the rule has between them (found by a search over seeds on the
+# host-run rule; tests/test_smooth_accuracy.py::test_decision_paths_are_taken asserts that they do), and its options
+DECISION_SEED, DECISION_OPTS = 8, dict(smooth=1.0, gtol=1e-5)
+
 _CASES = {}
+
+
+def decision_case(sh):
+    """The decision batch, the host-run rule's answer with the paths it took (the harness's watched loop) and the answer of
+    smooth_run_host itself, computed once."""
+    if "decision" not in _CASES:
+        ang, pose, weight, segs, bounds = decision_batch(DECISION_SEED)
+        watched = sh.run(ang, pose, segs, bounds, weight=weight, paths=True, **DECISION_OPTS)
+        ref = sh.run(ang, pose, segs, bounds, weight=weight, **DECISION_OPTS)
+        _CASES["decision"] = (ang, pose, weight, segs, bounds, watched, ref)
+    return _CASES["decision"]
+
+
+def assert_decision_paths(watched):
+    """The paths the decision batch is there for, on the host-run rule's record of it."""
+    info, paths = watched["info"].reshape(-1, 3), watched["paths"].reshape(-1, 3)
+    why, steps, rejected = info.T
+    assert sorted(set(why.tolist())) == [0, 1, 2, 4]
+    # (a) rejected trials -- `lambda * 4`, no copy of qn, the next ASSEMBLE skips the trajectory -- in trajectories that
+    # went on to accept steps afterwards
+    assert ((rejected > 50) & (steps > 50)).sum() >= 4
+    # (b) a pivot that is not positive does not occur in the whole rule (see test_smooth_accuracy.test_decision_paths_are_taken)
+    assert not paths[:, 0].any()
+    # (c) reason 2: damping exhausted by 25 unusable trials in a row, each lost to an angle outside the domain
+    assert np.array_equal(info[why == 2], [[2, 0, 25]]) and np.array_equal(paths[why == 2], [[0, 25, 25]])
+    assert not paths[why != 2, 1].any()
+    # (d) trajectories of one batch stop in different rounds: reason 0 and reason 1 at least 5 rounds apart, and others
+    # go on long after the first has stopped
+    assert min(abs(int(a) - int(b)) for a in paths[why == 0, 2] for b in paths[why == 1, 2]) >= 5
+    assert len(set(paths[:, 2].tolist())) >= 6 and paths[:, 2].min() == 25 and watched["rounds"] == paths[:, 2].max() > 500
+    assert (steps[why == 0] > 50).all()                              # the gradient test was met by work, not at the start
+    # (e) reason 4 on the default cap
+    assert (why == 4).sum() >= 2 and (steps[why == 4] == MAX_ITER).all()
+    assert (paths[:, 2] == steps + rejected).all()                   # a trial per round until it stops
 
 
 def case(sh, S, L, N, seed, **opts):
@@ -525,6 +579,78 @@ def test_gpu_kernels_equal_the_host_rule_bit_for_bit(lib, smooth_harness, N):  #
                        (N, "one workgroup of 64"))
     if N == 65:
         assert_equals_host(device_run(lib, ang, pose, weight, segs, bounds, max_iter=30, in_place=True), ref, (N, "in place"))
+
+
+@pytest.mark.gpu
+def test_gpu_decision_paths_equal_the_host_rule(lib, smooth_harness):  # noqa: F811
+    """The decision batch of tests/test_smooth_accuracy.py::test_decision_paths_are_taken on the kernels, run to its natural end (543 rounds of 16
+    launches): rejected trials, damping exhausted, the cap, and trajectories that stop in nine different rounds, so the
+    decide kernel's "not accepted" branch and the early return of a stopped trajectory's rows run in every phase.  That
+    the paths are taken is asserted on the host-run reference first."""
+    ang, pose, weight, segs, bounds, watched, ref = decision_case(smooth_harness)
+    assert_decision_paths(watched)
+    assert equal_runs(watched, ref)
+    assert_equals_host(device_run(lib, ang, pose, weight, segs, bounds, **DECISION_OPTS), ref, "decision batch, default plan")
+    assert_equals_host(device_run(lib, ang, pose, weight, segs, bounds, env=ONE_SMALL_WORKGROUP, **DECISION_OPTS), ref,
+                       "decision batch, one workgroup of 64")
+
+
+@pytest.mark.gpu
+def test_gpu_a_converged_batch_comes_back_as_its_bits(lib, smooth_harness):  # noqa: F811
+    """The decision batch's result fed back in.  Its two trajectories of the last sequence that stopped on the gradient
+    (two legs; one with the plane of weights and the weightless NaN key point), as a batch of their own: every trajectory
+    stops in the first STOP phase, no trial round launches, the output is the input's bits and info is (0, 0, 0).  (The
+    whole result is no converged batch: a trajectory that ended on the cap goes on, the one on reason 2 spends its 25
+    trials again, one that stalled tries once more.  It is run too, against the host rule.)"""
+    ang, pose, weight, segs, bounds, _, first = decision_case(smooth_harness)
+    S = ang.shape[0]
+    assert (first["info"][S - 1, :2, 0] == 0).all()
+    sub = (first["angles"][S - 1:, :2], pose[S - 1:, :2], weight[S - 1:, :2], segs[:2], bounds[:2])
+    ref = smooth_harness.run(sub[0], sub[1], sub[3], sub[4], weight=sub[2], **DECISION_OPTS)
+    assert ref["rounds"] == 0 and (ref["info"] == 0).all()
+    for env in (None, ONE_SMALL_WORKGROUP):
+        got = device_run(lib, *sub, env=env, **DECISION_OPTS)
+        assert_equals_host(got, ref, ("converged", env))
+        assert same_bits(got["angles"], sub[0]) and (got["info"] == 0).all()
+        assert same_bits(got["cost"], first["cost"][S - 1:, :2, [1, 1]])
+        assert np.array_equal(got["frame_info"], first["frame_info"][S - 1:, :2])
+    again = smooth_harness.run(first["angles"], pose, segs, bounds, weight=weight, **DECISION_OPTS)
+    stopped_at_once = (again["info"][..., 1:] == 0).all(-1)
+    assert stopped_at_once.sum() >= 3 and (again["info"][stopped_at_once, 0] <= 1).all() and not stopped_at_once.all()
+    got = device_run(lib, first["angles"], pose, weight, segs, bounds, **DECISION_OPTS)
+    assert_equals_host(got, again, "the whole result fed back")
+    assert same_bits(got["angles"][stopped_at_once], first["angles"][stopped_at_once])
+
+
+LONG = ((1025, 60), (2049, 40))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,max_iter", LONG)
+def test_gpu_eleven_and_twelve_strides(lib, smooth_harness, N, max_iter):  # noqa: F811
+    """RF 0:1025 and 0:2049 of the shipped recording against the host rule bit for bit, with guards: one frame past a
+    power of two, so n_pad is 2048 and 4096 and the last of the eleven and twelve strides reduces a single pair.
+
+    The cap on the accepted steps (LONG: 60 and 40).  A trial round is 6 + 2 ceil(log2 N) launches, 28 and
+    30 here, at the measured 15 us each 0.42 and 0.45 ms: 60 and 40 rounds are 25 and 18 ms of kernels, and by launches
+    alone a cap in the thousands would fit a second.  What a round costs in this test is the host-run reference, about 25
+    and 50 ms per round at these sizes; 60 and 40 rounds keep it to 1.5 and 2 s, and that is what sets the caps."""
+    ang, pose, seg, bounds = shipped_window("RF", 0, N)
+    ref = smooth_harness.run_one(ang, pose, seg, bounds, max_iter=max_iter)
+    assert tuple(ref["info"][:2]) == (4, max_iter) and ref["cost"][1] < ref["cost"][0] and ref["rounds"] >= max_iter
+    got = device_run(lib, ang[None, None], pose[None, None], None, [seg], [bounds], max_iter=max_iter)
+    assert_equals_host({k: v[0, 0] for k, v in got.items()}, ref, f"RF 0:{N}")
+
+
+@pytest.mark.gpu
+def test_gpu_many_trips_of_the_grid_stride_loop_at_stride_512(lib, smooth_harness):  # noqa: F811
+    """2 x 3 trajectories of 513 frames (ten strides, the last of 512 frames reduces one pair per trajectory) on one
+    workgroup of 64 lanes: the eight-lanes-per-row phases walk 24 624 items in 385 trips of the grid-stride loop.  Six
+    accepted steps at the most, which with the rejections between them are 16 rounds: one wavefront does all the work."""
+    ang, pose, weight, segs, bounds, ref = case(smooth_harness, 2, 3, 513, 700 + 513, max_iter=6)
+    assert (ref["info"][..., 1] > 0).all() and ref["rounds"] >= 6 and (ref["frame_info"] == BAD_INPUT).sum() == 1
+    assert_equals_host(device_run(lib, ang, pose, weight, segs, bounds, max_iter=6, env=ONE_SMALL_WORKGROUP), ref,
+                       "513 frames, one workgroup of 64")
 
 
 @pytest.mark.gpu
